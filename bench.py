@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: analysis+synthesis frames/sec, 48 kHz, 5 ms hop (BASELINE.json `metric`).
 
-    python bench.py --gpus N --steps K --warmup W [--gather f0|y]
+    python bench.py --gpus N --steps K --warmup W [--gather f0|y] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the whole hot path Harvest -> CheapTrick -> D4C -> Synthesis (demo order of
 reference test/test.cpp:288-384) over this rank's batch of synthetic 48 kHz 10 s utterances, inputs
@@ -14,9 +14,21 @@ utterances is dealt to the ranks by world_class_amd.shard.partition; utterances 
 no data-path collective (weak scaling), and the only collective is the final RCCL all-gather of the F0
 contours and output checksums (--gather y: of the waveforms too, BASELINE config 4's gather), timed inside
 the measured region and reported separately as `gather_ms`.  `value` = frames of all ranks / max-over-ranks
-wall time.
+wall time, `ms_per_step` = that wall time / K.
 
-At N = 1 rank 0 adds, outside the timed region:
+A plain run does only what the headline needs: set-up, W untimed steps, K timed steps, the outputs (--dump-outputs) and
+the result line.  --dump-outputs DIR writes what the last timed step returned (rank 0's share when N > 1) as float64
+DIR/<name>.npy, at most 64 MB in all: tpos, f0 and the row sums of the spectrogram (sp) and aperiodicity (ap) of every
+frame, 2048 rows of sp and ap, 2^20 samples of the waveform y; rows and samples at positions drawn with a fixed seed
+(all of them where there are fewer; frames too beyond 2^19).  The inputs are seeded, so the same arguments give the
+same inputs on every run and every build.
+
+--full adds the following after the timed region.  --no-extras, --no-cpu-baseline and --no-serialised leave parts out.
+  ties            the same step with one utterance forced onto the Harvest tie path (N = 1)
+  roofline        every kernel of a step alone on the chip (the serialised pass; --no-serialised: the kernels' times inside
+                  the timed steps), priced on profiles/pmc_traffic.json and profiles/issue_rates.json
+
+At N = 1 rank 0 adds as well, with --full:
   stages          the other BASELINE configs on this GPU: config 3 (256 x 48 kHz 10 s, CheapTrick only, against the HBM
                   roofline on B_ct), config 2 (64 x 16 kHz 10 s, full pipeline), config 4 (one GPU's share of 1024
                   utterances, Synthesis only), config 5 (one GPU's share of 4096 streams, 1 ms hop, chunked Harvest +
@@ -458,6 +470,37 @@ def serialised_kernels(w, L, d_x, x_len, d_t, d_f, f_len, d_sp, d_ap, y_len, d_y
     return best
 
 
+DUMP_SEED = 20240611
+DUMP_FRAMES = 1 << 19      # per-frame arrays (tpos, f0, row sums): every frame up to this many
+DUMP_ROWS = 2048           # rows of sp and ap
+DUMP_SAMPLES = 1 << 20     # waveform samples
+
+
+def _positions(n, k, seed):
+    """all of range(n) when n <= k, else k sorted positions drawn without replacement with a fixed seed"""
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(n, k, replace=False)).astype(np.int64)
+
+
+def dump_outputs(path, torch, dev, frames, bins, d_t, d_f, d_sp, d_ap, d_y):
+    """--dump-outputs: the outputs of the last timed step as float64 DIR/<name>.npy (module docstring); returns the bytes written"""
+    sp, ap = d_sp.view(frames, bins), d_ap.view(frames, bins)
+    fi = torch.from_numpy(_positions(frames, DUMP_FRAMES, DUMP_SEED)).to(dev)
+    ri = torch.from_numpy(_positions(frames, DUMP_ROWS, DUMP_SEED + 1)).to(dev)
+    yi = torch.from_numpy(_positions(d_y.numel(), DUMP_SAMPLES, DUMP_SEED + 2)).to(dev)
+    arrays = {"tpos": d_t.index_select(0, fi), "f0": d_f.index_select(0, fi),
+              "sp_rowsum": sp.sum(1).index_select(0, fi), "ap_rowsum": ap.sum(1).index_select(0, fi),
+              "sp_rows": sp.index_select(0, ri), "ap_rows": ap.index_select(0, ri), "y": d_y.index_select(0, yi)}
+    arrays = {k: v.to(torch.float64).cpu().numpy() for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= 64 * 10 ** 6, f"--dump-outputs would write {total} bytes"
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+    return total
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -470,13 +513,20 @@ def main():
     ap.add_argument("--share-gpu", action="store_true",
                     help="test mode: all ranks on device 0 under a gloo group (RCCL does not form a group of several ranks on one device); "
                          "exercises the sharded code path on a one-GPU box and reports n_gpus = 1")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the stages / with_transfers blocks (N = 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float64, at most 64 MB; see the module docstring)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else the benchmark measures: ties, roofline (serialised kernel pass), stages, "
+                         "with_transfers, cpu_baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the ties / stages / with_transfers blocks (N = 1)")
     ap.add_argument("--no-serialised", action="store_true",
-                    help="skip the serialised kernel pass (the counter passes of tools/profile_round.sh: every kernel launch of the process "
-                         "must belong to a pipeline step, the counters are divided by the number of steps); roofline.kernel_ms then comes "
-                         "from the overlapped step's events")
+                    help="with --full: skip the serialised kernel pass (the counter passes of tools/profile_round.sh: every kernel launch of "
+                         "the process must belong to a pipeline step, the counters are divided by the number of steps); roofline.kernel_ms "
+                         "then comes from the overlapped step's events")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         spawn_ranks(a, sys.argv[1:])
@@ -596,10 +646,12 @@ def main():
         total_frames = sum_over_ranks(frames, cdev)
     else:
         total_frames = frames
+    if a.dump_outputs and rank == 0:  # (before --full's passes, which run the path again and overwrite the outputs)
+        dump_outputs(a.dump_outputs, torch, dev, frames, bins, d_t, d_f, d_sp, d_ap, d_y)
 
     # What a tie costs (round-5 verdict, item 3): the same step with ONE of its utterances forced onto the tie flag -- that
     # utterance goes through the whole path once more by itself, the band-pass as direct FIR sums; everything else stands
-    if rank == 0 and world == 1 and not a.no_extras:
+    if rank == 0 and world == 1 and a.full and not a.no_extras:
         try:
             pipe.set_option("force_tie", str(n_utt // 3))
             step(); barrier()
@@ -629,7 +681,7 @@ def main():
     # 2.6 GB of page-locked buffers -- freeing tens of GB of device memory and pageable uploads leave this ROCm's copy path in a
     # slower state for the rest of the process (cause not found).
     host_first = {}
-    if rank == 0 and world == 1 and not a.no_extras:
+    if rank == 0 and world == 1 and a.full and not a.no_extras:
         try:  # (the unchanged caller's view)
             host_first["stages"] = {"dropin_single_utterance": stage_dropin(w, L, xs[0])}
         except Exception as e:
@@ -646,7 +698,7 @@ def main():
     # ... and the same kernels one after the other, each alone on the chip, one launch for the whole batch: the times the roofline
     # figures are priced on (no schedule effects, no exclusion list)
     kern = {}
-    if rank == 0:
+    if rank == 0 and a.full:
         kern = dict(kern_overlapped) if a.no_serialised else serialised_kernels(w, L, d_x, x_len, d_t, d_f, f_len, d_sp, d_ap, y_len, d_y, pipe.fft_size)
 
     if rank == 0:
@@ -737,7 +789,7 @@ def main():
             out["gather_ms"] = gather_s[0] * 1e3
             out["gather"] = a.gather
             out["ranks"] = world
-        if world == 1 and not a.no_extras:
+        if world == 1 and a.full and not a.no_extras:
             # (the host-memory measurements first: behind the config 4 / config 5 stages below the host front-end measured 10 - 25 ms
             # more in this process, and the drop-in caller 9 ms more behind the front-end's 2.6 GB of page-locked buffers -- large
             # host allocations and pageable uploads leave this ROCm's copy path in a slower state; cause not found)
@@ -790,7 +842,7 @@ def main():
             out["config"]["also_measured"] = also
             if out["roofline"] is not None:
                 out["roofline"]["also_measured"] = also
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(list(cache.values()))
             except Exception as e:  # the GPU number stays valid without it

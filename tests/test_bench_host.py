@@ -42,3 +42,29 @@ def test_cpu_baseline_leg_on_a_tiny_sample():
     frames, t0, t1 = bench._ref_call(([x, x], 2))
     assert frames == 2 * (int(1000.0 * len(x) / bench.FS / 5.0) + 1) and t1 > t0
     assert bench.usable_cores() >= 1
+
+
+def test_dump_outputs_samples_with_a_fixed_seed_and_stays_under_64_mb(tmp_path):
+    import torch
+    # the largest dump any workload can write (48 kHz: 1025 bins)
+    assert 4 * 8 * bench.DUMP_FRAMES + 2 * 8 * bench.DUMP_ROWS * 1025 + 8 * bench.DUMP_SAMPLES <= 64 * 10 ** 6
+    frames, bins, n_y = bench.DUMP_FRAMES + 5, 3, bench.DUMP_SAMPLES + 7  # one past every limit: all four get sampled
+    g = torch.Generator().manual_seed(1)
+    d_t, d_f = torch.arange(frames, dtype=torch.float64), torch.rand(frames, dtype=torch.float64, generator=g)
+    d_sp, d_ap = torch.rand(frames * bins, dtype=torch.float64, generator=g), torch.rand(frames * bins, dtype=torch.float64, generator=g)
+    d_y = torch.rand(n_y, dtype=torch.float64, generator=g)
+    total = bench.dump_outputs(str(tmp_path / "a"), torch, torch.device("cpu"), frames, bins, d_t, d_f, d_sp, d_ap, d_y)
+    bench.dump_outputs(str(tmp_path / "b"), torch, torch.device("cpu"), frames, bins, d_t, d_f, d_sp, d_ap, d_y)
+    names = {"tpos", "f0", "sp_rowsum", "ap_rowsum", "sp_rows", "ap_rows", "y"}
+    assert {f[:-4] for f in os.listdir(tmp_path / "a")} == names
+    got = {k: np.load(tmp_path / "a" / (k + ".npy")) for k in names}
+    assert all(v.dtype == np.float64 for v in got.values()) and sum(v.nbytes for v in got.values()) == total
+    for k in names:  # the same arguments, the same positions
+        assert np.array_equal(got[k], np.load(tmp_path / "b" / (k + ".npy")))
+    fi = got["tpos"].astype(np.int64)  # (tpos = frame index here)
+    assert len(fi) == bench.DUMP_FRAMES and np.all(np.diff(fi) > 0)
+    sp = d_sp.numpy().reshape(frames, bins)
+    assert np.array_equal(got["f0"], d_f.numpy()[fi]) and np.allclose(got["sp_rowsum"], sp.sum(1)[fi], rtol=1e-15)
+    assert got["sp_rows"].shape == got["ap_rows"].shape == (bench.DUMP_ROWS, bins) and got["y"].shape == (bench.DUMP_SAMPLES,)
+    assert all(np.any(np.all(sp == r, axis=1)) for r in got["sp_rows"][:16])
+    assert np.isin(got["y"], d_y.numpy()).all()

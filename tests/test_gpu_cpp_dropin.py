@@ -76,8 +76,8 @@ def test_reference_demo_unchanged_on_the_product(golden, port, tmp_path):
     c = golden.case("c1_16k_2s_floor40")
     fs = int(c["fs"])
     wio.wavwrite(c["x"][:fs], fs, tmp_path / "in.wav")
-    subprocess.run([exe, str(tmp_path / "in.wav"), str(tmp_path / "out"), "1.2", "0.9"], check=True, cwd=tmp_path,
-                   stdout=subprocess.DEVNULL)
+    # (names relative to cwd: the demo builds its output name in a char[100], which a long temporary directory overflows)
+    subprocess.run([exe, "in.wav", "out", "1.2", "0.9"], check=True, cwd=tmp_path, stdout=subprocess.DEVNULL)
     x = port_io.pcm16_of(c["x"][:fs]) / 32768.0
     port.rng_reset()
     tpos, f0 = port.harvest(x, fs, f0_floor=40.0)

@@ -1,9 +1,9 @@
 #!/bin/bash
-# Copies what tools/evidence_round.sh TAG left under gpurun_out/ into profiles/ under the names profiles/README.md lists:
+# Copies what tools/evidence_round.sh TAG left under $OUT_ROOT (default out/) into profiles/ under the names profiles/README.md lists:
 #   bash tools/collect_profiles.sh r04_a
 set -u
 T=$1
-G=gpurun_out
+G=${OUT_ROOT:-out}
 P=profiles
 cp $G/${T}_bench.json $P/${T}_bench_as_run.json
 cp $G/$T/stats_bench.json $P/${T}_bench_under_rocprof.json
