@@ -83,9 +83,66 @@ int wc_stream_push_device_fmt(wc_stream *s, const void *d_chunk, int chunk_forma
  * from; set it to continue the numbering of an earlier analysis (e.g. the value wc_rng_get_position() reports after one). */
 unsigned long long wc_stream_rng_position(const wc_stream *s, int stream);
 int wc_stream_set_rng_position(wc_stream *s, int stream, unsigned long long position);
+/* Aperiodicity (opt-in, before the first push; a negative threshold switches it off again): D4C (wc_d4c_create's threshold) runs on the
+ * frames each push commits, on the same window batch and whole-ms relative times as CheapTrick, with a noise position of its own
+ * per stream.  Needs lookback and lookahead of at least 38 ms (D4C's and LoveTrain's windows reach 37.5 ms either side of a frame).
+ * What cannot be exact: a whole-utterance D4C takes its LoveTrain draws for ALL frames before any main-pass draw (reference
+ * src/d4c.cpp:113-160), and a stream cannot know where that boundary falls, so each push's frames draw their LoveTrain noise and
+ * then their main-pass noise from the stream's D4C position.  The noise has amplitude kMySafeGuardMinimum (1e-12): against one
+ * whole-utterance D4C on the stream's committed F0 the LoveTrain voicing is identical and ap within 1e-7.  Without the option
+ * nothing changes.  With it, push through wc_stream_push_device_ex (d_ap: rows of fft_size/2+1, packed like d_sp). */
+int wc_stream_set_aperiodicity(wc_stream *s, double d4c_threshold);
+int wc_stream_push_device_ex(wc_stream *s, const void *d_chunk, int chunk_format, const int *n_new, const int *flush, double *d_tpos,
+                             double *d_f0, double *d_sp, double *d_ap, int *frames_out);
+/* D4C's noise position of stream u (0 after creation and reset) */
+unsigned long long wc_stream_d4c_rng_position(const wc_stream *s, int stream);
+int wc_stream_set_d4c_rng_position(wc_stream *s, int stream, unsigned long long position);
 /* frames committed so far / samples received so far for stream u */
 long long wc_stream_frames_committed(const wc_stream *s, int stream);
 long long wc_stream_samples_received(const wc_stream *s, int stream);
+
+/* ---- Chunked Synthesis for many concurrent streams (extension) ----
+ *
+ * Stream u receives frames 0, 1, 2, ... (f0, spectrogram row, aperiodicity row of fft_size/2+1) in order, frame k at time
+ * k * frame_period.  The samples it commits are the samples of ONE wc_synthesis_compute_device call over all of its frames
+ * (out_length = wc_synthesis_out_length(total frames), noise from the stream's position, which is 0 after create and reset):
+ * at fft_size 1024 and 2048 bit for bit with the batch's default path (the same response rows summed in the same pulse order;
+ * the batch's A/B variants WC_SYN_IMPL=block and WC_SYN_OLA=atomic, and batches whose rows exceed its row budget, add with FP64
+ * atomics instead and agree within 1e-12), at 512 and 4096 within 1e-12 (the batch's block kernels add with FP64 atomics there).  Every output sample is committed exactly once and in order, as
+ * soon as no later frame can change it (reference src/synthesis.cpp):
+ *   - sample i's F0 / VUV interpolates frames floor(i / fs / frame_period) and the one after it (:180-243): it is final once
+ *     i / fs < (F - 1) * frame_period for F frames received; the extrapolated point at f0_length exists only at the flush;
+ *   - a pulse at sample i is found when sample i + 1 is final (:264-283); its noise_size needs the NEXT pulse (:106-107), so
+ *     the newest pulse waits for its successor (the last pulse of the utterance gets 0 at the flush);
+ *   - a pulse's response covers samples index - fft_size/2 + 1 .. index + fft_size/2 (:118-139).
+ * So after a push with F frames received the stream has committed every sample below  min(P, E - 1) - fft_size/2 + 1,  where E
+ * is the first sample at or after (F - 1) frame periods and P the waiting pulse.  Latency bound (tested): committed >=
+ * (F - 2) * frame_period * fs - gap - fft_size/2, with the pulse gap at most 2 fs / (fs/fft_size + 1) samples in voiced
+ * stretches (the interpolated F0 stays above half the lowest F0) and fs/500 in unvoiced ones: about one frame period, plus the
+ * current pulse gap, plus fft_size/2 samples.  A flush commits everything up to wc_synthesis_out_length; a stream with fewer
+ * than two frames when flushed is an error.  Streams need not move in lockstep; a push that fails leaves every stream as it
+ * was.  A stream holds at most 2^31 samples (the reference's int indices).
+ *
+ * Per stream the handle carries the absolute next sample, the total and wrapped phase of the last final sample (the reference's
+ * sequential sum continued bit for bit), the waiting pulse, the noise position, a window of the frames that pending samples and
+ * pulses still need, and the partial sums of samples that final pulses have reached but later ones may still reach.
+ */
+typedef struct wc_synth_stream wc_synth_stream;
+/* fft_size 512, 1024, 2048 or 4096 (as wc_synthesis_create); max_frames_per_push: most frames one push gives one stream */
+wc_synth_stream *wc_synth_stream_create(int fs, int fft_size, double frame_period_ms, int n_streams, int max_frames_per_push);
+void wc_synth_stream_destroy(wc_synth_stream *s);
+int wc_synth_stream_max_samples_per_push(const wc_synth_stream *s);  /* d_y capacity per stream */
+int wc_synth_stream_reset(wc_synth_stream *s, int stream);
+/* n_frames: host array, frames appended per stream (0 = idle).  The frames are packed back to back in d_f0 / d_sp / d_ap (rows of
+ * fft_size/2+1), as wc_stream_push_device packs the frames it commits.  flush: host flags or NULL.  d_y: the committed samples,
+ * packed by samples_out[u] (host array). */
+int wc_synth_stream_push_device(wc_synth_stream *s, const int *n_frames, const int *flush, const double *d_f0, const double *d_sp,
+                                const double *d_ap, double *d_y, int *samples_out);
+/* noise position of stream u: where its next (or waiting) pulse takes its draws */
+unsigned long long wc_synth_stream_rng_position(const wc_synth_stream *s, int stream);
+int wc_synth_stream_set_rng_position(wc_synth_stream *s, int stream, unsigned long long position);
+long long wc_synth_stream_frames_received(const wc_synth_stream *s, int stream);
+long long wc_synth_stream_samples_committed(const wc_synth_stream *s, int stream);
 
 #ifdef __cplusplus
 }

@@ -1311,7 +1311,7 @@ int ct_prepare(wc_cheaptrick *c, hipStream_t s, int n_utt, const int *x_length, 
 		if (x_length[u] <= 0 || f0_length[u] < 0) return fail(WC_ERR_INVALID, "cheaptrick: non-positive length");
 		UttDesc &d = utts[u];
 		d.x_off = xo; d.f_off = fo; d.y_off = 0;
-		d.x_len = x_length[u]; d.f_len = f0_length[u]; d.y_len = 0; d.pad = 0;
+		d.x_len = x_length[u]; d.f_len = f0_length[u]; d.y_len = 0; d.f_base = 0;
 		d.rng_pos = rng_pos ? rng_pos[u] : 0ull;
 		xo += x_length[u];
 		fo += f0_length[u];

@@ -1941,7 +1941,7 @@ int d4c_enqueue(wc_d4c *d, hipStream_t s, int n_utt, const double *d_x, const in
 		if (x_length[u] <= 0 || f0_length[u] < 0) return fail(WC_ERR_INVALID, "d4c: non-positive length");
 		UttDesc &t = utts[u];
 		t.x_off = xo; t.f_off = fo; t.y_off = 0;
-		t.x_len = x_length[u]; t.f_len = f0_length[u]; t.y_len = 0; t.pad = 0;
+		t.x_len = x_length[u]; t.f_len = f0_length[u]; t.y_len = 0; t.f_base = 0;
 		t.rng_pos = rng_pos ? rng_pos[u] : 0ull;
 		xo += x_length[u];
 		fo += f0_length[u];

@@ -106,7 +106,8 @@ struct UttDesc {
 	long long x_off;   // first sample in the packed sample array
 	long long f_off;   // first frame (row) in the packed frame arrays
 	long long y_off;   // first output sample (synthesis)
-	int x_len, f_len, y_len, pad;
+	int x_len, f_len, y_len;
+	int f_base;        // absolute frame held in row f_off (synthesis streams; 0 for batch calls): frame k is row f_off + k - f_base
 	unsigned long long rng_pos;  // stream position at which this utterance starts the stage
 };
 

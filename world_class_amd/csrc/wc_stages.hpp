@@ -49,3 +49,4 @@ wc::Device *hv_device(const wc_harvest *h);
 wc::Device *ct_device(const wc_cheaptrick *c);
 wc::Device *d4c_device(const wc_d4c *d);
 wc::Device *syn_device(const wc_synthesis *sy);
+const double *syn_dc_remover(const wc_synthesis *sy);  // getDCRemover's table on the device (reference src/synthesis.cpp:290-303)

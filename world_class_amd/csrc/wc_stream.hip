@@ -109,13 +109,14 @@ struct wc_stream {
 	Device *dev;
 	wc_harvest *hv, *hv_front, *hv_tail;
 	wc_cheaptrick *ct;
+	wc_d4c *d4c = nullptr;  // wc_stream_set_aperiodicity: D4C on the committed frames
 	int fft_size, nc;
 	// per stream, host side
 	std::vector<long long> n_recv, hist_start, next_frame;  // samples received, absolute sample index of the history start, next frame to commit
 	std::vector<long long> rows_start;                         // absolute 1 ms frame of the ring's first row
 	std::vector<int> hist_len, parity, rows_len, rparity;      // samples in the history / rows in the ring, which ping-pong buffer holds them
 	std::vector<char> closed;
-	std::vector<uint64_t> rng_pos;
+	std::vector<uint64_t> rng_pos, d4c_pos;  // noise positions of CheapTrick / D4C
 	DevBuf hist[2], rows_c[2], rows_s[2], batch, hbatch, win_tpos, win_f0, tpos_rel, desc, chunk_f64;
 	HostBuf h_desc;
 	// harvest option copies for the handles created on demand
@@ -128,15 +129,15 @@ struct StreamStateGuard {
 	std::vector<long long> n_recv, hist_start, next_frame, rows_start;
 	std::vector<int> hist_len, parity, rows_len, rparity;
 	std::vector<char> closed;
-	std::vector<uint64_t> rng_pos;
+	std::vector<uint64_t> rng_pos, d4c_pos;
 	bool keep = false;
 	explicit StreamStateGuard(wc_stream *st)
 		: s(st), n_recv(st->n_recv), hist_start(st->hist_start), next_frame(st->next_frame), rows_start(st->rows_start), hist_len(st->hist_len),
-		  parity(st->parity), rows_len(st->rows_len), rparity(st->rparity), closed(st->closed), rng_pos(st->rng_pos) {}
+		  parity(st->parity), rows_len(st->rows_len), rparity(st->rparity), closed(st->closed), rng_pos(st->rng_pos), d4c_pos(st->d4c_pos) {}
 	~StreamStateGuard() {
 		if (keep) return;
 		s->n_recv = n_recv; s->hist_start = hist_start; s->next_frame = next_frame; s->rows_start = rows_start; s->hist_len = hist_len;
-		s->parity = parity; s->rows_len = rows_len; s->rparity = rparity; s->closed = closed; s->rng_pos = rng_pos;
+		s->parity = parity; s->rows_len = rows_len; s->rparity = rparity; s->closed = closed; s->rng_pos = rng_pos; s->d4c_pos = d4c_pos;
 	}
 };
 
@@ -156,6 +157,8 @@ static int common_parity(std::vector<int> &parity, const std::vector<int> &act, 
 			}
 	return parity[act[0]];
 }
+
+static int stream_widen(wc_stream *s, const void *d_chunk, int chunk_format, const int *n_new);
 
 extern "C" {
 
@@ -204,6 +207,7 @@ wc_stream *wc_stream_create(int fs, int n_streams, double frame_period_ms, int c
 	s->rows_start.assign(n_streams, 0); s->rows_len.assign(n_streams, 0); s->rparity.assign(n_streams, 0);
 	s->hist_len.assign(n_streams, 0); s->parity.assign(n_streams, 0); s->closed.assign(n_streams, 0);
 	s->rng_pos.assign(n_streams, 0);
+	s->d4c_pos.assign(n_streams, 0);
 	return s;
 }
 
@@ -211,6 +215,7 @@ void wc_stream_destroy(wc_stream *s) {
 	if (!s) return;
 	s->dev->quiesce();
 	wc_cheaptrick_destroy(s->ct);
+	wc_d4c_destroy(s->d4c);
 	wc_harvest_destroy(s->hv);
 	wc_harvest_destroy(s->hv_front);
 	wc_harvest_destroy(s->hv_tail);
@@ -277,14 +282,17 @@ int wc_stream_set_rng_position(wc_stream *s, int u, unsigned long long position)
 int wc_stream_reset(wc_stream *s, int u) {
 	if (!s || u < 0 || u >= s->n_streams) return fail(WC_ERR_INVALID, "stream reset: bad stream index");
 	DeviceLock lock(s->dev);
-	s->n_recv[u] = 0; s->hist_start[u] = 0; s->next_frame[u] = 0; s->hist_len[u] = 0; s->closed[u] = 0; s->rng_pos[u] = 0;
+	s->n_recv[u] = 0; s->hist_start[u] = 0; s->next_frame[u] = 0; s->hist_len[u] = 0; s->closed[u] = 0; s->rng_pos[u] = 0; s->d4c_pos[u] = 0;
 	s->rows_start[u] = 0; s->rows_len[u] = 0;
 	return WC_OK;
 }
 
-int wc_stream_push_device(wc_stream *s, const double *d_chunk, const int *n_new, const int *flush, double *d_tpos, double *d_f0,
-						  double *d_sp, int *frames_out) {
+static int stream_push(wc_stream *s, const double *d_chunk, const int *n_new, const int *flush, double *d_tpos, double *d_f0, double *d_sp,
+					   double *d_ap, int *frames_out) {
 	if (!s || !d_chunk || !d_tpos || !d_f0 || !d_sp || !frames_out) return fail(WC_ERR_INVALID, "stream push: null argument");
+	if ((s->d4c != nullptr) != (d_ap != nullptr))
+		return fail(WC_ERR_INVALID, s->d4c ? "stream push: aperiodicity is on: push with wc_stream_push_device_ex and a d_ap"
+										   : "stream push: d_ap given but wc_stream_set_aperiodicity was not called");
 	WC_HIP(hipSetDevice(s->dev->id));
 	DeviceLock lock(s->dev);
 	hipStream_t st = s->dev->active();
@@ -502,7 +510,68 @@ int wc_stream_push_device(wc_stream *s, const double *d_chunk, const int *n_new,
 		}
 	}
 	for (int a = 0; a < na; ++a) s->rng_pos[act[a]] = pos[a];
+	if (s->d4c) {
+		// ---- D4C on the same committed frames, window batch and whole-ms relative times, with its own noise positions ----
+		std::vector<uint64_t> pos4(na);
+		uint64_t lo4 = ~0ull, hi4 = 0;
+		for (int a = 0; a < na; ++a) {
+			pos4[a] = s->d4c_pos[act[a]];
+			if (count[a] > 0) { lo4 = std::min(lo4, pos4[a]); hi4 = std::max(hi4, pos4[a]); }
+		}
+		if (hi4 - lo4 <= (1ull << 28)) {
+			if ((rc = wc_d4c_compute_device(s->d4c, na, s->batch.as<double>(), win_len.data(), s->tpos_rel.as<double>(), d_f0, count.data(),
+											s->fft_size, d_ap, pos4.data())))
+				return rc;
+		} else {
+			for (int a = 0; a < na; ++a) {  // positions further apart than one draw table: one call per stream
+				if (count[a] == 0) continue;
+				if ((rc = wc_d4c_compute_device(s->d4c, 1, s->batch.as<double>() + desc[a].batch_off, &win_len[a], s->tpos_rel.as<double>() + desc[a].out_off,
+												d_f0 + desc[a].out_off, &count[a], s->fft_size, d_ap + desc[a].out_off * bins, &pos4[a])))
+					return rc;
+			}
+		}
+		for (int a = 0; a < na; ++a) s->d4c_pos[act[a]] = pos4[a];
+	}
 	guard.keep = true;
+	return WC_OK;
+}
+
+int wc_stream_push_device(wc_stream *s, const double *d_chunk, const int *n_new, const int *flush, double *d_tpos, double *d_f0,
+						  double *d_sp, int *frames_out) {
+	return stream_push(s, d_chunk, n_new, flush, d_tpos, d_f0, d_sp, nullptr, frames_out);
+}
+
+int wc_stream_set_aperiodicity(wc_stream *s, double d4c_threshold) {
+	if (!s) return fail(WC_ERR_INVALID, "stream: null handle");
+	DeviceLock lock(s->dev);
+	if (s->started) return fail(WC_ERR_INVALID, "stream: wc_stream_set_aperiodicity must come before the first push");
+	// D4C's windows reach 1.5 periods of its 47 Hz floor (reference src/d4c.cpp, GetWindowedWaveform) and LoveTrain's 1.5 periods of
+	// 40 Hz: 37.5 ms either side of a frame, which the history must hold behind and ahead of every committed frame
+	if (s->back_ms < 38 || s->ahead_ms < 38)
+		return fail(WC_ERR_INVALID, "stream: aperiodicity needs lookback and lookahead of at least 38 ms (the D4C / LoveTrain windows)");
+	if (s->d4c) { wc_d4c_destroy(s->d4c); s->d4c = nullptr; }
+	if (d4c_threshold < 0) return WC_OK;  // (negative: off again)
+	OnDeviceOf here(s->dev);
+	s->d4c = wc_d4c_create(s->fs, d4c_threshold);
+	return s->d4c ? WC_OK : WC_ERR_DEVICE;
+}
+
+int wc_stream_push_device_ex(wc_stream *s, const void *d_chunk, int chunk_format, const int *n_new, const int *flush, double *d_tpos,
+							 double *d_f0, double *d_sp, double *d_ap, int *frames_out) {
+	if (!s || !d_chunk) return fail(WC_ERR_INVALID, "stream push: null argument");
+	if (chunk_format == 0) return stream_push(s, static_cast<const double *>(d_chunk), n_new, flush, d_tpos, d_f0, d_sp, d_ap, frames_out);
+	WC_HIP(hipSetDevice(s->dev->id));
+	DeviceLock lock(s->dev);  // (held across the widening and the push: chunk_f64 is the handle's)
+	int rc;
+	if ((rc = stream_widen(s, d_chunk, chunk_format, n_new))) return rc;
+	return stream_push(s, s->chunk_f64.as<double>(), n_new, flush, d_tpos, d_f0, d_sp, d_ap, frames_out);
+}
+
+unsigned long long wc_stream_d4c_rng_position(const wc_stream *s, int u) { return (s && u >= 0 && u < s->n_streams) ? s->d4c_pos[u] : 0ull; }
+int wc_stream_set_d4c_rng_position(wc_stream *s, int u, unsigned long long position) {
+	if (!s || u < 0 || u >= s->n_streams) return fail(WC_ERR_INVALID, "stream: bad stream index");
+	DeviceLock lock(s->dev);
+	s->d4c_pos[u] = position;
 	return WC_OK;
 }
 
@@ -512,6 +581,17 @@ int wc_stream_push_device_fmt(wc_stream *s, const void *d_chunk, int chunk_forma
 							  double *d_f0, double *d_sp, int *frames_out) {
 	if (!s || !d_chunk) return fail(WC_ERR_INVALID, "stream push: null argument");
 	if (chunk_format == 0) return wc_stream_push_device(s, static_cast<const double *>(d_chunk), n_new, flush, d_tpos, d_f0, d_sp, frames_out);
+	WC_HIP(hipSetDevice(s->dev->id));
+	DeviceLock lock(s->dev);  // (held across the widening and the push: chunk_f64 is the handle's)
+	int rc;
+	if ((rc = stream_widen(s, d_chunk, chunk_format, n_new))) return rc;
+	return wc_stream_push_device(s, s->chunk_f64.as<double>(), n_new, flush, d_tpos, d_f0, d_sp, frames_out);
+}
+
+}  // extern "C"
+
+// the new samples of a push widened into chunk_f64 (chunk_format 1: int16 PCM, 2: float32)
+static int stream_widen(wc_stream *s, const void *d_chunk, int chunk_format, const int *n_new) {
 	if (chunk_format != 1 && chunk_format != 2) return fail(WC_ERR_INVALID, "stream push: chunk format must be 0 (float64), 1 (int16 PCM) or 2 (float32)");
 	WC_HIP(hipSetDevice(s->dev->id));
 	DeviceLock lock(s->dev);
@@ -525,8 +605,5 @@ int wc_stream_push_device_fmt(wc_stream *s, const void *d_chunk, int chunk_forma
 	if ((rc = s->chunk_f64.reserve(sizeof(double) * (size_t)std::max<long long>(total, 1)))) return rc;
 	if (chunk_format == 1) rc = wc_pcm16_to_double_device(static_cast<const int16_t *>(d_chunk), total, s->chunk_f64.as<double>());
 	else rc = wc_float_to_double_device(static_cast<const float *>(d_chunk), total, s->chunk_f64.as<double>());
-	if (rc) return rc;
-	return wc_stream_push_device(s, s->chunk_f64.as<double>(), n_new, flush, d_tpos, d_f0, d_sp, frames_out);
+	return rc;
 }
-
-}  // extern "C"

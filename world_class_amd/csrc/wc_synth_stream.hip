@@ -1,0 +1,626 @@
+// Chunked Synthesis for many concurrent streams (wc_synth_stream_*): include/world_class_stream.h states the semantics -- the
+// samples a stream commits are those of ONE whole-utterance Synthesis over all of its frames (reference src/synthesis.cpp:77-177).
+// Per push:
+//   ss_frames_kernel     each stream's frame window (f0 / sp / ap rows still needed) moves to the other ping-pong buffer, the
+//                        new frames appended
+//   ss_increment_kernel  phase increments of the samples that became final (the sample-rate F0 / VUV of reference :180-243,
+//                        absolute times i / fs, rows rebased into the window)
+//   ss_timebase_kernel   one wavefront per stream: the reference's sequential phase sum (:255-262) continued from the carried
+//                        total phase with chain64 (the batch's serial time base), wrap detection (:264-283), the pulse list
+//                        (the pulse left waiting by the last push first) and the noise sizes (:106-107)
+//   -- host: pulse counts, pending pulse, commit bound --
+//   the batch's response kernels (syn_launch_responses) on the pulses whose successor is known
+//   ss_overlap_kernel    carried partial sums + the new responses in pulse order (the batch's syn_overlap_add_kernel order):
+//                        the committed prefix to the packed output, the rest to the other carry buffer
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "wc_stages.hpp"
+#include "wc_synthesis.hpp"
+#include "../../include/world_class_stream.h"
+
+namespace wc {
+
+struct SsDesc {
+	long long win_old, win_new;  // row offsets of the stream's window in the old / new buffer
+	long long in_off;            // first new frame in the packed input
+	int keep_from, keep, n_in;   // rows [keep_from, keep_from + keep) of the old window are kept, n_in new frames appended
+	int f_base, f_len;           // absolute frame of new row 0; frames received after the push
+	int n0, n1;                  // samples [n0, n1) become final in this push
+	int cap;                     // slots of the stream's pulse list
+	int has_pend, pend_idx, pend_vuv;
+	double pend_shift;
+	double run, wrap, vu;        // phase sum, wrapped phase and VUV of sample n0 - 1
+	long long inc_off, slot;     // the stream's stretch of the increment scratch / first slot of its pulse list
+};
+
+struct SsOut {
+	double run, wrap, vu, last_shift;
+	int count, first_idx, last_idx, last_vuv;
+};
+
+struct OlDesc {
+	long long src_off, dst_off, y_off;  // carried samples (sample lo), new carry (sample cut), packed output (sample lo)
+	long long slot, pre;                // the stream's pulse list slots / first pulse of the compact numbering
+	int src_len, lo, hi, cut, n_p;      // samples [lo, hi) are formed: [lo, cut) committed, [cut, hi) carried
+};
+
+__global__ void ss_frames_kernel(const SsDesc *__restrict__ desc, int bins, const double *__restrict__ of0, const double *__restrict__ osp,
+								 const double *__restrict__ oap, const double *__restrict__ if0, const double *__restrict__ isp,
+								 const double *__restrict__ iap, double *__restrict__ nf0, double *__restrict__ nsp, double *__restrict__ nap) {
+	const SsDesc d = desc[blockIdx.y];
+	const long long total = (long long)(d.keep + d.n_in) * bins;
+	for (long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x; k < total; k += (long long)gridDim.x * blockDim.x) {
+		const int row = (int)(k / bins), c = (int)(k - (long long)row * bins);
+		const long long dst = (d.win_new + row) * bins + c;
+		if (row < d.keep) {
+			const long long src = (d.win_old + d.keep_from + row) * bins + c;
+			nsp[dst] = osp[src];
+			nap[dst] = oap[src];
+			if (c == 0) nf0[d.win_new + row] = of0[d.win_old + d.keep_from + row];
+		} else {
+			const long long src = (d.in_off + row - d.keep) * bins + c;
+			nsp[dst] = isp[src];
+			nap[dst] = iap[src];
+			if (c == 0) nf0[d.win_new + row] = if0[d.in_off + row - d.keep];
+		}
+	}
+}
+
+// syn_increment_kernel for the final samples of a stream: 2 pi f0_i / fs, the sign carrying the VUV
+__global__ void ss_increment_kernel(const SsDesc *__restrict__ desc, const double *__restrict__ wf0, int fs, int fft_size, double fp,
+									double *__restrict__ inc) {
+	const SsDesc d = desc[blockIdx.y];
+	Coarse co{wf0 + d.win_new, d.f_len, fs / fft_size + 1.0, fp, d.f_base};  // integer division (reference :97)
+	const double cval = 2.0 * kPi / fs;
+	for (int i = d.n0 + blockIdx.x * blockDim.x + threadIdx.x; i < d.n1; i += gridDim.x * blockDim.x) {
+		double f, v;
+		co.at(i / (double)fs, f, v);  // time_axis[i] (reference :227), absolute
+		const bool voiced = v > 0.5;
+		f = voiced ? f : 500.0;
+		const double dd = f * cval;
+		inc[d.inc_off + (i - d.n0)] = voiced ? dd : -dd;
+	}
+}
+
+// syn_timebase_kernel continued from the carried state of the stream (one wavefront per stream)
+__global__ __launch_bounds__(64) void ss_timebase_kernel(const SsDesc *__restrict__ desc, const double *__restrict__ inc_all, int fs,
+														 PulseBuf p, SsOut *__restrict__ out) {
+	const SsDesc d = desc[blockIdx.x];
+	const int lane = threadIdx.x;
+	const int n = d.n1 - d.n0;
+	const double *__restrict__ inc_g = inc_all + d.inc_off;
+	const double two_pi = 2.0 * kPi;
+	const long long slot0 = d.slot;
+	double run = d.run, prev_wrap = d.wrap, prev_vu = d.vu;
+	int cnt = 0;
+	if (d.has_pend) {
+		if (lane == 0) {
+			p.index[slot0] = d.pend_idx;
+			p.shift[slot0] = d.pend_shift;
+			p.vuv[slot0] = d.pend_vuv;
+		}
+		cnt = 1;
+	}
+	for (int base = 0; base < n; base += 64) {
+		const int i = d.n0 + base + lane;  // absolute sample index
+		const double sv = inc_g[base + lane];  // padded with zeros past n
+		const double vu = sv > 0.0 ? 1.0 : 0.0;
+		double mine = run;
+		const double *__restrict__ pu = inc_g + base;  // wave-uniform address: scalar loads
+		chain64(mine, pu);
+		const double wrap = fmod(mine, two_pi);
+		double w_prev = __shfl_up(wrap, 1, 64);
+		double v_prev = __shfl_up(vu, 1, 64);
+		if (lane == 0) { w_prev = prev_wrap; v_prev = prev_vu; }
+		// pulse between samples i-1 and i  <=>  |wrap[i] - wrap[i-1]| > pi ; the pulse sits at i-1 (reference :264-283)
+		const bool is_pulse = (base + lane < n) && (i >= 1) && (fabs(wrap - w_prev) > kPi);
+		const unsigned long long mask = __ballot(is_pulse);
+		if (is_pulse) {
+			const int slot = cnt + __popcll(mask & ((1ull << lane) - 1ull));
+			if (slot < d.cap) {
+				const double y1 = w_prev - two_pi, y2 = wrap;
+				const double xx = -y1 / (y2 - y1);
+				p.index[slot0 + slot] = i - 1;
+				p.shift[slot0 + slot] = xx / fs;
+				p.vuv[slot0 + slot] = v_prev > 0.5 ? 1 : 0;
+			}
+		}
+		cnt += __popcll(mask);
+		// the state of the last final sample (lanes past n hold padding)
+		const int last = min(63, n - 1 - base);
+		run = __shfl(mine, last, 64);
+		prev_wrap = __shfl(wrap, last, 64);
+		prev_vu = __shfl(vu, last, 64);
+	}
+	cnt = min(cnt, d.cap);  // (the host sizes the list for one pulse per sample: never taken)
+	__threadfence();
+	__syncthreads();
+	// noise_size = samples to the next pulse (reference :106-107); the last entry's is 0 (at a flush it is the utterance's last
+	// pulse; otherwise it waits for its successor and is not synthesised in this push)
+	for (int j = lane; j < cnt; j += 64) p.noise_size[slot0 + j] = (j + 1 < cnt) ? p.index[slot0 + j + 1] - p.index[slot0 + j] : 0;
+	if (lane == 0) {
+		SsOut o;
+		o.run = run; o.wrap = prev_wrap; o.vu = prev_vu;
+		o.count = cnt;
+		o.first_idx = cnt > 0 ? p.index[slot0] : 0;
+		o.last_idx = cnt > 0 ? p.index[slot0 + cnt - 1] : 0;
+		o.last_shift = cnt > 0 ? p.shift[slot0 + cnt - 1] : 0.0;
+		o.last_vuv = cnt > 0 ? p.vuv[slot0 + cnt - 1] : 0;
+		out[blockIdx.x] = o;
+	}
+}
+
+// Carried partial sums plus the response rows of the stream's newly final pulses, in pulse order (syn_overlap_add_kernel's tiles
+// and order: reference :118-139, y[index + 1 + j] += response[j] pulse after pulse); rows == nullptr: no pulses, a copy that
+// splits [lo, hi) into the committed and the carried part
+constexpr int SS_T = 256, SS_K = 4, SS_TILE = SS_T * SS_K;
+template <int N>
+__global__ __launch_bounds__(SS_T) void ss_overlap_kernel(const OlDesc *__restrict__ desc, const int *__restrict__ pidx_all,
+														  const double *__restrict__ rows_all, const double *__restrict__ src,
+														  double *__restrict__ y, double *__restrict__ dst) {
+	constexpr int M = N / 2;
+	const OlDesc d = desc[blockIdx.y];
+	const int t0 = d.lo + blockIdx.x * SS_TILE;
+	if (t0 >= d.hi) return;
+	const int n_p = rows_all ? d.n_p : 0;
+	const int *__restrict__ pidx = pidx_all + d.slot;
+	int lo = 0, hi = n_p;
+	while (lo < hi) {
+		const int mid = (lo + hi) >> 1;
+		if (pidx[mid] < t0 - M) lo = mid + 1; else hi = mid;
+	}
+	const int last = t0 + SS_TILE - 2 + M;
+	const int o0 = t0 + threadIdx.x;
+	double acc[SS_K];
+#pragma unroll
+	for (int m = 0; m < SS_K; ++m) {
+		const int o = o0 + m * SS_T;
+		acc[m] = (o < d.hi && o - d.lo < d.src_len) ? src[d.src_off + (o - d.lo)] : 0.0;
+	}
+	const double *__restrict__ rows = rows_all ? rows_all + d.pre * N : nullptr;
+	for (int i = lo; i < n_p; ++i) {
+		if (pidx[i] > last) break;
+		const int start = pidx[i] - M + 1;
+#pragma unroll
+		for (int m = 0; m < SS_K; ++m) {
+			const int j = o0 + m * SS_T - start;
+			acc[m] += (j >= 0 && j < N) ? rows[(long long)i * N + j] : 0.0;
+		}
+	}
+#pragma unroll
+	for (int m = 0; m < SS_K; ++m) {
+		const int o = o0 + m * SS_T;
+		if (o >= d.hi) continue;
+		if (o < d.cut) y[d.y_off + (o - d.lo)] = acc[m];
+		else dst[d.dst_off + (o - d.cut)] = acc[m];
+	}
+}
+
+}  // namespace wc
+
+using namespace wc;
+
+namespace {
+struct SsState {
+	int F = 0;          // frames received
+	int wbase = 0;      // absolute frame of window row 0
+	int wlen = 0;       // rows in the window
+	int n_fin = 0;      // samples whose phase is final
+	int cut = 0;        // samples committed
+	int clen = 0;       // carried partial sums (samples cut .. cut + clen)
+	int has_pend = 0, pend_idx = 0, pend_vuv = 0;
+	double pend_shift = 0.0;
+	double run = 0.0, wrap = 0.0, vu = 0.0;
+	unsigned long long rng_pos = 0;  // noise position of the pending (or next) pulse
+	long long frames = 0, samples = 0;
+	bool closed = false;
+};
+}  // namespace
+
+struct wc_synth_stream {
+	int fs, fft_size, n_streams, max_frames, fp_ms_x1000;
+	double frame_period;  // seconds
+	int gap, wcap, ccap, wsz;  // pulse gap bound (samples), window rows, carried samples, samples formed per push
+	Device *dev;
+	wc_synthesis *sy;
+	std::vector<SsState> st;
+	int parity = 0;
+	DevBuf wf0[2], wsp[2], wap[2], carry[2], work, inc, pulses, resp, meta, owner, aux;
+	HostBuf h_stage;
+};
+
+namespace {
+// A push that fails half way leaves every stream where it was: the host state is restored, the device buffers of the streams
+// are ping-pong pairs whose old side is only given up when the push succeeds.
+struct SynthStreamGuard {
+	wc_synth_stream *s;
+	std::vector<SsState> st;
+	int parity;
+	bool keep = false;
+	explicit SynthStreamGuard(wc_synth_stream *x) : s(x), st(x->st), parity(x->parity) {}
+	~SynthStreamGuard() {
+		if (keep) return;
+		s->st = st;
+		s->parity = parity;
+	}
+};
+
+// first sample whose time i / fs is not below (F - 1) frame periods: samples before it are final once F frames are in
+int final_limit(const wc_synth_stream *s, int F) {
+	if (F < 2) return 0;
+	const double edge = (double)(F - 1) * s->frame_period;  // Coarse::at's (j + 1) * fp
+	long long g = (long long)std::floor(edge * s->fs) - 2;
+	if (g < 0) g = 0;
+	while (g / (double)s->fs < edge) ++g;
+	return (int)std::min<long long>(g, INT_MAX);
+}
+
+int frame_of(const wc_synth_stream *s, int i) { return (int)std::floor(i / (double)s->fs / s->frame_period); }
+}  // namespace
+
+extern "C" {
+
+wc_synth_stream *wc_synth_stream_create(int fs, int fft_size, double frame_period_ms, int n_streams, int max_frames_per_push) {
+	if (n_streams <= 0 || max_frames_per_push <= 0) { set_error("synthesis stream: n_streams and max_frames_per_push must be positive"); return nullptr; }
+	wc_synthesis *sy = wc_synthesis_create(fs, fft_size, frame_period_ms);
+	if (!sy) return nullptr;
+	wc_synth_stream *s = new wc_synth_stream();
+	s->fs = fs; s->fft_size = fft_size; s->n_streams = n_streams; s->max_frames = max_frames_per_push;
+	s->frame_period = frame_period_ms / 1000.;  // reference :31
+	s->dev = syn_device(sy);
+	s->sy = sy;
+	const double lowest = fs / fft_size + 1.0;  // reference :97 (integer division)
+	// voiced: the interpolated F0 stays above lowest / 2 (a voiced sample lies within half a frame of a voiced frame); unvoiced: 500 Hz
+	s->gap = (int)std::ceil(std::max(2.0 * fs / lowest, fs / 500.0)) + 4;
+	const double spf = s->frame_period * fs;
+	s->wcap = max_frames_per_push + (int)std::ceil((s->gap + fft_size + 2.0 * spf) / spf) + 8;
+	s->ccap = s->gap + fft_size + 64;
+	s->wsz = (int)((max_frames_per_push + 2) * std::ceil(spf)) + s->gap + fft_size + 64;
+	s->st.assign(n_streams, SsState());
+	return s;
+}
+
+void wc_synth_stream_destroy(wc_synth_stream *s) {
+	if (!s) return;
+	s->dev->quiesce();
+	for (int k = 0; k < 2; ++k) { s->wf0[k].release(); s->wsp[k].release(); s->wap[k].release(); s->carry[k].release(); }
+	s->work.release(); s->inc.release(); s->pulses.release(); s->resp.release(); s->meta.release(); s->owner.release(); s->aux.release(); s->h_stage.release();
+	wc_synthesis_destroy(s->sy);
+	delete s;
+}
+
+int wc_synth_stream_max_samples_per_push(const wc_synth_stream *s) { return s ? s->wsz : WC_ERR_INVALID; }
+
+int wc_synth_stream_reset(wc_synth_stream *s, int u) {
+	if (!s || u < 0 || u >= s->n_streams) return fail(WC_ERR_INVALID, "synthesis stream: bad stream index");
+	DeviceLock lock(s->dev);
+	s->st[u] = SsState();
+	return WC_OK;
+}
+
+unsigned long long wc_synth_stream_rng_position(const wc_synth_stream *s, int u) {
+	return (s && u >= 0 && u < s->n_streams) ? s->st[u].rng_pos : 0ull;
+}
+int wc_synth_stream_set_rng_position(wc_synth_stream *s, int u, unsigned long long position) {
+	if (!s || u < 0 || u >= s->n_streams) return fail(WC_ERR_INVALID, "synthesis stream: bad stream index");
+	DeviceLock lock(s->dev);
+	s->st[u].rng_pos = position;
+	return WC_OK;
+}
+long long wc_synth_stream_frames_received(const wc_synth_stream *s, int u) { return (s && u >= 0 && u < s->n_streams) ? s->st[u].frames : -1; }
+long long wc_synth_stream_samples_committed(const wc_synth_stream *s, int u) { return (s && u >= 0 && u < s->n_streams) ? s->st[u].samples : -1; }
+
+int wc_synth_stream_push_device(wc_synth_stream *s, const int *n_frames, const int *flush, const double *d_f0, const double *d_sp,
+								const double *d_ap, double *d_y, int *samples_out) {
+	if (!s || !n_frames || !samples_out) return fail(WC_ERR_INVALID, "synthesis stream push: null argument");
+	const int n = s->n_streams, N = s->fft_size, M = N / 2, bins = M + 1;
+	const double fp_ms = s->frame_period * 1000.0;
+	long long total_in = 0;
+	for (int u = 0; u < n; ++u) {
+		const int nf = n_frames[u];
+		const bool fl = flush && flush[u];
+		const SsState &q = s->st[u];
+		if (nf < 0 || nf > s->max_frames) return fail(WC_ERR_INVALID, "synthesis stream push: n_frames out of range");
+		if (q.closed && (nf > 0 || fl)) return fail(WC_ERR_INVALID, "synthesis stream push: stream was flushed; wc_synth_stream_reset it first");
+		if (fl && q.F + nf < 2) return fail(WC_ERR_INVALID, "synthesis stream push: a stream needs at least two frames (reference src/synthesis.cpp:241-242)");
+		if ((double)(q.F + nf) * s->frame_period * s->fs > (double)INT_MAX - 4.0 * s->wsz)
+			return fail(WC_ERR_UNSUPPORTED, "synthesis stream push: a stream may hold at most 2^31 samples (the reference's int indices)");
+		total_in += nf;
+	}
+	if (total_in > 0 && (!d_f0 || !d_sp || !d_ap)) return fail(WC_ERR_INVALID, "synthesis stream push: null frame arrays");
+	if (!d_y) return fail(WC_ERR_INVALID, "synthesis stream push: null output");
+	WC_HIP(hipSetDevice(s->dev->id));
+	DeviceLock lock(s->dev);
+	hipStream_t hs = s->dev->active();
+	SynthStreamGuard guard(s);
+	for (int u = 0; u < n; ++u) samples_out[u] = 0;
+	// ---- host bookkeeping: windows and the samples that become final ----
+	std::vector<int> act;
+	std::vector<SsDesc> desc;
+	std::vector<int> E(n, 0), outlen(n, 0);
+	long long in_off = 0, inc_total = 0, slots = 0;
+	int max_rows = 0, max_new = 0;
+	for (int u = 0; u < n; ++u) {
+		SsState &q = s->st[u];
+		const int nf = n_frames[u];
+		const bool fl = flush && flush[u];
+		if (q.closed) continue;
+		const int F1 = q.F + nf;
+		// rows still needed: those of the waiting pulse and of the first sample that is not final (two rows of margin for the
+		// interpolation's left neighbour and the floor of the row arithmetic)
+		int need = frame_of(s, q.n_fin);
+		if (q.has_pend) need = std::min(need, frame_of(s, q.pend_idx));
+		int base = std::max(std::min(need - 2, q.F), q.wbase);
+		base = std::max(base, 0);
+		SsDesc d;
+		std::memset(&d, 0, sizeof(d));
+		d.win_old = (long long)u * s->wcap;
+		d.win_new = (long long)u * s->wcap;
+		d.in_off = in_off;
+		d.keep_from = base - q.wbase;
+		d.keep = q.F - base;
+		d.n_in = nf;
+		if (d.keep < 0 || d.keep_from < 0 || d.keep_from + d.keep > q.wlen) return fail(WC_ERR_INVALID, "synthesis stream push: internal window arithmetic");
+		if (d.keep + nf > s->wcap) return fail(WC_ERR_INVALID, "synthesis stream push: frame window too small (pulse gap beyond the bound)");
+		d.f_base = base;
+		d.f_len = F1;
+		int e;
+		if (fl) {
+			outlen[u] = wc_synthesis_out_length(F1, fp_ms, s->fs);
+			e = outlen[u];
+		} else {
+			e = std::min(final_limit(s, F1), std::max(wc_synthesis_out_length(std::max(F1, 2), fp_ms, s->fs) - 1, 0));
+		}
+		e = std::max(e, q.n_fin);
+		E[u] = e;
+		d.n0 = q.n_fin;
+		d.n1 = e;
+		d.cap = (e - q.n_fin) + 2;
+		d.has_pend = q.has_pend; d.pend_idx = q.pend_idx; d.pend_vuv = q.pend_vuv; d.pend_shift = q.pend_shift;
+		d.run = q.run; d.wrap = q.wrap; d.vu = q.vu;
+		d.inc_off = inc_total;
+		inc_total += ((long long)(e - q.n_fin) + 63) / 64 * 64 + 64;
+		d.slot = slots;
+		slots += d.cap;
+		max_rows = std::max(max_rows, d.keep + nf);
+		max_new = std::max(max_new, e - q.n_fin);
+		in_off += nf;
+		// the window rows of this push (updated here; the guard restores them if the push fails)
+		q.wbase = base; q.wlen = d.keep + nf; q.F = F1;
+		act.push_back(u);
+		desc.push_back(d);
+	}
+	const int na = (int)act.size();
+	if (na == 0) { guard.keep = true; return WC_OK; }
+	int rc;
+	const size_t win_rows = (size_t)n * s->wcap;
+	for (int k = 0; k < 2; ++k)
+		if ((rc = s->wf0[k].reserve(sizeof(double) * win_rows)) || (rc = s->wsp[k].reserve(sizeof(double) * win_rows * bins)) ||
+			(rc = s->wap[k].reserve(sizeof(double) * win_rows * bins)) || (rc = s->carry[k].reserve(sizeof(double) * (size_t)n * s->ccap)))
+			return rc;
+	if ((rc = s->inc.reserve(sizeof(double) * (size_t)std::max<long long>(inc_total, 64)))) return rc;
+	if ((rc = s->pulses.reserve((size_t)slots * (sizeof(int) * 3 + sizeof(double))))) return rc;
+	PulseBuf pb;
+	pb.shift = s->pulses.as<double>();
+	pb.index = reinterpret_cast<int *>(pb.shift + slots);
+	pb.noise_size = pb.index + slots;
+	pb.vuv = pb.noise_size + slots;
+	// device metadata: SsDesc[na] | SsOut[na] | OlDesc[na] | UttDesc[na] | pulse prefix (i64) [na + 1] | cap_off (i64) [na] |
+	//                  first_index [na] | per-stream prefix pairs (i64) [2 na]
+	const size_t meta_bytes = (sizeof(SsDesc) + sizeof(SsOut) + sizeof(OlDesc) + sizeof(UttDesc) + 4 * sizeof(long long) + sizeof(int)) * (size_t)na +
+							  sizeof(long long) + 256;
+	if ((rc = s->meta.reserve(meta_bytes)) || (rc = s->h_stage.reserve(meta_bytes))) return rc;
+	char *dm = static_cast<char *>(s->meta.p);
+	SsDesc *d_desc = reinterpret_cast<SsDesc *>(dm);
+	SsOut *d_out = reinterpret_cast<SsOut *>(d_desc + na);
+	OlDesc *d_ol = reinterpret_cast<OlDesc *>(d_out + na);
+	UttDesc *d_utt = reinterpret_cast<UttDesc *>(d_ol + na);
+	long long *d_prefix = reinterpret_cast<long long *>(d_utt + na);
+	long long *d_capoff = d_prefix + na + 1;
+	long long *d_pairs = d_capoff + na;
+	int *d_first = reinterpret_cast<int *>(d_pairs + 2 * na);
+	std::memcpy(s->h_stage.p, desc.data(), sizeof(SsDesc) * na);
+	WC_HIP(hipMemcpyAsync(d_desc, s->h_stage.p, sizeof(SsDesc) * na, hipMemcpyHostToDevice, hs));
+	if ((rc = s->h_stage.mark(hs))) return rc;
+	const int par = s->parity;
+	// ---- frame windows, increments, time base ----
+	{
+		const long long per = (long long)max_rows * bins;
+		dim3 grid((unsigned)std::max<long long>(1, std::min<long long>(64, (per + 255) / 256)), (unsigned)na);
+		hipLaunchKernelGGL(ss_frames_kernel, grid, dim3(256), 0, hs, d_desc, bins, s->wf0[par].as<double>(), s->wsp[par].as<double>(),
+						   s->wap[par].as<double>(), d_f0, d_sp, d_ap, s->wf0[1 - par].as<double>(), s->wsp[1 - par].as<double>(),
+						   s->wap[1 - par].as<double>());
+	}
+	WC_HIP(hipMemsetAsync(s->inc.p, 0, sizeof(double) * (size_t)std::max<long long>(inc_total, 64), hs));
+	if (max_new > 0) {
+		dim3 grid((unsigned)std::min(64, (max_new + 255) / 256), (unsigned)na);
+		hipLaunchKernelGGL(ss_increment_kernel, grid, dim3(256), 0, hs, d_desc, (const double *)s->wf0[1 - par].as<double>(), s->fs, N,
+						   s->frame_period, s->inc.as<double>());
+	}
+	hipLaunchKernelGGL(ss_timebase_kernel, dim3(na), dim3(64), 0, hs, d_desc, (const double *)s->inc.as<double>(), s->fs, pb, d_out);
+	WC_HIP(hipGetLastError());
+	std::vector<SsOut> tb(na);
+	WC_HIP(hipMemcpyAsync(tb.data(), d_out, sizeof(SsOut) * na, hipMemcpyDeviceToHost, hs));
+	WC_HIP(hipStreamSynchronize(hs));
+	// ---- which pulses are final, what is committed ----
+	std::vector<OlDesc> ol(na);
+	std::vector<UttDesc> utt(na);
+	std::vector<long long> prefix(na + 1, 0), capoff(na), pairs(2 * na);
+	std::vector<int> first(na), n_syn(na);
+	std::vector<unsigned long long> start(na);
+	const bool atomic = !(N == 1024 || N == 2048);
+	long long total_p = 0, y_total = 0;
+	int max_span = 0;
+	for (int a = 0; a < na; ++a) {
+		const int u = act[a];
+		SsState &q = s->st[u];
+		const bool fl = flush && flush[u];
+		const SsOut &o = tb[a];
+		const int cnt = o.count;
+		const bool pend = !fl && cnt > 0;
+		n_syn[a] = fl ? cnt : std::max(cnt - 1, 0);
+		const int e = E[u];
+		int cut, hi;
+		if (fl) {
+			cut = hi = outlen[u];
+		} else {
+			// later pulses lie at or after the waiting one, or at or after the last final sample; they reach back M - 1 samples
+			const int p_min = pend ? std::min(o.last_idx, e - 1) : e - 1;
+			cut = std::max(q.cut, p_min - M + 1);
+			hi = std::max(q.cut + q.clen, std::max(e + M - 1, cut));
+		}
+		if (cut < q.cut) return fail(WC_ERR_INVALID, "synthesis stream push: internal commit arithmetic");
+		if (hi - q.cut > s->wsz || hi - cut > s->ccap) return fail(WC_ERR_INVALID, "synthesis stream push: carry too small (pulse gap beyond the bound)");
+		OlDesc &d = ol[a];
+		d.src_off = (long long)u * s->ccap;
+		d.dst_off = (long long)u * s->ccap;
+		d.y_off = y_total;
+		d.slot = desc[a].slot;
+		d.pre = total_p;
+		d.src_len = q.clen;
+		d.lo = q.cut; d.hi = hi; d.cut = cut;
+		d.n_p = n_syn[a];
+		max_span = std::max(max_span, hi - q.cut);
+		UttDesc &t = utt[a];
+		std::memset(&t, 0, sizeof(t));
+		t.f_off = (long long)u * s->wcap;
+		t.f_len = q.F;
+		t.f_base = q.wbase;
+		// (block kernels, N = 512 / 4096: absolute sample o is added at work[u * wsz + o - lo], o < hi)
+		t.y_off = (long long)u * s->wsz - q.cut;
+		t.y_len = hi;
+		t.rng_pos = q.rng_pos;
+		start[a] = q.rng_pos;
+		first[a] = o.first_idx;
+		capoff[a] = desc[a].slot;
+		prefix[a] = total_p;
+		pairs[2 * a] = 0; pairs[2 * a + 1] = n_syn[a];
+		total_p += n_syn[a];
+		samples_out[u] = cut - q.cut;
+		y_total += cut - q.cut;
+		// ---- state after this push ----
+		q.run = o.run; q.wrap = o.wrap; q.vu = o.vu;
+		q.n_fin = e;
+		if (cnt > 0) {
+			const unsigned long long adv = (unsigned long long)(o.last_idx - o.first_idx);  // reference :106-107: draws up to the last pulse
+			q.rng_pos += adv;
+		}
+		q.has_pend = pend; q.pend_idx = o.last_idx; q.pend_vuv = o.last_vuv; q.pend_shift = o.last_shift;
+		q.cut = cut; q.clen = hi - cut;
+		q.frames = q.F;
+		q.samples = cut;
+		if (fl) { q.closed = true; q.has_pend = 0; q.clen = 0; }
+	}
+	prefix[na] = total_p;
+	{
+		if ((rc = s->h_stage.reserve(meta_bytes))) return rc;  // (waits for the staging buffer's earlier upload)
+		char *h = static_cast<char *>(s->h_stage.p);
+		std::memcpy(h + ((char *)d_ol - dm), ol.data(), sizeof(OlDesc) * na);
+		std::memcpy(h + ((char *)d_utt - dm), utt.data(), sizeof(UttDesc) * na);
+		std::memcpy(h + ((char *)d_prefix - dm), prefix.data(), sizeof(long long) * (na + 1));
+		std::memcpy(h + ((char *)d_capoff - dm), capoff.data(), sizeof(long long) * na);
+		std::memcpy(h + ((char *)d_pairs - dm), pairs.data(), sizeof(long long) * 2 * na);
+		std::memcpy(h + ((char *)d_first - dm), first.data(), sizeof(int) * na);
+		const size_t off = (char *)d_ol - dm, len = ((char *)(d_first + na)) - (char *)d_ol;
+		WC_HIP(hipMemcpyAsync(dm + off, h + off, len, hipMemcpyHostToDevice, hs));
+		if ((rc = s->h_stage.mark(hs))) return rc;
+	}
+	double *carry_old = s->carry[par].as<double>(), *carry_new = s->carry[1 - par].as<double>();
+	const unsigned tiles = (unsigned)std::max(1, (max_span + SS_TILE - 1) / SS_TILE);
+	auto overlap = [&](const double *rows, const double *src, double *dst, const OlDesc *descs) {
+		switch (N) {
+			case 512: hipLaunchKernelGGL(ss_overlap_kernel<512>, dim3(tiles, na), dim3(SS_T), 0, hs, descs, (const int *)pb.index, rows, src, d_y, dst); break;
+			case 1024: hipLaunchKernelGGL(ss_overlap_kernel<1024>, dim3(tiles, na), dim3(SS_T), 0, hs, descs, (const int *)pb.index, rows, src, d_y, dst); break;
+			case 2048: hipLaunchKernelGGL(ss_overlap_kernel<2048>, dim3(tiles, na), dim3(SS_T), 0, hs, descs, (const int *)pb.index, rows, src, d_y, dst); break;
+			default: hipLaunchKernelGGL(ss_overlap_kernel<4096>, dim3(tiles, na), dim3(SS_T), 0, hs, descs, (const int *)pb.index, rows, src, d_y, dst); break;
+		}
+	};
+	// ---- responses of the final pulses ----
+	std::vector<OlDesc> ol_expand;
+	if (atomic) {
+		// the carried sums and zeros to the work rows, where the block kernels add the responses with FP64 atomics
+		if ((rc = s->work.reserve(sizeof(double) * (size_t)n * s->wsz))) return rc;
+	}
+	if (total_p > 0) {
+		if (!atomic && (rc = s->resp.reserve(sizeof(double) * (size_t)total_p * N))) return rc;
+		SynArgs sa;
+		std::memset(&sa, 0, sizeof(sa));
+		sa.utts = d_utt; sa.n_utt = na; sa.pulse_prefix = d_prefix; sa.cap_off = d_capoff; sa.first_index = d_first; sa.p = pb;
+		sa.f0 = s->wf0[1 - par].as<double>(); sa.sp = s->wsp[1 - par].as<double>(); sa.ap = s->wap[1 - par].as<double>();
+		sa.tw = s->dev->twiddle; sa.dc_remover = syn_dc_remover(s->sy);
+		sa.out = atomic ? s->work.as<double>() : nullptr;
+		sa.resp = atomic ? nullptr : s->resp.as<double>();
+		sa.rng_start = nullptr; sa.trace = nullptr; sa.only_pulse = -1; sa.fs = s->fs; sa.frame_period = s->frame_period;
+		// pulse -> stream of the compact numbering (the one-wavefront kernels), and a per-stream copy that starts at 0
+		std::vector<int> owner((size_t)total_p);
+		for (int a = 0; a < na; ++a) std::fill(owner.begin() + prefix[a], owner.begin() + prefix[a + 1], a);
+		DevBuf &pu = s->owner;
+		if ((rc = pu.reserve(sizeof(int) * (size_t)total_p * 2))) return rc;
+		WC_HIP(hipMemcpyAsync(pu.p, owner.data(), sizeof(int) * (size_t)total_p, hipMemcpyHostToDevice, hs));
+		WC_HIP(hipMemsetAsync(pu.as<int>() + total_p, 0, sizeof(int) * (size_t)total_p, hs));
+		WC_HIP(hipStreamSynchronize(hs));  // (owner is a host vector)
+		if (atomic) {
+			std::vector<OlDesc> ex(ol);
+			for (auto &d : ex) { d.dst_off = d.src_off / s->ccap * s->wsz; d.cut = d.lo; }
+			ol_expand = ex;
+		}
+		uint64_t lo = ~0ull, hi = 0;
+		for (int a = 0; a < na; ++a) {
+			if (n_syn[a] == 0) continue;
+			lo = std::min<uint64_t>(lo, start[a]);
+			hi = std::max<uint64_t>(hi, start[a] + (uint64_t)(E[act[a]] - first[a]) + 1);
+		}
+		if (atomic) {
+			// expand: carried sums -> work rows (everything "carried", nothing committed)
+			if ((rc = s->aux.reserve(sizeof(OlDesc) * na))) return rc;
+			WC_HIP(hipMemcpyAsync(s->aux.p, ol_expand.data(), sizeof(OlDesc) * na, hipMemcpyHostToDevice, hs));
+			overlap(nullptr, carry_old, s->work.as<double>(), s->aux.as<OlDesc>());
+			WC_HIP(hipStreamSynchronize(hs));  // (ol_expand is a host vector)
+		}
+		if (hi - lo <= (1ull << 28)) {
+			if ((rc = s->dev->ensure_rng(lo, hi))) return rc;
+			sa.rng_table = s->dev->rng_table.as<uint32_t>(); sa.rng_base = s->dev->rng_base;
+			sa.pulse_utt = pu.as<int>();
+			sa.total_pulses = total_p;
+			if ((rc = syn_launch_responses(N, sa, hs))) return rc;
+		} else {
+			// streams whose noise positions lie further apart than one draw table covers: one launch per stream, each with its own
+			// stretch of the table
+			for (int a = 0; a < na; ++a) {
+				if (n_syn[a] == 0) continue;
+				if ((rc = s->dev->ensure_rng(start[a], start[a] + (uint64_t)(E[act[a]] - first[a]) + 1))) return rc;
+				SynArgs one = sa;
+				one.utts = d_utt + a; one.n_utt = 1; one.pulse_prefix = d_pairs + 2 * a; one.cap_off = d_capoff + a; one.first_index = d_first + a;
+				one.rng_table = s->dev->rng_table.as<uint32_t>(); one.rng_base = s->dev->rng_base;
+				one.pulse_utt = pu.as<int>() + total_p;
+				one.resp = atomic ? nullptr : s->resp.as<double>() + prefix[a] * N;
+				one.total_pulses = n_syn[a];
+				if ((rc = syn_launch_responses(N, one, hs))) return rc;
+				WC_HIP(hipStreamSynchronize(hs));  // (the next stream's table replaces this one)
+			}
+		}
+	}
+	// ---- ordered overlap-add: committed prefix out, the rest carried ----
+	if (atomic && total_p > 0) {
+		std::vector<OlDesc> sp(ol);
+		for (auto &d : sp) { d.src_off = d.src_off / s->ccap * s->wsz; d.src_len = d.hi - d.lo; d.n_p = 0; }
+		if ((rc = s->h_stage.reserve(meta_bytes))) return rc;
+		std::memcpy(s->h_stage.p, sp.data(), sizeof(OlDesc) * na);
+		WC_HIP(hipMemcpyAsync(d_ol, s->h_stage.p, sizeof(OlDesc) * na, hipMemcpyHostToDevice, hs));
+		if ((rc = s->h_stage.mark(hs))) return rc;
+		overlap(nullptr, s->work.as<double>(), carry_new, d_ol);
+	} else {
+		overlap(atomic ? nullptr : s->resp.as<double>(), carry_old, carry_new, d_ol);
+	}
+	WC_HIP(hipGetLastError());
+	WC_HIP(hipStreamSynchronize(hs));
+	s->parity = 1 - par;
+	guard.keep = true;
+	return WC_OK;
+}
+
+}  // extern "C"

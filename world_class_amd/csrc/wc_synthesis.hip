@@ -23,17 +23,11 @@
 #include "wc_frames.hpp"
 #include "wc_wavefft.hpp"
 #include "wc_hostcopy.hpp"
+#include "wc_synthesis.hpp"
 
 namespace wc {
 
 constexpr double kSafe = 0.000000000001;
-
-struct PulseBuf {
-	int *index;       // sample index of the pulse
-	double *shift;    // fractional time shift (s)
-	int *noise_size;  // samples to the next pulse (0 for the last pulse)
-	int *vuv;         // interpolated VUV at the pulse
-};
 
 struct TbArgs {
 	const UttDesc *utts;
@@ -46,34 +40,6 @@ struct TbArgs {
 	const long long *inc_off;  // per-utterance first slot in the padded increment scratch
 	int fs, fft_size;
 	double frame_period;       // seconds
-};
-
-// interp1 of a coarse contour given on the uniform axis j * fp (j = 0 .. L) at time t, with the
-// reference's histc semantics (reference src/world_matlabfunctions.cpp:136-182): k = clamp(#{j : j fp <= t}, 1, L)
-struct Coarse {
-	const double *f0;
-	int L;
-	double lowest_f0, fp;
-	__device__ __forceinline__ double cf_in(int j) const {  // reference :232-236
-		double v = f0[j];
-		return (v < lowest_f0) ? 0.0 : v;
-	}
-	__device__ __forceinline__ double cv_in(int j) const { return (cf_in(j) == 0.0) ? 0.0 : 1.0; }
-	// one extrapolated point at j == L (reference :239-242)
-	__device__ __forceinline__ double cf(int j) const { return j < L ? cf_in(j) : cf_in(L - 1) * 2 - cf_in(L - 2); }
-	__device__ __forceinline__ double cv(int j) const { return j < L ? cv_in(j) : cv_in(L - 1) * 2 - cv_in(L - 2); }
-	__device__ __forceinline__ void at(double t, double &f, double &v) const {
-		int j = (int)(t / fp);
-		j = max(0, min(j, L));
-		while (j < L && t >= (j + 1) * fp) ++j;
-		while (j > 0 && t < j * fp) --j;
-		int k = min(max(j + 1, 1), L);
-		double x0 = (k - 1) * fp, x1 = k * fp;
-		double s = (t - x0) / (x1 - x0);
-		double f_a = cf(k - 1), f_b = cf(k), v_a = cv(k - 1), v_b = cv(k);
-		f = f_a + s * (f_b - f_a);
-		v = v_a + s * (v_b - v_a);
-	}
 };
 
 // Phase increment of every output sample (reference :211-216, :255-262): 2 pi f0_i / fs with the
@@ -98,104 +64,6 @@ __global__ void syn_increment_kernel(TbArgs a, int n_utt, long long total_out, d
 	const double cval = 2.0 * kPi / a.fs;
 	const double d = f * cval;
 	inc[a.inc_off[lo] + i] = voiced ? d : -d;
-}
-
-// 64 steps of the sequential phase sum, entirely in one asm block: lane L ends with run + |p[0]| + ... + |p[L]|
-// added in exactly that order.  The increments are fetched with scalar loads (8 doubles per s_load_dwordx16)
-// into two register tuples that are refilled while the other one is being consumed (SMEM returns out of
-// order, so the only legal wait is lgkmcnt(0): wait, issue the next load, then run the 8 dependent adds).
-// The set of participating lanes shrinks by shifting EXEC, so each step is one dependent v_add_f64.
-// (the two tuples are the fixed registers s[40:55] and s[56:71], declared as clobbers)
-__device__ __forceinline__ void chain64(double &mine, const double *__restrict__ p) {
-	unsigned long long save;
-	asm volatile(
-		"s_mov_b64 %[sv], exec\n\t"
-		"s_load_dwordx16 s[40:55], %[p], 0x0\n\t"
-		"s_waitcnt lgkmcnt(0)\n\t"
-		"s_load_dwordx16 s[56:71], %[p], 0x40\n\t"
-		"v_add_f64 %[m], %[m], |s[40:41]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[42:43]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[44:45]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[46:47]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[48:49]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[50:51]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[52:53]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[54:55]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"s_waitcnt lgkmcnt(0)\n\t"
-		"s_load_dwordx16 s[40:55], %[p], 0x80\n\t"
-		"v_add_f64 %[m], %[m], |s[56:57]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[58:59]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[60:61]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[62:63]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[64:65]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[66:67]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[68:69]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[70:71]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"s_waitcnt lgkmcnt(0)\n\t"
-		"s_load_dwordx16 s[56:71], %[p], 0xc0\n\t"
-		"v_add_f64 %[m], %[m], |s[40:41]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[42:43]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[44:45]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[46:47]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[48:49]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[50:51]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[52:53]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[54:55]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"s_waitcnt lgkmcnt(0)\n\t"
-		"s_load_dwordx16 s[40:55], %[p], 0x100\n\t"
-		"v_add_f64 %[m], %[m], |s[56:57]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[58:59]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[60:61]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[62:63]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[64:65]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[66:67]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[68:69]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[70:71]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"s_waitcnt lgkmcnt(0)\n\t"
-		"s_load_dwordx16 s[56:71], %[p], 0x140\n\t"
-		"v_add_f64 %[m], %[m], |s[40:41]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[42:43]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[44:45]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[46:47]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[48:49]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[50:51]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[52:53]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[54:55]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"s_waitcnt lgkmcnt(0)\n\t"
-		"s_load_dwordx16 s[40:55], %[p], 0x180\n\t"
-		"v_add_f64 %[m], %[m], |s[56:57]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[58:59]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[60:61]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[62:63]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[64:65]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[66:67]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[68:69]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[70:71]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"s_waitcnt lgkmcnt(0)\n\t"
-		"s_load_dwordx16 s[56:71], %[p], 0x1c0\n\t"
-		"v_add_f64 %[m], %[m], |s[40:41]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[42:43]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[44:45]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[46:47]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[48:49]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[50:51]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[52:53]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[54:55]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"s_waitcnt lgkmcnt(0)\n\t"
-		"v_add_f64 %[m], %[m], |s[56:57]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[58:59]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[60:61]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[62:63]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[64:65]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[66:67]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[68:69]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"v_add_f64 %[m], %[m], |s[70:71]|\n\t s_lshl_b64 exec, exec, 1\n\t"
-		"s_mov_b64 exec, %[sv]\n\t"
-		: [m] "+v"(mine), [sv] "=&s"(save)
-		: [p] "s"(p)
-		: "scc", "memory", "s40", "s41", "s42", "s43", "s44", "s45", "s46", "s47", "s48", "s49", "s50", "s51", "s52", "s53",
-		  "s54", "s55", "s56", "s57", "s58", "s59", "s60", "s61", "s62", "s63", "s64", "s65", "s66", "s67", "s68", "s69", "s70",
-		  "s71");
 }
 
 // One wavefront per utterance.  The reference accumulates the phase with a sequential running sum
@@ -924,29 +792,6 @@ __global__ void syn_noise_size_kernel(const long long *__restrict__ cap_off, con
 	}
 }
 
-struct SynArgs {
-	const UttDesc *utts;
-	int n_utt;
-	const long long *pulse_prefix;  // exclusive prefix of the per-utterance pulse counts (n_utt + 1)
-	const long long *cap_off;
-	const int *first_index;
-	PulseBuf p;
-	const double *f0, *sp, *ap;
-	const uint32_t *rng_table;
-	unsigned long long rng_base;
-	const double2 *tw;
-	const double *dc_remover;
-	double *out;
-	const int *pulse_utt;  // the one-wavefront kernel: utterance of every pulse of the compact numbering (syn_pulse_utt_kernel)
-	double *resp;  // the one-wavefront kernel: [pulse][N] responses in output order, summed by syn_overlap_add_kernel (NULL: atomics into out)
-	long long total_pulses;  // launch size (capacity); the real count is pulse_prefix[n_utt]
-	const unsigned long long *rng_start;  // per-utterance stream position (device), NULL = utts[u].rng_pos
-	unsigned long long *trace;  // WC_SYN_TRACE builds: 16 shader-clock stamps per pulse
-	long long only_pulse;  // debugging aid (builds with -DWC_DEBUG_HOOKS, env WC_DEBUG_ONLY_PULSE): synthesise only this pulse, -1 = all
-	int fs;
-	double frame_period;
-};
-
 // MinimumPhaseAnalysis::compute (reference src/world_common.cpp:196-233) for the block.
 // ls[BPT]: log spectrum of this thread's bins k = tid + e T (k <= M).  On return A[0..M] holds the
 // minimum-phase spectrum (full complex, M+1 entries).  Ends with a __syncthreads().
@@ -1095,10 +940,10 @@ __global__ __launch_bounds__(T) void syn_pulse_kernel(SynArgs a) {
 	const int fl = min(L - 1, (int)floor(t / fp));
 	const int ce = min(L - 1, (int)ceil(t / fp));
 	const double ipol = t / fp - fl;
-	const double *__restrict__ sf = a.sp + (ud.f_off + fl) * (long long)(M + 1);
-	const double *__restrict__ sc = a.sp + (ud.f_off + ce) * (long long)(M + 1);
-	const double *__restrict__ af = a.ap + (ud.f_off + fl) * (long long)(M + 1);
-	const double *__restrict__ ac = a.ap + (ud.f_off + ce) * (long long)(M + 1);
+	const double *__restrict__ sf = a.sp + (ud.f_off + fl - ud.f_base) * (long long)(M + 1);
+	const double *__restrict__ sc = a.sp + (ud.f_off + ce - ud.f_base) * (long long)(M + 1);
+	const double *__restrict__ af = a.ap + (ud.f_off + fl - ud.f_base) * (long long)(M + 1);
+	const double *__restrict__ ac = a.ap + (ud.f_off + ce - ud.f_base) * (long long)(M + 1);
 	double env[BPT], ar[BPT], ls[BPT];
 #pragma unroll
 	for (int e = 0; e < BPT; ++e) {
@@ -1383,10 +1228,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WC_SYN_WAVE_
 	const int fl = min(Lf - 1, (int)floor(t / fp));
 	const int ce = min(Lf - 1, (int)ceil(t / fp));
 	const double ipol = uniform_d(t / fp - fl);
-	const double *__restrict__ sf = a.sp + (ud.f_off + fl) * (long long)(M + 1);
-	const double *__restrict__ sc = a.sp + (ud.f_off + ce) * (long long)(M + 1);
-	const double *__restrict__ af = a.ap + (ud.f_off + fl) * (long long)(M + 1);
-	const double *__restrict__ ac = a.ap + (ud.f_off + ce) * (long long)(M + 1);
+	const double *__restrict__ sf = a.sp + (ud.f_off + fl - ud.f_base) * (long long)(M + 1);
+	const double *__restrict__ sc = a.sp + (ud.f_off + ce - ud.f_base) * (long long)(M + 1);
+	const double *__restrict__ af = a.ap + (ud.f_off + fl - ud.f_base) * (long long)(M + 1);
+	const double *__restrict__ ac = a.ap + (ud.f_off + ce - ud.f_base) * (long long)(M + 1);
 	const bool same = fl == ce;
 	auto blend = [&](double s0, double s1, double a0, double a1, double &env, double &ar) {
 		if (same) {
@@ -1411,7 +1256,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WC_SYN_WAVE_
 	// pulses from now -- are asked for here, a cache line per lane, and looked at only when the wavefront ends (see d4c2_band_kernel)
 	double pf_s, pf_a;
 	{
-		const long long r2 = (ud.f_off + min(ce + WC_SYN_ROW_PF, Lf - 1)) * (long long)(M + 1) + 16 * lane;
+		const long long r2 = (ud.f_off + min(ce + WC_SYN_ROW_PF, Lf - 1) - ud.f_base) * (long long)(M + 1) + 16 * lane;
 		pf_s = a.sp[r2];
 		pf_a = a.ap[r2];
 	}
@@ -1733,10 +1578,10 @@ __global__ __launch_bounds__(64 * kSyn8Waves) __attribute__((amdgpu_waves_per_eu
 	const int fl = min(Lf - 1, (int)floor(t / fp));
 	const int ce = min(Lf - 1, (int)ceil(t / fp));
 	const double ipol = uniform_d(t / fp - fl);
-	const double *__restrict__ sf = a.sp + (ud.f_off + fl) * (long long)(M + 1);
-	const double *__restrict__ sc = a.sp + (ud.f_off + ce) * (long long)(M + 1);
-	const double *__restrict__ af = a.ap + (ud.f_off + fl) * (long long)(M + 1);
-	const double *__restrict__ ac = a.ap + (ud.f_off + ce) * (long long)(M + 1);
+	const double *__restrict__ sf = a.sp + (ud.f_off + fl - ud.f_base) * (long long)(M + 1);
+	const double *__restrict__ sc = a.sp + (ud.f_off + ce - ud.f_base) * (long long)(M + 1);
+	const double *__restrict__ af = a.ap + (ud.f_off + fl - ud.f_base) * (long long)(M + 1);
+	const double *__restrict__ ac = a.ap + (ud.f_off + ce - ud.f_base) * (long long)(M + 1);
 	const bool same = fl == ce;
 	auto blend = [&](double s0, double s1, double a0, double a1, double &env, double &ar) {
 		if (same) {
@@ -2012,6 +1857,22 @@ static void launch_pulses(const SynArgs &a, hipStream_t s) {
 	hipLaunchKernelGGL((syn_pulse_kernel<N, TP>), dim3((unsigned)(8 * ((a.total_pulses + 7) / 8))), dim3(TP), 0, s, a);
 }
 
+int wc::syn_launch_responses(int fft_size, const SynArgs &a, hipStream_t s) {
+	switch (fft_size) {
+		case 512: launch_pulses<512>(a, s); break;
+		case 1024: {
+			const long long per = (a.total_pulses + 7) / 8;
+			hipLaunchKernelGGL(syn_pulse_wave8_kernel, dim3((unsigned)(8 * ((per + kSyn8Waves - 1) / kSyn8Waves))), dim3(64 * kSyn8Waves), 0, s, a);
+			break;
+		}
+		case 2048: hipLaunchKernelGGL(syn_pulse_wave_kernel<false>, dim3((unsigned)(8 * ((a.total_pulses + 7) / 8))), dim3(64), 0, s, a); break;
+		case 4096: launch_pulses<4096>(a, s); break;
+		default: return fail(WC_ERR_UNSUPPORTED, "synthesis: fft_size must be 512, 1024, 2048 or 4096");
+	}
+	WC_HIP(hipGetLastError());
+	return WC_OK;
+}
+
 // per-utterance pulse prefix, overflow flag and end-of-stage stream positions (one small workgroup)
 __global__ void syn_prefix_kernel(int n_utt, const int *__restrict__ count, const int *__restrict__ cap,
 								  const int *__restrict__ first_index, const int *__restrict__ last_index,
@@ -2046,7 +1907,7 @@ int syn_prepare(wc_synthesis *sy, hipStream_t s, int n_utt, const double *d_f0, 
 		if (f0_length[u] < 2) return fail(WC_ERR_INVALID, "synthesis: f0_length must be at least 2 (reference src/synthesis.cpp:241-242)");
 		if (out_length[u] < 0) return fail(WC_ERR_INVALID, "synthesis: negative out_length");
 		UttDesc &t = utts[u];
-		t.x_off = 0; t.f_off = fo; t.y_off = yo; t.x_len = 0; t.f_len = f0_length[u]; t.y_len = out_length[u]; t.pad = 0;
+		t.x_off = 0; t.f_off = fo; t.y_off = yo; t.x_len = 0; t.f_len = f0_length[u]; t.y_len = out_length[u]; t.f_base = 0;
 		t.rng_pos = rng_pos ? rng_pos[u] : 0ull;
 		fo += f0_length[u];
 		yo += out_length[u];
@@ -2358,6 +2219,7 @@ static int syn_run_device(wc_synthesis *sy, int n_utt, const double *d_f0, const
 }
 
 wc::Device *syn_device(const wc_synthesis *sy) { return sy->dev; }
+const double *syn_dc_remover(const wc_synthesis *sy) { return sy->dc_remover.as<double>(); }
 
 extern "C" {
 

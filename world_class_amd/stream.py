@@ -1,4 +1,4 @@
-"""Chunked Harvest + CheapTrick for many concurrent streams: Python mirror of include/world_class_stream.h (the semantics
+"""Chunked Harvest + CheapTrick, and chunked Synthesis, for many concurrent streams: Python mirror of include/world_class_stream.h (the semantics
 are stated there; the reference itself has no streaming mode, reference src/harvest.cpp:431-440, :676-703 are non-causal)."""
 import ctypes as C
 
@@ -23,6 +23,19 @@ STREAM_SIGNATURES = {
     "wc_stream_set_rng_position": (C.c_int, [_vp, C.c_int, C.c_ulonglong]),
     "wc_stream_frames_committed": (C.c_longlong, [_vp, C.c_int]),
     "wc_stream_samples_received": (C.c_longlong, [_vp, C.c_int]),
+    "wc_stream_set_aperiodicity": (C.c_int, [_vp, C.c_double]),
+    "wc_stream_push_device_ex": (C.c_int, [_vp, _vp, C.c_int, _ip, _ip, _vp, _vp, _vp, _vp, _ip]),
+    "wc_stream_d4c_rng_position": (C.c_ulonglong, [_vp, C.c_int]),
+    "wc_stream_set_d4c_rng_position": (C.c_int, [_vp, C.c_int, C.c_ulonglong]),
+    "wc_synth_stream_create": (_vp, [C.c_int, C.c_int, C.c_double, C.c_int, C.c_int]),
+    "wc_synth_stream_destroy": (None, [_vp]),
+    "wc_synth_stream_max_samples_per_push": (C.c_int, [_vp]),
+    "wc_synth_stream_reset": (C.c_int, [_vp, C.c_int]),
+    "wc_synth_stream_push_device": (C.c_int, [_vp, _ip, _ip, _vp, _vp, _vp, _vp, _ip]),
+    "wc_synth_stream_rng_position": (C.c_ulonglong, [_vp, C.c_int]),
+    "wc_synth_stream_set_rng_position": (C.c_int, [_vp, C.c_int, C.c_ulonglong]),
+    "wc_synth_stream_frames_received": (C.c_longlong, [_vp, C.c_int]),
+    "wc_synth_stream_samples_committed": (C.c_longlong, [_vp, C.c_int]),
 }
 _bound = False
 
@@ -44,13 +57,16 @@ class StreamAnalyzer:
     (absolute times, F0, spectrogram rows), `lookahead_ms` behind the newest sample."""
 
     def __init__(self, fs, n_streams, frame_period=1.0, chunk_ms=200, lookback_ms=400, lookahead_ms=400, harvest_f0_floor=71.0,
-                 harvest_f0_ceil=800.0, q1=-0.15, cheaptrick_f0_floor=71.0, fft_size=0, context_ms=0):
+                 harvest_f0_ceil=800.0, q1=-0.15, cheaptrick_f0_floor=71.0, fft_size=0, context_ms=0, aperiodicity=False, d4c_threshold=0.85):
         L = _lib()
         self.fs, self.n_streams, self.frame_period = fs, n_streams, float(frame_period)
         self._h = _handle(L.wc_stream_create(fs, n_streams, float(frame_period), chunk_ms, lookback_ms, lookahead_ms, harvest_f0_floor,
                                              harvest_f0_ceil, q1, cheaptrick_f0_floor, fft_size))
         if context_ms:  # incremental mode: Harvest's front on the newest chunk + 2 context only (see the header)
             _check(L.wc_stream_set_incremental(self._h, context_ms))
+        self.aperiodicity = bool(aperiodicity)
+        if self.aperiodicity:  # D4C on the committed frames, with its own noise position per stream (see the header)
+            _check(L.wc_stream_set_aperiodicity(self._h, float(d4c_threshold)))
         self.fft_size = L.wc_stream_get_fft_size(self._h)
         self.bins = self.fft_size // 2 + 1
         self.chunk_samples = L.wc_stream_chunk_samples(self._h)
@@ -58,16 +74,23 @@ class StreamAnalyzer:
         self.latency_ms = lookahead_ms + chunk_ms
         cap = n_streams * self.max_frames
         self._d_t, self._d_f, self._d_sp = DeviceArray(cap), DeviceArray(cap), DeviceArray(cap * self.bins)
+        self._d_ap = DeviceArray(cap * self.bins) if self.aperiodicity else None
 
-    def push_device(self, d_chunk, n_new=None, flush=None, d_tpos=None, d_f0=None, d_sp=None, chunk_format=0):
+    def push_device(self, d_chunk, n_new=None, flush=None, d_tpos=None, d_f0=None, d_sp=None, chunk_format=0, d_ap=None):
         """device pointers in and out (packed layouts of the header); chunk_format 0 = float64, 1 = int16 PCM, 2 = float32;
-        returns frames committed per stream"""
+        d_ap: aperiodicity rows (streams created with aperiodicity=True); returns frames committed per stream"""
         n = self.n_streams
         out = (C.c_int * n)()
-        _check(_lib().wc_stream_push_device_fmt(self._h, _ptr(d_chunk), chunk_format, _ints(n_new) if n_new is not None else None,
-                                            _ints(flush) if flush is not None else None,
-                                            _ptr(d_tpos if d_tpos is not None else self._d_t), _ptr(d_f0 if d_f0 is not None else self._d_f),
-                                            _ptr(d_sp if d_sp is not None else self._d_sp), out))
+        nn = _ints(n_new) if n_new is not None else None
+        fl = _ints(flush) if flush is not None else None
+        t = _ptr(d_tpos if d_tpos is not None else self._d_t)
+        f = _ptr(d_f0 if d_f0 is not None else self._d_f)
+        sp = _ptr(d_sp if d_sp is not None else self._d_sp)
+        if self.aperiodicity:
+            _check(_lib().wc_stream_push_device_ex(self._h, _ptr(d_chunk), chunk_format, nn, fl, t, f, sp,
+                                                   _ptr(d_ap if d_ap is not None else self._d_ap), out))
+        else:
+            _check(_lib().wc_stream_push_device_fmt(self._h, _ptr(d_chunk), chunk_format, nn, fl, t, f, sp, out))
         return list(out)
 
     def push(self, chunks, flush=None):
@@ -87,9 +110,12 @@ class StreamAnalyzer:
         t = self._d_t.to_host()[:tot]
         f = self._d_f.to_host()[:tot]
         sp = self._d_sp.to_host()[:tot * self.bins].reshape(tot, self.bins)
+        ap = self._d_ap.to_host()[:tot * self.bins].reshape(tot, self.bins) if self.aperiodicity else None
         res, o = [], 0
         for c in counts:
             res.append(dict(tpos=t[o:o + c].copy(), f0=f[o:o + c].copy(), sp=sp[o:o + c].copy()))
+            if ap is not None:
+                res[-1]["ap"] = ap[o:o + c].copy()
             o += c
         return res
 
@@ -102,6 +128,12 @@ class StreamAnalyzer:
     def set_rng_position(self, stream, position):
         _check(_lib().wc_stream_set_rng_position(self._h, stream, int(position)))
 
+    def d4c_rng_position(self, stream):
+        return int(_lib().wc_stream_d4c_rng_position(self._h, stream))
+
+    def set_d4c_rng_position(self, stream, position):
+        _check(_lib().wc_stream_set_d4c_rng_position(self._h, stream, int(position)))
+
     def frames_committed(self, stream):
         return int(_lib().wc_stream_frames_committed(self._h, stream))
 
@@ -110,7 +142,7 @@ class StreamAnalyzer:
         concatenated per-stream results"""
         assert len(xs) == self.n_streams
         cs = self.chunk_samples
-        acc = [dict(tpos=[], f0=[], sp=[]) for _ in xs]
+        acc = [dict(tpos=[], f0=[], sp=[], **({"ap": []} if self.aperiodicity else {})) for _ in xs]
         done = [False] * len(xs)
         pos = 0
         while not all(done):
@@ -128,12 +160,101 @@ class StreamAnalyzer:
                 for k in acc[u]:
                     acc[u][k].append(r[k])
             pos += cs
-        return [dict(tpos=np.concatenate(a["tpos"]), f0=np.concatenate(a["f0"]), sp=np.concatenate(a["sp"])) for a in acc]
+        return [{k: np.concatenate(v) for k, v in a.items()} for a in acc]
 
     def __del__(self):
         try:
             if getattr(self, "_h", None):
                 _lib().wc_stream_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+
+class StreamSynthesizer:
+    """n_streams concurrent synthesis streams: every push appends up to `max_frames` frames (f0, spectrogram and aperiodicity rows)
+    per stream and returns the samples that no later frame can change -- those of one whole-utterance Synthesis over all frames."""
+
+    def __init__(self, fs, fft_size, frame_period=5.0, n_streams=1, max_frames=200):
+        L = _lib()
+        self.fs, self.fft_size, self.frame_period, self.n_streams, self.max_frames = fs, fft_size, float(frame_period), n_streams, max_frames
+        self.bins = fft_size // 2 + 1
+        self._h = _handle(L.wc_synth_stream_create(fs, fft_size, float(frame_period), n_streams, max_frames))
+        self.max_samples = L.wc_synth_stream_max_samples_per_push(self._h)
+        self._d_y = DeviceArray(n_streams * self.max_samples)
+
+    def push_device(self, n_frames, d_f0, d_sp, d_ap, flush=None, d_y=None):
+        """device pointers in and out (packed layouts of the header); returns the samples committed per stream"""
+        out = (C.c_int * self.n_streams)()
+        _check(_lib().wc_synth_stream_push_device(self._h, _ints(n_frames), _ints(flush) if flush is not None else None, _ptr(d_f0),
+                                                  _ptr(d_sp), _ptr(d_ap), _ptr(d_y if d_y is not None else self._d_y), out))
+        return list(out)
+
+    def push(self, f0s, sps, aps, flush=None):
+        """f0s / sps / aps: per stream the new frames (empty = idle).  Returns the committed samples of every stream."""
+        n_frames = [len(f) for f in f0s]
+        tot = sum(n_frames)
+        f0 = np.concatenate([np.asarray(f, dtype=np.float64) for f in f0s]) if tot else np.zeros(1)
+        sp = np.concatenate([np.asarray(v, dtype=np.float64).reshape(-1, self.bins) for v in sps]) if tot else np.zeros((1, self.bins))
+        ap = np.concatenate([np.asarray(v, dtype=np.float64).reshape(-1, self.bins) for v in aps]) if tot else np.zeros((1, self.bins))
+        d = [DeviceArray.from_host(np.ascontiguousarray(a)) for a in (f0, sp, ap)]
+        try:
+            counts = self.push_device(n_frames, d[0], d[1], d[2], flush)
+        finally:
+            for a in d:
+                a.free()
+        y = self._d_y.to_host()[:sum(counts)]
+        res, o = [], 0
+        for c in counts:
+            res.append(y[o:o + c].copy())
+            o += c
+        return res
+
+    def reset(self, stream):
+        _check(_lib().wc_synth_stream_reset(self._h, stream))
+
+    def rng_position(self, stream):
+        return int(_lib().wc_synth_stream_rng_position(self._h, stream))
+
+    def set_rng_position(self, stream, position):
+        _check(_lib().wc_synth_stream_set_rng_position(self._h, stream, int(position)))
+
+    def frames_received(self, stream):
+        return int(_lib().wc_synth_stream_frames_received(self._h, stream))
+
+    def samples_committed(self, stream):
+        return int(_lib().wc_synth_stream_samples_committed(self._h, stream))
+
+    def run_whole(self, params, pattern, on_push=None):
+        """convenience for tests: params[u] = (f0, sp, ap) of a whole utterance; pattern[u] = list of frame counts per push (cycled;
+        0 = an idle push), the last push of a stream flushes it.  Returns the concatenated samples per stream."""
+        n = self.n_streams
+        assert len(params) == n and len(pattern) == n
+        pos, k, done = [0] * n, [0] * n, [False] * n
+        acc = [[] for _ in range(n)]
+        while not all(done):
+            f0s, sps, aps, flush = [], [], [], []
+            for u, (f0, sp, ap) in enumerate(params):
+                c = 0 if done[u] else min(pattern[u][k[u] % len(pattern[u])], self.max_frames, len(f0) - pos[u])
+                k[u] += 1
+                last = not done[u] and pos[u] + c >= len(f0)
+                f0s.append(f0[pos[u]:pos[u] + c])
+                sps.append(sp[pos[u]:pos[u] + c])
+                aps.append(ap[pos[u]:pos[u] + c])
+                flush.append(1 if last else 0)
+                pos[u] += c
+            for u, y in enumerate(self.push(f0s, sps, aps, flush)):
+                acc[u].append(y)
+                if on_push is not None:
+                    on_push(u, len(y))
+            for u in range(n):
+                done[u] = done[u] or bool(flush[u])
+        return [np.concatenate(a) for a in acc]
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                _lib().wc_synth_stream_destroy(self._h)
                 self._h = None
         except Exception:
             pass
