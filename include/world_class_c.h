@@ -150,6 +150,25 @@ int wc_synthesis_compute_device(wc_synthesis *s, int n_utt, const double *d_f0, 
 int wc_synthesis_compute_batch(wc_synthesis *s, int n_utt, const double *const *f0, const int *f0_length, int fft_size,
                                const double *const *const *spectrogram, const double *const *const *aperiodicity,
                                const int *out_length, double *const *out, uint64_t *rng_pos);
+/* Synthesis from coded features (extension; world_class_codec.h): what a TTS / voice-conversion model predicts -- f0, the
+ * mel-cepstrum of number_of_dimensions coefficients and the GetNumberOfAperiodicities(fs) band aperiodicities per frame
+ * (reference src/codec.cpp) -- straight to the waveform.  d_coded_sp / d_coded_ap: one coded row per frame, packed like d_sp /
+ * d_ap.  The rows are decoded (wc_decode_features_device) into scratch of the handle -- frames x (fft_size/2+1) doubles twice,
+ * grown on demand, kept between calls and released with the handle by wc_synthesis_destroy -- and synthesised exactly as by
+ * wc_synthesis_compute_device on those rows: the same samples bit for bit, the same noise draws and rng_pos contract, the same
+ * wc_set_stream ordering.  Refused (WC_ERR_INVALID, noise positions and outputs untouched): 1 <= number_of_dimensions <=
+ * fft_size/2 violated, fs below 12 kHz (no aperiodicity band), null arrays. */
+int wc_synthesis_compute_coded_device(wc_synthesis *s, int n_utt, const double *d_f0, const int *f0_length,
+                                      const double *d_coded_sp, int number_of_dimensions, const double *d_coded_ap,
+                                      const int *out_length, double *d_out, uint64_t *rng_pos);
+/* The same from host arrays: f0[u] (f0_length[u] doubles), coded_sp[u] (f0_length[u] x number_of_dimensions), coded_ap[u]
+ * (f0_length[u] x GetNumberOfAperiodicities(fs)) -- what wc_pipeline_run_batch_host_coded returns -- gathered into page-locked
+ * staging and sent up in one copy; y[u]: out_length[u] doubles, or int16 quantised like the reference's wavwrite when
+ * y_is_pcm16 = 1.  Checks as the device call, and a null row table is refused. */
+int wc_synthesis_run_batch_host_coded(wc_synthesis *s, int n_utt, const double *const *f0, const int *f0_length,
+                                      const double *const *coded_sp, int number_of_dimensions,
+                                      const double *const *coded_ap, const int *out_length,
+                                      void *const *y, int y_is_pcm16, uint64_t *rng_pos);
 
 /* ---- fused pipeline (extension): Harvest -> CheapTrick -> D4C -> Synthesis in the demo's order (reference
  * test/test.cpp:288-384) for a packed batch, everything device resident, the stages overlapped on several HIP

@@ -37,6 +37,13 @@ int wc_decode_spectral_envelope_device(int fs, int fft_size, long long n_frames,
 									   double *d_sp);
 int wc_code_aperiodicity_device(int fs, int fft_size, long long n_frames, const double *d_ap, double *d_coded);
 int wc_decode_aperiodicity_device(int fs, int fft_size, long long n_frames, const double *d_coded, double *d_ap);
+/* Both decoders in one pass, the input of Synthesis from coded features: d_coded_sp (n_frames x number_of_dimensions) and
+ * d_coded_ap (n_frames x GetNumberOfAperiodicities(fs)) -> d_sp, d_ap (n_frames x (fft_size/2+1) each).  fft_size 2048: one
+ * wavefront per frame with the transform in registers; 512, 1024, 4096: the two kernels above.  fft_size 512..4096,
+ * 1 <= number_of_dimensions <= fft_size/2, fs of at least 12 kHz.  Stream-ordered (enqueues only, after the first call at a
+ * new fs). */
+int wc_decode_features_device(int fs, int fft_size, long long n_frames, int number_of_dimensions, const double *d_coded_sp,
+                              const double *d_coded_ap, double *d_sp, double *d_ap);
 
 #ifdef __cplusplus
 }

@@ -138,6 +138,14 @@ int wc_synth_stream_reset(wc_synth_stream *s, int stream);
  * packed by samples_out[u] (host array). */
 int wc_synth_stream_push_device(wc_synth_stream *s, const int *n_frames, const int *flush, const double *d_f0, const double *d_sp,
                                 const double *d_ap, double *d_y, int *samples_out);
+/* The same with coded rows (world_class_codec.h): d_coded_sp / d_coded_ap hold number_of_dimensions / GetNumberOfAperiodicities(fs)
+ * doubles per frame, packed like d_f0.  They are decoded (wc_decode_features_device) into rows of the handle (max_frames_per_push x
+ * n_streams, allocated on the first coded push, released by wc_synth_stream_destroy) and pushed as by wc_synth_stream_push_device:
+ * the samples are those of one wc_synthesis_compute_coded_device call per stream.  number_of_dimensions and fs are checked as
+ * there; a push that fails leaves every stream as it was. */
+int wc_synth_stream_push_coded_device(wc_synth_stream *s, const int *n_frames, const int *flush, const double *d_f0,
+                                      const double *d_coded_sp, int number_of_dimensions, const double *d_coded_ap,
+                                      double *d_y, int *samples_out);
 /* noise position of stream u: where its next (or waiting) pulse takes its draws */
 unsigned long long wc_synth_stream_rng_position(const wc_synth_stream *s, int stream);
 int wc_synth_stream_set_rng_position(wc_synth_stream *s, int stream, unsigned long long position);

@@ -57,6 +57,58 @@ class Synthesis:
                                                 _ptr_array(ys), arg))
         return (ys, list(arr)) if rng_pos is not None else ys
 
+    def compute_coded_device(self, d_f0, f0_lengths, d_coded_sp, number_of_dimensions, d_coded_ap, out_lengths, d_out, rng_pos=None):
+        """wc_synthesis_compute_coded_device: device pointers, coded rows packed like d_f0"""
+        n = len(f0_lengths)
+        arr, arg = _rng_arg(rng_pos, n)
+        _check(lib().wc_synthesis_compute_coded_device(self._h, n, _ptr(d_f0), _ints(f0_lengths), _ptr(d_coded_sp), int(number_of_dimensions),
+                                                       _ptr(d_coded_ap), _ints(out_lengths), _ptr(d_out), arg))
+        return list(arr) if arr is not None else None
+
+    def _coded_args(self, f0, csp, cap, what):
+        from .codec import number_of_aperiodicities
+        f, csp, cap = _c(f0), _c(csp), _c(cap)
+        if csp.ndim != 2 or csp.shape[0] != len(f) or cap.shape != (len(f), number_of_aperiodicities(self.fs)):
+            raise ValueError(f"{what}: coded_sp must be ({len(f)}, number_of_dimensions), coded_ap ({len(f)}, {number_of_aperiodicities(self.fs)})")
+        return f, csp, cap
+
+    def compute_coded(self, f0, coded_sp, coded_ap, out_length=None):
+        """one utterance from coded features (f0, mel-cepstrum, band aperiodicity) through the device call; the noise continues
+        from the process-global position, as compute() does"""
+        from . import DeviceArray, rng_get_position, rng_set_position
+        f, csp, cap = self._coded_args(f0, coded_sp, coded_ap, "Synthesis.compute_coded")
+        if out_length is None:
+            out_length = self.out_length(len(f))
+        d = [DeviceArray.from_host(a) for a in (f, csp, cap)]
+        d_out = DeviceArray(out_length)
+        try:
+            pos = self.compute_coded_device(d[0], [len(f)], d[1], csp.shape[1], d[2], [out_length], d_out, [rng_get_position()])
+            rng_set_position(pos[0])
+            return d_out.to_host()
+        finally:
+            for a in d + [d_out]:
+                a.free()
+
+    def compute_batch_coded(self, f0s, csps, caps, out_lengths=None, y_pcm16=False, rng_pos=None):
+        """wc_synthesis_run_batch_host_coded: ragged host arrays in, one waveform per utterance out (int16 with y_pcm16)"""
+        if not (len(f0s) == len(csps) == len(caps)) or len(f0s) == 0:
+            raise ValueError("Synthesis.compute_batch_coded: f0s, csps, caps must be non-empty lists of the same length")
+        args = [self._coded_args(f, a, b, f"Synthesis.compute_batch_coded: utterance {u}") for u, (f, a, b) in enumerate(zip(f0s, csps, caps))]
+        nd = args[0][1].shape[1]
+        if any(a[1].shape[1] != nd for a in args):
+            raise ValueError("Synthesis.compute_batch_coded: every coded_sp must have the same number_of_dimensions")
+        fl = [len(a[0]) for a in args]
+        if out_lengths is None:
+            out_lengths = [self.out_length(n) for n in fl]
+        if len(out_lengths) != len(fl):
+            raise ValueError("Synthesis.compute_batch_coded: out_lengths must have one entry per utterance")
+        ys = [np.zeros(n, dtype=np.int16 if y_pcm16 else np.float64) for n in out_lengths]
+        arr, arg = _rng_arg(rng_pos, len(fl))
+        _check(lib().wc_synthesis_run_batch_host_coded(self._h, len(fl), _ptr_array([a[0] for a in args]), _ints(fl),
+                                                       _ptr_array([a[1] for a in args]), nd, _ptr_array([a[2] for a in args]),
+                                                       _ints(out_lengths), _ptr_array(ys), 1 if y_pcm16 else 0, arg))
+        return (ys, list(arr)) if rng_pos is not None else ys
+
     def __del__(self):
         try:
             if getattr(self, "_h", None):

@@ -18,6 +18,7 @@ CODEC_SIGNATURES = {
     "wc_decode_spectral_envelope_device": (C.c_int, [C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p]),
     "wc_code_aperiodicity_device": (C.c_int, [C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p]),
     "wc_decode_aperiodicity_device": (C.c_int, [C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p]),
+    "wc_decode_features_device": (C.c_int, [C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _bound = False
@@ -86,3 +87,9 @@ def code_aperiodicity_device(fs, fft_size, n_frames, d_ap, d_coded):
 
 def decode_aperiodicity_device(fs, fft_size, n_frames, d_coded, d_ap):
     _check(_L().wc_decode_aperiodicity_device(int(fs), int(fft_size), int(n_frames), _ptr(d_coded), _ptr(d_ap)))
+
+
+def decode_features_device(fs, fft_size, n_frames, number_of_dimensions, d_coded_sp, d_coded_ap, d_sp, d_ap):
+    """both coded rows of n_frames frames -> spectrogram and aperiodicity rows (fft_size/2+1 each), one pass on the device"""
+    _check(_L().wc_decode_features_device(int(fs), int(fft_size), int(n_frames), int(number_of_dimensions), _ptr(d_coded_sp),
+                                          _ptr(d_coded_ap), _ptr(d_sp), _ptr(d_ap)))

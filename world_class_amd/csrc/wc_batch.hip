@@ -8,6 +8,8 @@
 #include <cstring>
 #include <vector>
 
+#include "../../include/world_class_codec.h"
+#include "../../include/world_class_io.h"
 #include "wc_stages.hpp"
 #include "wc_hostcopy.hpp"
 
@@ -192,6 +194,73 @@ int wc_synthesis_compute_batch(wc_synthesis *sy, int n_utt, const double *const 
 	if ((rc = wc_synthesis_compute_device(sy, n_utt, sc.f.d.as<double>(), f0_length, sc.a.d.as<double>(), sc.b.d.as<double>(), out_length,
 										  sc.y.d.as<double>(), rng_pos))) return rc;
 	return unpack_down(sc.y, n_utt, out, out_length, s);
+}
+
+// Synthesis from coded features (world_class_c.h): f0 | coded sp | coded ap of all utterances in one page-locked region, one copy up;
+// wc_synthesis_compute_coded_device; the waveform (or its int16 quantisation) in one copy down, scattered by several threads.
+int wc_synthesis_run_batch_host_coded(wc_synthesis *sy, int n_utt, const double *const *f0, const int *f0_length,
+									  const double *const *coded_sp, int number_of_dimensions, const double *const *coded_ap,
+									  const int *out_length, void *const *y, int y_is_pcm16, uint64_t *rng_pos) {
+	if (!sy || n_utt <= 0 || !f0 || !f0_length || !coded_sp || !coded_ap || !out_length || !y)
+		return fail(WC_ERR_INVALID, "synthesis coded batch: null argument");
+	if (y_is_pcm16 != 0 && y_is_pcm16 != 1) return fail(WC_ERR_INVALID, "synthesis coded batch: y_is_pcm16 must be 0 or 1");
+	const int fs = syn_fs(sy), fft_size = wc_synthesis_get_fft_size(sy), nd = number_of_dimensions;
+	if (const char *why = decode_features_check(fs, fft_size, nd)) return fail(WC_ERR_INVALID, why);
+	const int n_ap = GetNumberOfAperiodicities(fs);
+	long long frames = 0, total_out = 0;
+	for (int u = 0; u < n_utt; ++u) {
+		if (f0_length[u] < 2) return fail(WC_ERR_INVALID, "synthesis coded batch: f0_length must be at least 2");
+		if (out_length[u] < 0) return fail(WC_ERR_INVALID, "synthesis coded batch: negative out_length");
+		if (!f0[u] || !coded_sp[u] || !coded_ap[u] || (out_length[u] > 0 && !y[u])) return fail(WC_ERR_INVALID, "synthesis coded batch: null table");
+		frames += f0_length[u];
+		total_out += out_length[u];
+	}
+	Device *dev = syn_device(sy);  // (the handle's device, whatever the calling thread's wc_set_device says)
+	WC_HIP(hipSetDevice(dev->id));
+	DeviceLock lock(dev);
+	OnDeviceOf here(dev);  // (wc_double_to_pcm16_device)
+	hipStream_t s = dev->active();
+	BatchScratch sc = scratch(dev);
+	const size_t n_in = (size_t)frames * (1 + nd + n_ap);
+	int rc;
+	if ((rc = sc.a.h.reserve(sizeof(double) * n_in))) return rc;
+	if ((rc = sc.a.d.reserve(sizeof(double) * n_in))) return rc;
+	double *h = sc.a.h.as<double>(), *d = sc.a.d.as<double>();
+	std::vector<CopyJob> jobs;
+	long long fo = 0;
+	for (int u = 0; u < n_utt; ++u) {
+		const size_t n = f0_length[u];
+		jobs.push_back({h + fo, f0[u], sizeof(double) * n});
+		jobs.push_back({h + frames + fo * nd, coded_sp[u], sizeof(double) * n * nd});
+		jobs.push_back({h + frames * (1 + nd) + fo * n_ap, coded_ap[u], sizeof(double) * n * n_ap});
+		fo += f0_length[u];
+	}
+	parallel_copy(jobs);
+	WC_HIP(hipMemcpyAsync(d, h, sizeof(double) * n_in, hipMemcpyHostToDevice, s));
+	if ((rc = sc.a.h.mark(s))) return rc;
+	if (total_out == 0) return WC_OK;
+	if ((rc = sc.y.d.reserve(sizeof(double) * total_out))) return rc;
+	if ((rc = wc_synthesis_compute_coded_device(sy, n_utt, d, f0_length, d + frames, nd, d + frames * (1 + nd), out_length, sc.y.d.as<double>(),
+												rng_pos))) return rc;
+	const size_t y_elem = y_is_pcm16 ? sizeof(int16_t) : sizeof(double);
+	const void *src = sc.y.d.p;
+	if (y_is_pcm16) {
+		if ((rc = sc.b.d.reserve(sizeof(int16_t) * total_out))) return rc;
+		if ((rc = wc_double_to_pcm16_device(sc.y.d.as<double>(), total_out, sc.b.d.as<int16_t>()))) return rc;
+		src = sc.b.d.p;
+	}
+	if ((rc = sc.y.h.reserve(y_elem * total_out))) return rc;
+	WC_HIP(hipMemcpyAsync(sc.y.h.p, src, y_elem * total_out, hipMemcpyDeviceToHost, s));
+	WC_HIP(hipStreamSynchronize(s));
+	jobs.clear();
+	const char *hy = static_cast<const char *>(sc.y.h.p);
+	long long yo = 0;
+	for (int u = 0; u < n_utt; ++u) {
+		if (out_length[u]) jobs.push_back({y[u], hy + y_elem * yo, y_elem * (size_t)out_length[u]});
+		yo += out_length[u];
+	}
+	parallel_copy(jobs);
+	return WC_OK;
 }
 
 }  // extern "C"

@@ -19,6 +19,7 @@
 #include "../../include/world_class_codec.h"
 #include "wc_device.hpp"
 #include "wc_internal.hpp"
+#include "wc_stages.hpp"
 
 using namespace wc;
 
@@ -226,6 +227,23 @@ void report(int rc) {
 
 }  // namespace
 
+// GetParametersForDecoding, reference :144-166
+void wc::codec_decode_sp_plan(int fs, int fft_size, int nd, std::vector<int> &k, std::vector<double> &s, std::vector<double2> &w) {
+	const int md = fft_size / 2;
+	const double floor_mel = frequency_to_mel(kFloorFrequency);
+	const double ceil_mel = frequency_to_mel(fs / 2.0 < kCeilFrequency ? fs / 2.0 : kCeilFrequency);
+	w.assign(md, make_double2(0.0, 0.0));
+	for (int i = 0; i < nd; ++i)
+		w[i] = make_double2(std::cos(i * kPiH / fft_size) * std::sqrt((double)fft_size), std::sin(i * kPiH / fft_size) * std::sqrt((double)fft_size));
+	w[0].x /= std::sqrt(2.0);
+	std::vector<double> mel_axis(md + 2), freq_axis(md + 1);
+	for (int i = 0; i < md; ++i) mel_axis[i + 1] = mel_to_frequency((ceil_mel - floor_mel) * i / md + floor_mel);
+	mel_axis[0] = 0;
+	mel_axis[md + 1] = fs / 2.0;
+	for (int i = 0; i < md + 1; ++i) freq_axis[i] = static_cast<double>(i) * fs / fft_size;
+	interp1_plan(mel_axis, freq_axis, k, s);
+}
+
 extern "C" {
 
 int GetNumberOfAperiodicities(int fs) {
@@ -283,21 +301,10 @@ int wc_decode_spectral_envelope_device(int fs, int fft_size, long long n_frames,
 	DeviceLock lock(dev);
 	if (n_frames == 0) return WC_OK;
 	const int md = fft_size / 2;
-	// GetParametersForDecoding, reference :144-166
-	const double floor_mel = frequency_to_mel(kFloorFrequency);
-	const double ceil_mel = frequency_to_mel(fs / 2.0 < kCeilFrequency ? fs / 2.0 : kCeilFrequency);
-	std::vector<double2> w(md, make_double2(0.0, 0.0));
-	for (int i = 0; i < nd; ++i)
-		w[i] = make_double2(std::cos(i * kPiH / fft_size) * std::sqrt((double)fft_size), std::sin(i * kPiH / fft_size) * std::sqrt((double)fft_size));
-	w[0].x /= std::sqrt(2.0);
-	std::vector<double> mel_axis(md + 2), freq_axis(md + 1);
-	for (int i = 0; i < md; ++i) mel_axis[i + 1] = mel_to_frequency((ceil_mel - floor_mel) * i / md + floor_mel);
-	mel_axis[0] = 0;
-	mel_axis[md + 1] = fs / 2.0;
-	for (int i = 0; i < md + 1; ++i) freq_axis[i] = static_cast<double>(i) * fs / fft_size;
 	std::vector<int> k;
 	std::vector<double> s;
-	interp1_plan(mel_axis, freq_axis, k, s);
+	std::vector<double2> w;
+	codec_decode_sp_plan(fs, fft_size, nd, k, s, w);
 	PlanBufs bufs;
 	SpPlan plan;
 	int rc;

@@ -50,3 +50,18 @@ wc::Device *ct_device(const wc_cheaptrick *c);
 wc::Device *d4c_device(const wc_d4c *d);
 wc::Device *syn_device(const wc_synthesis *sy);
 const double *syn_dc_remover(const wc_synthesis *sy);  // getDCRemover's table on the device (reference src/synthesis.cpp:290-303)
+int syn_fs(const wc_synthesis *sy);
+
+// Feature decoding for Synthesis from coded features (wc_codec.hip, wc_synth_coded.hip)
+namespace wc {
+// GetParametersForDecoding (reference src/codec.cpp:144-166): the interp1 plan (k, s) from the mel axis onto bins 0 .. fft_size/2
+// and the IDCT weights of the first nd coefficients (the rest 0)
+void codec_decode_sp_plan(int fs, int fft_size, int nd, std::vector<int> &k, std::vector<double> &s, std::vector<double2> &w);
+// nullptr if (fs, fft_size, nd) can be decoded, else why not: fft_size 512 .. 4096, 1 <= nd <= fft_size/2, fs >= 12 kHz (at
+// least one aperiodicity band)
+const char *decode_features_check(int fs, int fft_size, int nd);
+// Both coded rows of n_frames frames -> rows of fft_size/2+1 doubles (arguments already checked).  fft_size 2048: the one-wavefront
+// kernel, enqueued on s; other sizes: the codec's workgroup-per-frame kernels (wc_decode_*_device) on dev's active stream.
+int decode_features_enqueue(Device *dev, hipStream_t s, int fs, int fft_size, long long n_frames, int nd, const double *d_coded_sp,
+							const double *d_coded_ap, double *d_sp, double *d_ap);
+}  // namespace wc

@@ -1,0 +1,192 @@
+// Feature decoding for Synthesis from coded features (include/world_class_codec.h: wc_decode_features_device; world_class_c.h:
+// wc_synthesis_compute_coded_device; world_class_stream.h: wc_synth_stream_push_coded_device).
+//
+//   decode_features_wave_kernel   one 64-lane wavefront per frame at fft_size 2048, both rows of the frame in one pass:
+//     spectral envelope (reference src/codec.cpp:63-85, :298-325): weights -> IDCTForCodec as a BACKWARD c2c transform of
+//       1024 points held in registers (wf_fft1024_dit, wc_wavefft.hpp; pruned first stage when nd <= 256) -> the even/odd
+//       interleave onto the mel axis in LDS -> interp1 onto the linear axis -> exp
+//     aperiodicity (:19-40, :238-267): voiced/unvoiced test on the band mean -> interp1 at 3 kHz multiples -> 10^(v/20)
+//   The arithmetic of the codec's decode_sp_kernel / decode_ap_kernel (wc_codec.hip) with the plan of wc::codec_decode_sp_plan,
+//   except for the FFT's order of operations and 10^(v/20) as one exp: the rows differ from theirs in the last bits only.  The
+//   kernel is bound by its FP64 transcendentals (an exp per bin of either row), so the second stage's twiddles sit in LDS: 162
+//   VGPRs, 3 waves per SIMD.  Other fft sizes take those workgroup-per-frame kernels.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <map>
+#include <mutex>
+#include <vector>
+
+#include "../../include/world_class_c.h"
+#include "../../include/world_class_codec.h"
+#include "wc_stages.hpp"
+#include "wc_wavefft.hpp"
+
+using namespace wc;
+
+namespace {
+
+constexpr double kFrequencyInterval = 3000.0, kSafeGuard = 0.000000000001;  // world_constantnumbers.hpp
+constexpr double kLn10By20 = 0.11512925464970228420;                         // ln(10) / 20
+
+struct DecPlan {
+	const int *k;        // 1025 segment indices (1-based) on the mel axis
+	const double *s;     // 1025 fractions
+	const double2 *w;    // 1024 IDCT weights
+};
+
+__global__ __launch_bounds__(64) void decode_features_wave_kernel(const double *__restrict__ csp, const double *__restrict__ cap,
+																  double *__restrict__ sp, double *__restrict__ ap, int nd, int n_ap,
+																  int fs, DecPlan p, const double2 *__restrict__ tw) {
+	constexpr int MD = 1024, BINS = MD + 1, FFT = 2 * MD;
+	__shared__ double L[kWfLds];  // the transform's exchange buffer, then the mel-axis row mel[0 .. MD + 1]
+	__shared__ double T2[kWfT2Lds];  // the second stage's twiddles: out of the registers, which then leave room for 3 waves per SIMD
+	const int lane = threadIdx.x;
+	const long long f = blockIdx.x;
+	wf_t2_to_lds(T2, tw, lane);
+
+	// ---- spectral envelope ----
+	{
+		const double *__restrict__ c = csp + f * nd;
+		const double normalization = sqrt((double)MD);
+		double re[16], im[16];
+#pragma unroll
+		for (int q = 0; q < 16; ++q) {  // strided: slot q holds coefficient lane + 64 q
+			const int i = lane + 64 * q;
+			re[q] = 0.0;
+			im[q] = 0.0;
+			if (i < nd) {
+				const double2 w = p.w[i];
+				re[q] = c[i] * w.x * normalization;
+				im[q] = -c[i] * w.y * normalization;
+			}
+		}
+		if (nd <= 256) wdft16<-1, 1>(re, im);  // coefficients 256 .. 1023 are zero
+		else wdft16<-1>(re, im);
+		wf_fft1024_dit_rest<-1>(re, im, L, tw, lane, T2);
+		// paired: slot 4 g + q holds X[j_g + 256 q].  mel[1 + 2 k] = Re X[k] (k < 512), mel[2048 - 2 k] = Re X[k] (k >= 512);
+		// the two ends repeat their neighbours: mel[0] = X[0] (lane 0, A_0), mel[MD + 1] = X[512] (lane 0, A_2)
+		const int jg[4] = {lane, lane ? 256 - lane : 128, 64 + lane, 192 - lane};
+#pragma unroll
+		for (int g = 0; g < 4; ++g)
+#pragma unroll
+			for (int q = 0; q < 4; ++q) {
+				const int k = jg[g] + 256 * q;
+				L[k < 512 ? 1 + 2 * k : 2048 - 2 * k] = re[4 * g + q];
+			}
+		if (lane == 0) {
+			L[0] = re[0];
+			L[MD + 1] = re[2];
+		}
+		wf_fence();
+		double *__restrict__ row = sp + f * BINS;
+		for (int j = lane; j < BINS; j += 64) {
+			const int k = p.k[j];
+			const double v = L[k - 1] + p.s[j] * (L[k] - L[k - 1]);
+			row[j] = exp(v / MD);
+		}
+	}
+
+	// ---- aperiodicity ----
+	const double *__restrict__ c = cap + f * n_ap;
+	double *__restrict__ row = ap + f * BINS;
+	double tmp = 0.0;
+	for (int i = 0; i < n_ap; ++i) tmp += c[i];
+	tmp /= n_ap;
+	if (tmp > -0.5) {  // CheckVUV: treated as unvoiced, the initial value stays
+		for (int j = lane; j < BINS; j += 64) row[j] = 1.0 - kSafeGuard;
+		return;
+	}
+	const int na = n_ap + 2;
+	auto axis = [&](int q) { return q == na - 1 ? fs / 2.0 : q * kFrequencyInterval; };
+	auto val = [&](int q) { return q == 0 ? -60.0 : (q == na - 1 ? -kSafeGuard : c[q - 1]); };
+	for (int j = lane; j < BINS; j += 64) {
+		const double fj = static_cast<double>(fs) / FFT * j;
+		int k = 1;  // histc: clamp(#{q : axis(q) <= f}, 1, na - 1)
+		while (k < na && fj >= axis(k)) ++k;
+		k = k < na - 1 ? k : na - 1;
+		const double x0 = axis(k - 1), x1 = axis(k);
+		const double s = (fj - x0) / (x1 - x0);
+		const double v = val(k - 1) + s * (val(k) - val(k - 1));
+		row[j] = exp(v * kLn10By20);  // 10^(v/20): one exp instead of pow's log + exp (within 1e-15 of it: ap <= 1, |v| <= 60)
+	}
+}
+
+// The plan of fft_size 2048 per (device, fs), built and uploaded on first use and kept for the life of the process (28 KB each):
+// a call then only enqueues.
+struct WavePlan {
+	DevBuf k, s, w;
+};
+std::mutex g_plan_mu;
+std::map<std::pair<int, int>, WavePlan *> g_plans;
+
+int wave_plan(Device *dev, int fs, DecPlan *out) {
+	std::lock_guard<std::mutex> g(g_plan_mu);
+	WavePlan *&pl = g_plans[{dev->id, fs}];
+	if (!pl) {
+		std::vector<int> k;
+		std::vector<double> s;
+		std::vector<double2> w;
+		codec_decode_sp_plan(fs, 2048, 1024, k, s, w);  // all weights: the kernel drops the coefficients beyond nd
+		WavePlan *n = new WavePlan();
+		int rc = n->k.reserve(sizeof(int) * k.size());
+		if (!rc) rc = n->s.reserve(sizeof(double) * s.size());
+		if (!rc) rc = n->w.reserve(sizeof(double2) * w.size());
+		hipError_t e = hipSuccess;
+		if (!rc) e = hipMemcpy(n->k.p, k.data(), sizeof(int) * k.size(), hipMemcpyHostToDevice);
+		if (!rc && e == hipSuccess) e = hipMemcpy(n->s.p, s.data(), sizeof(double) * s.size(), hipMemcpyHostToDevice);
+		if (!rc && e == hipSuccess) e = hipMemcpy(n->w.p, w.data(), sizeof(double2) * w.size(), hipMemcpyHostToDevice);
+		if (!rc && e != hipSuccess) rc = fail(WC_ERR_DEVICE, std::string("decode_features: plan upload: ") + hipGetErrorString(e));
+		if (rc) {
+			n->k.release(); n->s.release(); n->w.release();
+			delete n;
+			return rc;
+		}
+		pl = n;
+	}
+	out->k = pl->k.as<int>();
+	out->s = pl->s.as<double>();
+	out->w = pl->w.as<double2>();
+	return WC_OK;
+}
+
+}  // namespace
+
+const char *wc::decode_features_check(int fs, int fft_size, int nd) {
+	if (!(fft_size == 512 || fft_size == 1024 || fft_size == 2048 || fft_size == 4096)) return "decode_features: fft_size must be 512, 1024, 2048 or 4096";
+	if (nd < 1 || nd > fft_size / 2) return "decode_features: number_of_dimensions must be 1 .. fft_size/2";
+	if (fs <= 0 || GetNumberOfAperiodicities(fs) < 1) return "decode_features: fs must be at least 12 kHz (no aperiodicity band below)";
+	return nullptr;
+}
+
+int wc::decode_features_enqueue(Device *dev, hipStream_t s, int fs, int fft_size, long long n_frames, int nd, const double *d_coded_sp,
+								const double *d_coded_ap, double *d_sp, double *d_ap) {
+	if (n_frames == 0) return WC_OK;
+	int rc;
+	if (fft_size == 2048) {
+		DecPlan p;
+		if ((rc = wave_plan(dev, fs, &p))) return rc;
+		hipLaunchKernelGGL(decode_features_wave_kernel, dim3((unsigned)n_frames), dim3(64), 0, s, d_coded_sp, d_coded_ap, d_sp, d_ap, nd,
+						   GetNumberOfAperiodicities(fs), fs, p, (const double2 *)dev->twiddle);
+		WC_HIP(hipGetLastError());
+		return WC_OK;
+	}
+	OnDeviceOf here(dev);  // (the codec's entry points run on the calling thread's device)
+	if ((rc = wc_decode_spectral_envelope_device(fs, fft_size, n_frames, nd, d_coded_sp, d_sp))) return rc;
+	return wc_decode_aperiodicity_device(fs, fft_size, n_frames, d_coded_ap, d_ap);
+}
+
+extern "C" {
+
+int wc_decode_features_device(int fs, int fft_size, long long n_frames, int number_of_dimensions, const double *d_coded_sp,
+							  const double *d_coded_ap, double *d_sp, double *d_ap) {
+	if (const char *why = decode_features_check(fs, fft_size, number_of_dimensions)) return fail(WC_ERR_INVALID, why);
+	if (n_frames < 0 || n_frames > 0xffffffffll) return fail(WC_ERR_INVALID, "decode_features: n_frames out of range");
+	if (n_frames > 0 && (!d_coded_sp || !d_coded_ap || !d_sp || !d_ap)) return fail(WC_ERR_INVALID, "decode_features: null argument");
+	Device *dev = current_device();
+	if (!dev) return WC_ERR_DEVICE;
+	DeviceLock lock(dev);
+	return decode_features_enqueue(dev, dev->active(), fs, fft_size, n_frames, number_of_dimensions, d_coded_sp, d_coded_ap, d_sp, d_ap);
+}
+
+}  // extern "C"

@@ -230,6 +230,7 @@ struct wc_synth_stream {
 	std::vector<SsState> st;
 	int parity = 0;
 	DevBuf wf0[2], wsp[2], wap[2], carry[2], work, inc, pulses, resp, meta, owner, aux;
+	DevBuf dsp, dap;  // wc_synth_stream_push_coded_device: the pushed frames' decoded rows (max_frames x n_streams, on first use)
 	HostBuf h_stage;
 };
 
@@ -288,6 +289,7 @@ void wc_synth_stream_destroy(wc_synth_stream *s) {
 	if (!s) return;
 	s->dev->quiesce();
 	for (int k = 0; k < 2; ++k) { s->wf0[k].release(); s->wsp[k].release(); s->wap[k].release(); s->carry[k].release(); }
+	s->dsp.release(); s->dap.release();
 	s->work.release(); s->inc.release(); s->pulses.release(); s->resp.release(); s->meta.release(); s->owner.release(); s->aux.release(); s->h_stage.release();
 	wc_synthesis_destroy(s->sy);
 	delete s;
@@ -621,6 +623,33 @@ int wc_synth_stream_push_device(wc_synth_stream *s, const int *n_frames, const i
 	s->parity = 1 - par;
 	guard.keep = true;
 	return WC_OK;
+}
+
+// The pushed frames' coded rows are decoded (wc::decode_features_enqueue) into the handle's rows on the caller's stream, and the push
+// runs on them: the stream state is only touched by wc_synth_stream_push_device, which keeps it unchanged when it fails.
+int wc_synth_stream_push_coded_device(wc_synth_stream *s, const int *n_frames, const int *flush, const double *d_f0,
+									  const double *d_coded_sp, int number_of_dimensions, const double *d_coded_ap, double *d_y,
+									  int *samples_out) {
+	if (!s || !n_frames || !samples_out) return fail(WC_ERR_INVALID, "synthesis stream push: null argument");
+	if (const char *why = decode_features_check(s->fs, s->fft_size, number_of_dimensions)) return fail(WC_ERR_INVALID, why);
+	long long total_in = 0;
+	for (int u = 0; u < s->n_streams; ++u) {
+		if (n_frames[u] < 0 || n_frames[u] > s->max_frames) return fail(WC_ERR_INVALID, "synthesis stream push: n_frames out of range");
+		total_in += n_frames[u];
+	}
+	if (total_in > 0 && (!d_f0 || !d_coded_sp || !d_coded_ap)) return fail(WC_ERR_INVALID, "synthesis stream push: null frame arrays");
+	if (!d_y) return fail(WC_ERR_INVALID, "synthesis stream push: null output");
+	WC_HIP(hipSetDevice(s->dev->id));
+	DeviceLock lock(s->dev);
+	if (total_in > 0) {
+		const size_t rows = sizeof(double) * (size_t)s->max_frames * s->n_streams * (s->fft_size / 2 + 1);
+		int rc;
+		if ((rc = s->dsp.reserve(rows))) return rc;
+		if ((rc = s->dap.reserve(rows))) return rc;
+		if ((rc = decode_features_enqueue(s->dev, s->dev->active(), s->fs, s->fft_size, total_in, number_of_dimensions, d_coded_sp, d_coded_ap,
+										  s->dsp.as<double>(), s->dap.as<double>()))) return rc;
+	}
+	return wc_synth_stream_push_device(s, n_frames, flush, d_f0, s->dsp.as<double>(), s->dap.as<double>(), d_y, samples_out);
 }
 
 }  // extern "C"

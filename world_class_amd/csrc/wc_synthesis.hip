@@ -24,6 +24,7 @@
 #include "wc_wavefft.hpp"
 #include "wc_hostcopy.hpp"
 #include "wc_synthesis.hpp"
+#include "wc_stages.hpp"
 
 namespace wc {
 
@@ -1843,6 +1844,7 @@ struct wc_synthesis {
 	bool phase_single;  // WC_SYN_PHASE=single: the phase sum by one workgroup per utterance (A/B and the bit-identity test)
 	bool serial_timebase;  // WC_SYN_TIMEBASE=serial: the one-wavefront sequential accumulation instead of the exact parallel one
 	HostBuf h_stage, h_rows;
+	DevBuf dec_sp, dec_ap;  // wc_synthesis_compute_coded_device: the decoded rows
 	long long total_out = 0, cap_total = 0;  // of the most recent syn_prepare
 	int n_utt = 0, max_out = 0;
 };
@@ -2219,6 +2221,7 @@ static int syn_run_device(wc_synthesis *sy, int n_utt, const double *d_f0, const
 }
 
 wc::Device *syn_device(const wc_synthesis *sy) { return sy->dev; }
+int syn_fs(const wc_synthesis *sy) { return sy->fs; }
 const double *syn_dc_remover(const wc_synthesis *sy) { return sy->dc_remover.as<double>(); }
 
 extern "C" {
@@ -2278,6 +2281,7 @@ void wc_synthesis_destroy(wc_synthesis *s) {
 	if (s->e_twin) (void)hipEventDestroy(s->e_twin);
 	s->dc_remover.release(); s->utts.release(); s->meta.release(); s->pulses.release(); s->incs.release(); s->phase.release(); s->tile_cnt.release(); s->phase_seg.release(); s->resp.release(); s->pulse_utt.release();
 	s->d_f0.release(); s->d_sp.release(); s->d_ap.release(); s->d_out.release(); s->h_stage.release(); s->h_rows.release();
+	s->dec_sp.release(); s->dec_ap.release();
 	delete s;
 }
 
@@ -2289,6 +2293,33 @@ int wc_synthesis_compute_device(wc_synthesis *s, int n_utt, const double *d_f0, 
 		return fail(WC_ERR_INVALID, "synthesis: null argument");
 	WC_HIP(hipSetDevice(s->dev->id));
 	DeviceLock lock(s->dev);
+	return syn_run_device(s, n_utt, d_f0, f0_length, d_sp, d_ap, out_length, d_out, rng_pos);
+}
+
+// Synthesis from coded features: the rows are decoded into the handle's dec_sp / dec_ap on the caller's stream, and the batch runs
+// on them as in wc_synthesis_compute_device.  (Decoding on a side stream beside the time base measured no faster: DESIGN.md
+// section 10.)
+int wc_synthesis_compute_coded_device(wc_synthesis *s, int n_utt, const double *d_f0, const int *f0_length, const double *d_coded_sp,
+									  int number_of_dimensions, const double *d_coded_ap, const int *out_length, double *d_out,
+									  uint64_t *rng_pos) {
+	if (!s || n_utt <= 0 || !d_f0 || !f0_length || !d_coded_sp || !d_coded_ap || !out_length || !d_out)
+		return fail(WC_ERR_INVALID, "synthesis coded: null argument");
+	if (const char *why = decode_features_check(s->fs, s->fft_size, number_of_dimensions)) return fail(WC_ERR_INVALID, why);
+	long long frames = 0;
+	for (int u = 0; u < n_utt; ++u) {  // (checked here too: a refused call enqueues nothing)
+		if (f0_length[u] < 2) return fail(WC_ERR_INVALID, "synthesis: f0_length must be at least 2 (reference src/synthesis.cpp:241-242)");
+		if (out_length[u] < 0) return fail(WC_ERR_INVALID, "synthesis: negative out_length");
+		frames += f0_length[u];
+	}
+	WC_HIP(hipSetDevice(s->dev->id));
+	DeviceLock lock(s->dev);
+	const size_t rows = sizeof(double) * (size_t)frames * (s->fft_size / 2 + 1);
+	int rc;
+	if ((rc = s->dec_sp.reserve(rows))) return rc;
+	if ((rc = s->dec_ap.reserve(rows))) return rc;
+	double *d_sp = s->dec_sp.as<double>(), *d_ap = s->dec_ap.as<double>();
+	if ((rc = decode_features_enqueue(s->dev, s->dev->active(), s->fs, s->fft_size, frames, number_of_dimensions, d_coded_sp, d_coded_ap,
+									  d_sp, d_ap))) return rc;
 	return syn_run_device(s, n_utt, d_f0, f0_length, d_sp, d_ap, out_length, d_out, rng_pos);
 }
 

@@ -32,6 +32,7 @@ STREAM_SIGNATURES = {
     "wc_synth_stream_max_samples_per_push": (C.c_int, [_vp]),
     "wc_synth_stream_reset": (C.c_int, [_vp, C.c_int]),
     "wc_synth_stream_push_device": (C.c_int, [_vp, _ip, _ip, _vp, _vp, _vp, _vp, _ip]),
+    "wc_synth_stream_push_coded_device": (C.c_int, [_vp, _ip, _ip, _vp, _vp, C.c_int, _vp, _vp, _ip]),
     "wc_synth_stream_rng_position": (C.c_ulonglong, [_vp, C.c_int]),
     "wc_synth_stream_set_rng_position": (C.c_int, [_vp, C.c_int, C.c_ulonglong]),
     "wc_synth_stream_frames_received": (C.c_longlong, [_vp, C.c_int]),
@@ -190,16 +191,34 @@ class StreamSynthesizer:
                                                   _ptr(d_sp), _ptr(d_ap), _ptr(d_y if d_y is not None else self._d_y), out))
         return list(out)
 
+    def push_coded_device(self, n_frames, d_f0, d_coded_sp, number_of_dimensions, d_coded_ap, flush=None, d_y=None):
+        """as push_device with coded rows (number_of_dimensions mel-cepstral coefficients and the band aperiodicities per frame)"""
+        out = (C.c_int * self.n_streams)()
+        _check(_lib().wc_synth_stream_push_coded_device(self._h, _ints(n_frames), _ints(flush) if flush is not None else None, _ptr(d_f0),
+                                                        _ptr(d_coded_sp), int(number_of_dimensions), _ptr(d_coded_ap),
+                                                        _ptr(d_y if d_y is not None else self._d_y), out))
+        return list(out)
+
     def push(self, f0s, sps, aps, flush=None):
         """f0s / sps / aps: per stream the new frames (empty = idle).  Returns the committed samples of every stream."""
+        return self._push(f0s, sps, aps, flush, self.bins, self.bins, self.push_device)
+
+    def push_coded(self, f0s, csps, caps, flush=None):
+        """push with coded rows: csps[u] (frames x number_of_dimensions), caps[u] (frames x number_of_aperiodicities(fs))"""
+        from .codec import number_of_aperiodicities
+        nd = next((np.shape(v)[1] for v in csps if len(v)), 1)
+        return self._push(f0s, csps, caps, flush, nd, number_of_aperiodicities(self.fs),
+                          lambda n, f, a, b, fl: self.push_coded_device(n, f, a, nd, b, fl))
+
+    def _push(self, f0s, sps, aps, flush, w_sp, w_ap, run):
         n_frames = [len(f) for f in f0s]
         tot = sum(n_frames)
         f0 = np.concatenate([np.asarray(f, dtype=np.float64) for f in f0s]) if tot else np.zeros(1)
-        sp = np.concatenate([np.asarray(v, dtype=np.float64).reshape(-1, self.bins) for v in sps]) if tot else np.zeros((1, self.bins))
-        ap = np.concatenate([np.asarray(v, dtype=np.float64).reshape(-1, self.bins) for v in aps]) if tot else np.zeros((1, self.bins))
+        sp = np.concatenate([np.asarray(v, dtype=np.float64).reshape(-1, w_sp) for v in sps]) if tot else np.zeros((1, w_sp))
+        ap = np.concatenate([np.asarray(v, dtype=np.float64).reshape(-1, w_ap) for v in aps]) if tot else np.zeros((1, w_ap))
         d = [DeviceArray.from_host(np.ascontiguousarray(a)) for a in (f0, sp, ap)]
         try:
-            counts = self.push_device(n_frames, d[0], d[1], d[2], flush)
+            counts = run(n_frames, d[0], d[1], d[2], flush)
         finally:
             for a in d:
                 a.free()
