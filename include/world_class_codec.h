@@ -19,9 +19,11 @@ extern "C" {
 
 /* reference include/codec.hpp:23, src/codec.cpp:211-214: int(min(15000, fs / 2 - 3000) / 3000) */
 int GetNumberOfAperiodicities(int fs);
-/* reference include/codec.hpp:38-39, src/codec.cpp:216-236 */
+/* reference include/codec.hpp:38-39, src/codec.cpp:216-236.  Below 12 kHz there is no band and nothing is written. */
 void CodeAperiodicity(const double *const *aperiodicity, int f0_length, int fs, int fft_size, double **coded_aperiodicity);
-/* reference include/codec.hpp:53-54, src/codec.cpp:238-267 */
+/* reference include/codec.hpp:53-54, src/codec.cpp:238-267.  Below 12 kHz (no band) the reference's mean of zero bands is NaN, so
+ * every frame counts as voiced: each row becomes 10^(v/20) of the line v from -60 dB at 0 Hz to -1e-12 dB at fs/2, and the coded
+ * rows are not read.  So does this function, and wc_decode_aperiodicity_device. */
 void DecodeAperiodicity(const double *const *coded_aperiodicity, int f0_length, int fs, int fft_size, double **aperiodicity);
 /* reference include/codec.hpp:69-71, src/codec.cpp:269-296 */
 void CodeSpectralEnvelope(const double *const *spectrogram, int f0_length, int fs, int fft_size, int number_of_dimensions,
@@ -35,7 +37,7 @@ int wc_code_spectral_envelope_device(int fs, int fft_size, long long n_frames, i
 									 double *d_coded);
 int wc_decode_spectral_envelope_device(int fs, int fft_size, long long n_frames, int number_of_dimensions, const double *d_coded,
 									   double *d_sp);
-int wc_code_aperiodicity_device(int fs, int fft_size, long long n_frames, const double *d_ap, double *d_coded);
+int wc_code_aperiodicity_device(int fs, int fft_size, long long n_frames, const double *d_ap, double *d_coded);  /* fs >= 12 kHz */
 int wc_decode_aperiodicity_device(int fs, int fft_size, long long n_frames, const double *d_coded, double *d_ap);
 /* Both decoders in one pass, the input of Synthesis from coded features: d_coded_sp (n_frames x number_of_dimensions) and
  * d_coded_ap (n_frames x GetNumberOfAperiodicities(fs)) -> d_sp, d_ap (n_frames x (fft_size/2+1) each).  fft_size 2048: one

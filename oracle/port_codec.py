@@ -1,5 +1,6 @@
 """TEST INFRASTRUCTURE ONLY.  numpy restatement of the reference's feature codec (src/codec.cpp:12-325), pinned to the real
-reference by tests/test_codec_oracle.py through tests/golden/io/codec_golden.npz (made by oracle/gen_golden_codec.py)."""
+reference by tests/test_codec_oracle.py through tests/golden/io/codec_golden.npz (made by oracle/gen_golden_codec.py) and
+tests/golden/io/codec_sizes.npz (every fft size and band count, oracle/gen_golden_codec_sizes.py)."""
 import numpy as np
 
 from .port_io import interp1
@@ -83,7 +84,8 @@ def code_aperiodicity(ap, fs, fft_size):
 
 
 def decode_aperiodicity(coded, fs, fft_size):
-    """reference :238-267"""
+    """reference :238-267.  Below 12 kHz there is no band: the mean is 0 / 0 = NaN, not above -0.5, so every frame is voiced and
+    decodes to the line from -60 dB at 0 Hz to -1e-12 dB at fs/2"""
     n_ap = number_of_aperiodicities(fs)
     bins = fft_size // 2 + 1
     freq = fs / fft_size * np.arange(bins)
@@ -93,7 +95,7 @@ def decode_aperiodicity(coded, fs, fft_size):
         tmp = 0.0
         for v in coded[f]:
             tmp += v
-        if tmp / n_ap > -0.5:
+        if (tmp / n_ap if n_ap else np.nan) > -0.5:
             continue
         coarse = np.concatenate([[-60.0], coded[f], [-SAFE]])
         out[f] = np.power(10.0, interp1(coarse_axis, coarse, freq) / 20.0)

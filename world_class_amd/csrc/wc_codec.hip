@@ -153,7 +153,7 @@ __global__ __launch_bounds__(256) void decode_ap_kernel(const double *__restrict
 	double *__restrict__ row = ap + (long long)blockIdx.x * bins;
 	double tmp = 0.0;
 	for (int i = 0; i < n_ap; ++i) tmp += c[i];
-	tmp /= n_ap;
+	tmp /= n_ap;  // no band (fs below 12 kHz): 0 / 0 = NaN, voiced, and the row is the line from -60 dB at 0 Hz to fs/2
 	if (tmp > -0.5) {  // CheckVUV: treated as unvoiced, the initial value stays
 		for (int j = threadIdx.x; j < bins; j += 256) row[j] = 1.0 - kSafeGuard;
 		return;
@@ -336,8 +336,8 @@ int wc_code_aperiodicity_device(int fs, int fft_size, long long n_frames, const 
 }
 
 int wc_decode_aperiodicity_device(int fs, int fft_size, long long n_frames, const double *d_coded, double *d_ap) {
-	const int n_ap = GetNumberOfAperiodicities(fs);
-	if (fs <= 0 || fft_size < 2 || n_frames < 0 || n_ap < 1) return fail(WC_ERR_INVALID, "decode_aperiodicity: bad argument (fs must exceed 12 kHz)");
+	const int n_ap = GetNumberOfAperiodicities(fs);  // 0 below 12 kHz: d_coded is not read (reference :238-267 fills every row)
+	if (fs <= 0 || fft_size < 2 || n_frames < 0) return fail(WC_ERR_INVALID, "decode_aperiodicity: bad argument");
 	Device *dev = current_device();
 	if (!dev) return WC_ERR_DEVICE;
 	DeviceLock lock(dev);
@@ -376,11 +376,11 @@ void DecodeSpectralEnvelope(const double *const *coded_spectral_envelope, int f0
 void CodeAperiodicity(const double *const *aperiodicity, int f0_length, int fs, int fft_size, double **coded_aperiodicity) {
 	Device *dev = current_device();
 	if (!dev) { report(WC_ERR_DEVICE); return; }
-	if (f0_length <= 0) return;
 	const int n_ap = GetNumberOfAperiodicities(fs);
+	if (f0_length <= 0 || n_ap < 1) return;  // no band below 12 kHz: the reference writes nothing either
 	ScopedBuf in, out;
 	int rc = rows_to_device(aperiodicity, f0_length, fft_size / 2 + 1, in, dev->active());
-	if (!rc) rc = out.reserve(sizeof(double) * (size_t)f0_length * (n_ap > 0 ? n_ap : 1));
+	if (!rc) rc = out.reserve(sizeof(double) * (size_t)f0_length * n_ap);
 	if (!rc) rc = wc_code_aperiodicity_device(fs, fft_size, f0_length, in.as<double>(), out.as<double>());
 	if (!rc) rc = device_to_rows(out, f0_length, n_ap, coded_aperiodicity, dev->active());
 	report(rc);
@@ -392,7 +392,7 @@ void DecodeAperiodicity(const double *const *coded_aperiodicity, int f0_length, 
 	if (f0_length <= 0) return;
 	const int n_ap = GetNumberOfAperiodicities(fs);
 	ScopedBuf in, out;
-	int rc = n_ap >= 1 ? rows_to_device(coded_aperiodicity, f0_length, n_ap, in, dev->active()) : fail(WC_ERR_INVALID, "decode_aperiodicity: fs must exceed 12 kHz");
+	int rc = n_ap >= 1 ? rows_to_device(coded_aperiodicity, f0_length, n_ap, in, dev->active()) : WC_OK;  // no band: nothing to read
 	if (!rc) rc = out.reserve(sizeof(double) * (size_t)f0_length * (fft_size / 2 + 1));
 	if (!rc) rc = wc_decode_aperiodicity_device(fs, fft_size, f0_length, in.as<double>(), out.as<double>());
 	if (!rc) rc = device_to_rows(out, f0_length, fft_size / 2 + 1, aperiodicity, dev->active());
