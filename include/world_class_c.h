@@ -187,6 +187,13 @@ int wc_pipeline_get_fft_size(const wc_pipeline *p);
 int wc_pipeline_set_option(wc_pipeline *p, const char *name, const char *value);
 int wc_pipeline_run_device(wc_pipeline *p, int n_utt, const double *d_x, const int *x_length, double *d_tpos, double *d_f0,
                            double *d_sp, double *d_ap, double *d_y, uint64_t *rng_pos);
+/* The same step with the feature coder (world_class_codec.h: wc_code_features_device) behind CheapTrick / D4C: the full rows stay in
+ * buffers of the handle, and what comes out per frame is d_coded_sp (number_of_dimensions mel-cepstral coefficients,
+ * 1 .. fft_size/4+1) and d_coded_ap (GetNumberOfAperiodicities(fs) band values; NULL: spectral envelope only, required NULL below
+ * 12 kHz).  tpos, f0, y and the returned rng_pos are those of wc_pipeline_run_device bit for bit, the coded rows those of
+ * wc_code_features_device on its rows.  Arguments are checked before anything runs; the coder is enqueued on the caller's stream. */
+int wc_pipeline_run_coded_device(wc_pipeline *p, int n_utt, const double *d_x, const int *x_length, double *d_tpos, double *d_f0,
+                                 double *d_coded_sp, int number_of_dimensions, double *d_coded_ap, double *d_y, uint64_t *rng_pos);
 
 /* Host batch front-end: n_utt ragged utterances given by host pointers: doubles (x_is_pcm16 = 0), the 16-bit PCM samples of a
  * WAV file (x_is_pcm16 = 1: expanded on the device as sample / 32768, what the reference's wavread returns) or 32-bit floats

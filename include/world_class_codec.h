@@ -46,6 +46,16 @@ int wc_decode_aperiodicity_device(int fs, int fft_size, long long n_frames, cons
  * new fs). */
 int wc_decode_features_device(int fs, int fft_size, long long n_frames, int number_of_dimensions, const double *d_coded_sp,
                               const double *d_coded_ap, double *d_sp, double *d_ap);
+/* Both coders in one pass: d_sp, d_ap (n_frames x (fft_size/2+1)) -> d_coded_sp (n_frames x number_of_dimensions),
+ * d_coded_ap (n_frames x GetNumberOfAperiodicities(fs)).  d_ap and d_coded_ap may both be NULL (sp only; then any fs).
+ * fft_size 2048, 4096: one wavefront per frame with the transform in registers; 512, 1024: the kernels of the two single coders.
+ * Either way the plan is built once per (device, fs, fft_size) and kept, so a call only enqueues on the calling thread's stream
+ * (wc_set_stream) and never waits for the device, and a frame's coded rows depend on that frame alone, bit for bit.  Within
+ * 1e-11 of the reference like the single coders, not bit-identical to them at fft_size 2048 / 4096 (another order of operations).
+ * Refused with WC_ERR_INVALID, outputs untouched: another fft_size, number_of_dimensions outside 1 .. fft_size/4+1, aperiodicity
+ * below 12 kHz, exactly one of d_ap / d_coded_ap NULL, NULL sp arrays with n_frames > 0, n_frames < 0 or above 2^32-1. */
+int wc_code_features_device(int fs, int fft_size, long long n_frames, int number_of_dimensions, const double *d_sp,
+                            const double *d_ap, double *d_coded_sp, double *d_coded_ap);
 
 #ifdef __cplusplus
 }

@@ -94,6 +94,17 @@ int wc_stream_set_rng_position(wc_stream *s, int stream, unsigned long long posi
 int wc_stream_set_aperiodicity(wc_stream *s, double d4c_threshold);
 int wc_stream_push_device_ex(wc_stream *s, const void *d_chunk, int chunk_format, const int *n_new, const int *flush, double *d_tpos,
                              double *d_f0, double *d_sp, double *d_ap, int *frames_out);
+/* The same push with the committed frames CODED (world_class_codec.h: wc_code_features_device): the rows go to buffers of the handle
+ * (max_frames_per_push x n_streams rows, allocated on the first coded push, released by wc_stream_destroy) and are coded from
+ * there on the caller's stream into d_coded_sp (number_of_dimensions doubles per frame, 1 .. fft_size/4+1) and d_coded_ap
+ * (GetNumberOfAperiodicities(fs) per frame), packed by frames_out like d_f0.  d_coded_ap goes with wc_stream_set_aperiodicity
+ * (and an fs of at least 12 kHz): non-NULL on a stream with it, NULL on one without (spectral envelope only); the other two
+ * combinations are refused.  Arguments are checked and the buffers reserved before the push: a refused call leaves every stream's
+ * state untouched.  Coded and plain pushes may alternate on a handle; frames, noise positions and accounting are those of the
+ * plain push.  With wc_synth_stream_push_coded_device this closes the loop analysis -> modify -> synthesis in the coded domain
+ * without a row leaving the device: 60 + 5 doubles per frame instead of 2 x 1025 at 48 kHz. */
+int wc_stream_push_coded_device(wc_stream *s, const void *d_chunk, int chunk_format, const int *n_new, const int *flush, double *d_tpos,
+                                double *d_f0, double *d_coded_sp, int number_of_dimensions, double *d_coded_ap, int *frames_out);
 /* D4C's noise position of stream u (0 after creation and reset) */
 unsigned long long wc_stream_d4c_rng_position(const wc_stream *s, int stream);
 int wc_stream_set_d4c_rng_position(wc_stream *s, int stream, unsigned long long position);

@@ -31,6 +31,16 @@ class Pipeline:
                                             _ptr(d_ap), _ptr(d_y), arg))
         return list(arr) if arr is not None else None
 
+    def run_coded_device(self, d_x, x_lengths, d_tpos, d_f0, d_coded_sp, number_of_dimensions, d_coded_ap, d_y, rng_pos=None):
+        """wc_pipeline_run_coded_device: run_device with the feature coder behind CheapTrick / D4C -- per frame `number_of_dimensions`
+        mel-cepstral coefficients and the band aperiodicities (d_coded_ap None: the spectral envelope alone) instead of the rows"""
+        n = len(x_lengths)
+        arr, arg = _rng_arg(rng_pos, n)
+        _check(lib().wc_pipeline_run_coded_device(self._h, n, _ptr(d_x), _ints(x_lengths), _ptr(d_tpos), _ptr(d_f0), _ptr(d_coded_sp),
+                                                  int(number_of_dimensions), None if d_coded_ap is None else _ptr(d_coded_ap),
+                                                  _ptr(d_y), arg))
+        return list(arr) if arr is not None else None
+
     def run_batch(self, xs, rng_pos=None):
         """Host lists in, list of dicts (tpos, f0, sp, ap, y) out."""
         xl = [len(x) for x in xs]

@@ -19,6 +19,7 @@ CODEC_SIGNATURES = {
     "wc_code_aperiodicity_device": (C.c_int, [C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p]),
     "wc_decode_aperiodicity_device": (C.c_int, [C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p]),
     "wc_decode_features_device": (C.c_int, [C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "wc_code_features_device": (C.c_int, [C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _bound = False
@@ -93,3 +94,11 @@ def decode_features_device(fs, fft_size, n_frames, number_of_dimensions, d_coded
     """both coded rows of n_frames frames -> spectrogram and aperiodicity rows (fft_size/2+1 each), one pass on the device"""
     _check(_L().wc_decode_features_device(int(fs), int(fft_size), int(n_frames), int(number_of_dimensions), _ptr(d_coded_sp),
                                           _ptr(d_coded_ap), _ptr(d_sp), _ptr(d_ap)))
+
+
+def code_features_device(fs, fft_size, n_frames, number_of_dimensions, d_sp, d_ap, d_coded_sp, d_coded_ap):
+    """spectrogram and aperiodicity rows of n_frames frames -> both coded rows, one pass on the device, enqueue-only;
+    d_ap and d_coded_ap both None: the spectral envelope alone"""
+    _check(_L().wc_code_features_device(int(fs), int(fft_size), int(n_frames), int(number_of_dimensions), _ptr(d_sp),
+                                        None if d_ap is None else _ptr(d_ap), _ptr(d_coded_sp),
+                                        None if d_coded_ap is None else _ptr(d_coded_ap)))

@@ -244,6 +244,52 @@ void wc::codec_decode_sp_plan(int fs, int fft_size, int nd, std::vector<int> &k,
 	interp1_plan(mel_axis, freq_axis, k, s);
 }
 
+// GetParametersForCoding, reference :125-142
+void wc::codec_code_sp_plan(int fs, int fft_size, std::vector<int> &k, std::vector<double> &s, std::vector<double2> &w) {
+	const int md = fft_size / 2;
+	const double floor_mel = frequency_to_mel(kFloorFrequency);
+	const double ceil_mel = frequency_to_mel(fs / 2.0 < kCeilFrequency ? fs / 2.0 : kCeilFrequency);
+	std::vector<double> mel_axis(md), freq_axis(md + 1);
+	w.assign(md, make_double2(0.0, 0.0));
+	for (int i = 0; i < md; ++i) {
+		mel_axis[i] = (ceil_mel - floor_mel) * i / md + floor_mel;
+		w[i] = make_double2(2.0 * std::cos(i * kPiH / fft_size) / std::sqrt((double)fft_size),
+							2.0 * std::sin(i * kPiH / fft_size) / std::sqrt((double)fft_size));
+		freq_axis[i] = frequency_to_mel(static_cast<double>(i) * fs / fft_size);
+	}
+	w[0].x /= std::sqrt(2.0);
+	// the reference leaves frequency_axis[fft_size/2] unset (:140-141) and never reaches it: every mel point lies below
+	// frequency_axis[fft_size/2 - 1]; the natural value keeps the axis monotone
+	freq_axis[md] = frequency_to_mel(static_cast<double>(md) * fs / fft_size);
+	interp1_plan(freq_axis, mel_axis, k, s);
+}
+
+// the workgroup-per-frame coders on a plan that lives on the device (wc_code_features.hip keeps one per (device, fs, fft_size))
+int wc::codec_code_sp_launch(Device *dev, hipStream_t st, int fft_size, long long n_frames, int nd, const double *d_sp, double *d_coded,
+							 const int *d_k, const double *d_s, const double2 *d_w) {
+	SpPlan plan;
+	plan.k = const_cast<int *>(d_k);
+	plan.s = const_cast<double *>(d_s);
+	plan.w = const_cast<double2 *>(d_w);
+	const dim3 grid((unsigned)n_frames), block(256);
+	switch (fft_size / 2) {
+		case 256: hipLaunchKernelGGL(code_sp_kernel<256>, grid, block, 0, st, d_sp, d_coded, nd, plan, dev->twiddle); break;
+		case 512: hipLaunchKernelGGL(code_sp_kernel<512>, grid, block, 0, st, d_sp, d_coded, nd, plan, dev->twiddle); break;
+		case 1024: hipLaunchKernelGGL(code_sp_kernel<1024>, grid, block, 0, st, d_sp, d_coded, nd, plan, dev->twiddle); break;
+		default: hipLaunchKernelGGL(code_sp_kernel<2048>, grid, block, 0, st, d_sp, d_coded, nd, plan, dev->twiddle); break;
+	}
+	WC_HIP(hipGetLastError());
+	return WC_OK;
+}
+
+int wc::codec_code_ap_launch(hipStream_t st, int fs, int fft_size, long long n_frames, const double *d_ap, double *d_coded) {
+	const int n_ap = GetNumberOfAperiodicities(fs);
+	const long long total = n_frames * n_ap;
+	hipLaunchKernelGGL(code_ap_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, d_ap, d_coded, n_frames, n_ap, fs, fft_size);
+	WC_HIP(hipGetLastError());
+	return WC_OK;
+}
+
 extern "C" {
 
 int GetNumberOfAperiodicities(int fs) {
@@ -259,24 +305,10 @@ int wc_code_spectral_envelope_device(int fs, int fft_size, long long n_frames, i
 	DeviceLock lock(dev);
 	if (n_frames == 0) return WC_OK;
 	const int md = fft_size / 2;
-	// GetParametersForCoding, reference :125-142
-	const double floor_mel = frequency_to_mel(kFloorFrequency);
-	const double ceil_mel = frequency_to_mel(fs / 2.0 < kCeilFrequency ? fs / 2.0 : kCeilFrequency);
-	std::vector<double> mel_axis(md), freq_axis(md + 1);
-	std::vector<double2> w(md);
-	for (int i = 0; i < md; ++i) {
-		mel_axis[i] = (ceil_mel - floor_mel) * i / md + floor_mel;
-		w[i] = make_double2(2.0 * std::cos(i * kPiH / fft_size) / std::sqrt((double)fft_size),
-							2.0 * std::sin(i * kPiH / fft_size) / std::sqrt((double)fft_size));
-		freq_axis[i] = frequency_to_mel(static_cast<double>(i) * fs / fft_size);
-	}
-	w[0].x /= std::sqrt(2.0);
-	// the reference leaves frequency_axis[fft_size/2] unset (:140-141) and never reaches it: every mel point lies below
-	// frequency_axis[fft_size/2 - 1]; the natural value keeps the axis monotone
-	freq_axis[md] = frequency_to_mel(static_cast<double>(md) * fs / fft_size);
 	std::vector<int> k;
 	std::vector<double> s;
-	interp1_plan(freq_axis, mel_axis, k, s);
+	std::vector<double2> w;
+	codec_code_sp_plan(fs, fft_size, k, s, w);
 	PlanBufs bufs;
 	SpPlan plan;
 	int rc;

@@ -841,6 +841,31 @@ int wc_pipeline_run_device(wc_pipeline *p, int n_utt, const double *d_x, const i
 	return pipeline_run(p, n_utt, d_x, x_length, d_tpos, d_f0, d_sp, d_ap, d_y, rng_pos, nullptr);
 }
 
+// wc_pipeline_run_device with the rows kept in the handle and the feature coder (wc::code_features_enqueue) behind the step, on the
+// caller's stream: what leaves is number_of_dimensions + GetNumberOfAperiodicities(fs) doubles per frame instead of fft_size + 2.
+// Everything is checked and the plan built before the step runs.
+int wc_pipeline_run_coded_device(wc_pipeline *p, int n_utt, const double *d_x, const int *x_length, double *d_tpos, double *d_f0,
+								 double *d_coded_sp, int number_of_dimensions, double *d_coded_ap, double *d_y, uint64_t *rng_pos) {
+	if (!p || n_utt <= 0 || !d_x || !x_length || !d_tpos || !d_f0 || !d_coded_sp || !d_y) return fail(WC_ERR_INVALID, "pipeline: null argument");
+	if (const char *why = code_features_check(p->fs, p->fft_size, number_of_dimensions, d_coded_ap != nullptr)) return fail(WC_ERR_INVALID, why);
+	WC_HIP(hipSetDevice(p->dev->id));
+	DeviceLock lock(p->dev);
+	long long nf = 0;
+	for (int u = 0; u < n_utt; ++u) {
+		if (x_length[u] <= 0) return fail(WC_ERR_INVALID, "pipeline: non-positive x_length");
+		nf += wc_get_samples(p->fs, x_length[u], p->frame_period);
+	}
+	const int bins = p->fft_size / 2 + 1;
+	int rc;
+	if ((rc = p->b_sp.reserve(sizeof(double) * nf * bins))) return rc;
+	if ((rc = p->b_ap.reserve(sizeof(double) * nf * bins))) return rc;
+	if ((rc = code_features_prepare(p->dev, p->fs, p->fft_size))) return rc;
+	if ((rc = pipeline_run(p, n_utt, d_x, x_length, d_tpos, d_f0, p->b_sp.as<double>(), p->b_ap.as<double>(), d_y, rng_pos, nullptr))) return rc;
+	// (the step has waited for every group's Synthesis, the last reader of the rows, to hand back the noise positions)
+	return code_features_enqueue(p->dev, p->dev->active(), p->fs, p->fft_size, nf, number_of_dimensions, p->b_sp.as<double>(),
+								 d_coded_ap ? p->b_ap.as<double>() : nullptr, d_coded_sp, d_coded_ap);
+}
+
 // Host batch front-end: ragged utterances as 16-bit PCM (as stored in a WAV file) or as doubles,
 // gathered into pinned memory, one H2D copy, expanded on the device, fused pipeline, outputs packed into pinned memory with
 // one D2H copy per requested array, scattered to the caller's per-utterance buffers.  Any output table may be NULL.

@@ -64,4 +64,23 @@ const char *decode_features_check(int fs, int fft_size, int nd);
 // kernel, enqueued on s; other sizes: the codec's workgroup-per-frame kernels (wc_decode_*_device) on dev's active stream.
 int decode_features_enqueue(Device *dev, hipStream_t s, int fs, int fft_size, long long n_frames, int nd, const double *d_coded_sp,
 							const double *d_coded_ap, double *d_sp, double *d_ap);
+
+// Feature coding (wc_codec.hip, wc_code_features.hip)
+// GetParametersForCoding (reference src/codec.cpp:125-142): the interp1 plan (k, s) from bins 0 .. fft_size/2 (in mel) onto the
+// fft_size/2 points of the mel axis and the DCT weights
+void codec_code_sp_plan(int fs, int fft_size, std::vector<int> &k, std::vector<double> &s, std::vector<double2> &w);
+// code_sp_kernel / code_ap_kernel enqueued on st with a plan that already lives on the device (arguments already checked)
+int codec_code_sp_launch(Device *dev, hipStream_t st, int fft_size, long long n_frames, int nd, const double *d_sp, double *d_coded,
+						 const int *d_k, const double *d_s, const double2 *d_w);
+int codec_code_ap_launch(hipStream_t st, int fs, int fft_size, long long n_frames, const double *d_ap, double *d_coded);
+// nullptr if (fs, fft_size, nd) can be coded, else why not: fft_size 512 .. 4096, 1 <= nd <= fft_size/4+1, and with the
+// aperiodicity fs >= 12 kHz (at least one band)
+const char *code_features_check(int fs, int fft_size, int nd, bool with_ap);
+// builds and uploads the coding plan of (dev, fs, fft_size) unless it is there already (the only step of a coding call that
+// allocates or waits; callers that must not fail behind a state change run it first)
+int code_features_prepare(Device *dev, int fs, int fft_size);
+// Both rows of n_frames frames -> coded rows, enqueued on s (arguments already checked; d_ap and d_coded_ap both NULL: sp only).
+// fft_size 2048 / 4096: the one-wavefront kernel; 512 / 1024: the codec's workgroup-per-frame kernels on the cached plan.
+int code_features_enqueue(Device *dev, hipStream_t s, int fs, int fft_size, long long n_frames, int nd, const double *d_sp,
+						  const double *d_ap, double *d_coded_sp, double *d_coded_ap);
 }  // namespace wc

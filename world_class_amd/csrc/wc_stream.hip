@@ -118,6 +118,7 @@ struct wc_stream {
 	std::vector<char> closed;
 	std::vector<uint64_t> rng_pos, d4c_pos;  // noise positions of CheapTrick / D4C
 	DevBuf hist[2], rows_c[2], rows_s[2], batch, hbatch, win_tpos, win_f0, tpos_rel, desc, chunk_f64;
+	DevBuf full_sp, full_ap;  // wc_stream_push_coded_device: the committed rows of a push (max_frames_per_push x n_streams), coded from here
 	HostBuf h_desc;
 	// harvest option copies for the handles created on demand
 	double hv_floor, hv_ceil;
@@ -220,7 +221,7 @@ void wc_stream_destroy(wc_stream *s) {
 	wc_harvest_destroy(s->hv_front);
 	wc_harvest_destroy(s->hv_tail);
 	for (DevBuf *b : {&s->hist[0], &s->hist[1], &s->rows_c[0], &s->rows_c[1], &s->rows_s[0], &s->rows_s[1], &s->batch, &s->hbatch, &s->win_tpos,
-					  &s->win_f0, &s->tpos_rel, &s->desc, &s->chunk_f64})
+					  &s->win_f0, &s->tpos_rel, &s->desc, &s->chunk_f64, &s->full_sp, &s->full_ap})
 		b->release();
 	s->h_desc.release();
 	delete s;
@@ -565,6 +566,33 @@ int wc_stream_push_device_ex(wc_stream *s, const void *d_chunk, int chunk_format
 	int rc;
 	if ((rc = stream_widen(s, d_chunk, chunk_format, n_new))) return rc;
 	return stream_push(s, s->chunk_f64.as<double>(), n_new, flush, d_tpos, d_f0, d_sp, d_ap, frames_out);
+}
+
+// The push of wc_stream_push_device_ex with the committed rows kept in the handle and coded from there (wc::code_features_enqueue) on
+// the caller's stream.  Everything that can be refused or can fail to allocate comes before the push, so a failed call leaves every
+// stream's state untouched.
+int wc_stream_push_coded_device(wc_stream *s, const void *d_chunk, int chunk_format, const int *n_new, const int *flush, double *d_tpos,
+								double *d_f0, double *d_coded_sp, int number_of_dimensions, double *d_coded_ap, int *frames_out) {
+	if (!s || !d_chunk || !d_tpos || !d_f0 || !d_coded_sp || !frames_out) return fail(WC_ERR_INVALID, "stream push: null argument");
+	if ((s->d4c != nullptr) != (d_coded_ap != nullptr))
+		return fail(WC_ERR_INVALID, s->d4c ? "stream push: aperiodicity is on: push with a d_coded_ap"
+										   : "stream push: d_coded_ap given but wc_stream_set_aperiodicity was not called");
+	if (const char *why = code_features_check(s->fs, s->fft_size, number_of_dimensions, d_coded_ap != nullptr)) return fail(WC_ERR_INVALID, why);
+	WC_HIP(hipSetDevice(s->dev->id));
+	DeviceLock lock(s->dev);
+	const int bins = s->fft_size / 2 + 1;
+	const size_t row_bytes = sizeof(double) * (size_t)wc_stream_max_frames_per_push(s) * s->n_streams * bins;
+	int rc;
+	if ((rc = s->full_sp.reserve(row_bytes))) return rc;
+	if (d_coded_ap && (rc = s->full_ap.reserve(row_bytes))) return rc;
+	if ((rc = code_features_prepare(s->dev, s->fs, s->fft_size))) return rc;
+	if ((rc = wc_stream_push_device_ex(s, d_chunk, chunk_format, n_new, flush, d_tpos, d_f0, s->full_sp.as<double>(),
+									   d_coded_ap ? s->full_ap.as<double>() : nullptr, frames_out)))
+		return rc;
+	long long total = 0;
+	for (int u = 0; u < s->n_streams; ++u) total += frames_out[u];
+	return code_features_enqueue(s->dev, s->dev->active(), s->fs, s->fft_size, total, number_of_dimensions, s->full_sp.as<double>(),
+								 d_coded_ap ? s->full_ap.as<double>() : nullptr, d_coded_sp, d_coded_ap);
 }
 
 unsigned long long wc_stream_d4c_rng_position(const wc_stream *s, int u) { return (s && u >= 0 && u < s->n_streams) ? s->d4c_pos[u] : 0ull; }

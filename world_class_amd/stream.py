@@ -25,6 +25,7 @@ STREAM_SIGNATURES = {
     "wc_stream_samples_received": (C.c_longlong, [_vp, C.c_int]),
     "wc_stream_set_aperiodicity": (C.c_int, [_vp, C.c_double]),
     "wc_stream_push_device_ex": (C.c_int, [_vp, _vp, C.c_int, _ip, _ip, _vp, _vp, _vp, _vp, _ip]),
+    "wc_stream_push_coded_device": (C.c_int, [_vp, _vp, C.c_int, _ip, _ip, _vp, _vp, _vp, C.c_int, _vp, _ip]),
     "wc_stream_d4c_rng_position": (C.c_ulonglong, [_vp, C.c_int]),
     "wc_stream_set_d4c_rng_position": (C.c_int, [_vp, C.c_int, C.c_ulonglong]),
     "wc_synth_stream_create": (_vp, [C.c_int, C.c_int, C.c_double, C.c_int, C.c_int]),
@@ -76,6 +77,7 @@ class StreamAnalyzer:
         cap = n_streams * self.max_frames
         self._d_t, self._d_f, self._d_sp = DeviceArray(cap), DeviceArray(cap), DeviceArray(cap * self.bins)
         self._d_ap = DeviceArray(cap * self.bins) if self.aperiodicity else None
+        self._d_csp = self._d_cap = None  # coded rows of push_coded: allocated on its first call
 
     def push_device(self, d_chunk, n_new=None, flush=None, d_tpos=None, d_f0=None, d_sp=None, chunk_format=0, d_ap=None):
         """device pointers in and out (packed layouts of the header); chunk_format 0 = float64, 1 = int16 PCM, 2 = float32;
@@ -120,6 +122,54 @@ class StreamAnalyzer:
             o += c
         return res
 
+    def push_coded_device(self, d_chunk, d_coded_sp, number_of_dimensions, d_coded_ap=None, n_new=None, flush=None, d_tpos=None, d_f0=None,
+                          chunk_format=0):
+        """push_device with the committed frames coded on the device: d_coded_sp takes number_of_dimensions doubles per frame,
+        d_coded_ap (streams created with aperiodicity=True, else None) number_of_aperiodicities(fs); returns frames per stream"""
+        n = self.n_streams
+        out = (C.c_int * n)()
+        nn = _ints(n_new) if n_new is not None else None
+        fl = _ints(flush) if flush is not None else None
+        t = _ptr(d_tpos if d_tpos is not None else self._d_t)
+        f = _ptr(d_f0 if d_f0 is not None else self._d_f)
+        _check(_lib().wc_stream_push_coded_device(self._h, _ptr(d_chunk), chunk_format, nn, fl, t, f, _ptr(d_coded_sp), int(number_of_dimensions),
+                                                  None if d_coded_ap is None else _ptr(d_coded_ap), out))
+        return list(out)
+
+    def push_coded(self, chunks, number_of_dimensions=60, flush=None):
+        """push with coded results: a list of dicts (tpos, f0, csp, and cap when aperiodicity is on) per stream"""
+        from .codec import number_of_aperiodicities
+        nd, n_ap = int(number_of_dimensions), number_of_aperiodicities(self.fs) if self.aperiodicity else 0
+        cap = self.n_streams * self.max_frames
+        if self._d_csp is None or self._d_csp.n < cap * nd:
+            self._d_csp = DeviceArray(cap * nd)
+        if self.aperiodicity and self._d_cap is None:
+            self._d_cap = DeviceArray(cap * max(n_ap, 1))
+        filled = [np.asarray(c) for c in chunks if len(c)]  # (idle streams pass empty chunks of any type)
+        dt = filled[0].dtype if filled and filled[0].dtype in (np.int16, np.float32) else np.dtype(np.float64)
+        assert all(c.dtype == dt or dt == np.float64 for c in filled), "chunks of one push share a sample format"
+        fmt = {np.dtype(np.int16): 1, np.dtype(np.float32): 2}.get(np.dtype(dt), 0)
+        chunks = [np.ascontiguousarray(c, dtype=dt) for c in chunks]
+        n_new = [len(c) for c in chunks]
+        flat = np.concatenate(chunks) if sum(n_new) else np.zeros(1, dtype=dt)
+        d = DeviceArray.from_host(flat, dtype=dt)
+        try:
+            counts = self.push_coded_device(d, self._d_csp, nd, self._d_cap if self.aperiodicity else None, n_new, flush, chunk_format=fmt)
+        finally:
+            d.free()
+        tot = sum(counts)
+        t = self._d_t.to_host()[:tot]
+        f = self._d_f.to_host()[:tot]
+        csp = self._d_csp.to_host()[:tot * nd].reshape(tot, nd)
+        cap_rows = self._d_cap.to_host()[:tot * n_ap].reshape(tot, n_ap) if self.aperiodicity else None
+        res, o = [], 0
+        for c in counts:
+            res.append(dict(tpos=t[o:o + c].copy(), f0=f[o:o + c].copy(), csp=csp[o:o + c].copy()))
+            if cap_rows is not None:
+                res[-1]["cap"] = cap_rows[o:o + c].copy()
+            o += c
+        return res
+
     def reset(self, stream):
         _check(_lib().wc_stream_reset(self._h, stream))
 
@@ -138,12 +188,13 @@ class StreamAnalyzer:
     def frames_committed(self, stream):
         return int(_lib().wc_stream_frames_committed(self._h, stream))
 
-    def run_whole(self, xs):
+    def run_whole(self, xs, coded=None):
         """convenience for tests: stream whole signals chunk by chunk (all streams in lockstep, ragged ends flushed) and return the
-        concatenated per-stream results"""
+        concatenated per-stream results; coded = a number of dimensions: through push_coded (csp / cap instead of sp / ap)"""
         assert len(xs) == self.n_streams
         cs = self.chunk_samples
-        acc = [dict(tpos=[], f0=[], sp=[], **({"ap": []} if self.aperiodicity else {})) for _ in xs]
+        keys = ("csp", "cap") if coded else ("sp", "ap")
+        acc = [dict(tpos=[], f0=[], **{keys[0]: []}, **({keys[1]: []} if self.aperiodicity else {})) for _ in xs]
         done = [False] * len(xs)
         pos = 0
         while not all(done):
@@ -157,7 +208,7 @@ class StreamAnalyzer:
                 chunks.append(x[pos:pos + cs])
                 flush.append(1 if last else 0)
                 done[u] = last
-            for u, r in enumerate(self.push(chunks, flush)):
+            for u, r in enumerate(self.push_coded(chunks, coded, flush) if coded else self.push(chunks, flush)):
                 for k in acc[u]:
                     acc[u][k].append(r[k])
             pos += cs
