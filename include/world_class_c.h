@@ -161,6 +161,14 @@ int wc_synthesis_compute_batch(wc_synthesis *s, int n_utt, const double *const *
 int wc_synthesis_compute_coded_device(wc_synthesis *s, int n_utt, const double *d_f0, const int *f0_length,
                                       const double *d_coded_sp, int number_of_dimensions, const double *d_coded_ap,
                                       const int *out_length, double *d_out, uint64_t *rng_pos);
+/* The same with a formant shift per frame: the rows are decoded by wc_decode_features_modified_device (world_class_codec.h) with
+ * d_spectral_ratio, one ratio per frame packed like d_f0 (0 = that frame as it is), and synthesised as above: the samples are
+ * those of that decoder followed by wc_synthesis_compute_device.  NULL: wc_synthesis_compute_coded_device, bit for bit.  A pitch
+ * shift is the caller's own product on d_f0 (wc_modify_parameters_frames_device does it per frame); the call does not copy it. */
+int wc_synthesis_compute_coded_modified_device(wc_synthesis *s, int n_utt, const double *d_f0, const int *f0_length,
+                                               const double *d_coded_sp, int number_of_dimensions, const double *d_coded_ap,
+                                               const double *d_spectral_ratio, const int *out_length, double *d_out,
+                                               uint64_t *rng_pos);
 /* The same from host arrays: f0[u] (f0_length[u] doubles), coded_sp[u] (f0_length[u] x number_of_dimensions), coded_ap[u]
  * (f0_length[u] x GetNumberOfAperiodicities(fs)) -- what wc_pipeline_run_batch_host_coded returns -- gathered into page-locked
  * staging and sent up in one copy; y[u]: out_length[u] doubles, or int16 quantised like the reference's wavwrite when

@@ -46,6 +46,15 @@ int wc_decode_aperiodicity_device(int fs, int fft_size, long long n_frames, cons
  * new fs). */
 int wc_decode_features_device(int fs, int fft_size, long long n_frames, int number_of_dimensions, const double *d_coded_sp,
                               const double *d_coded_ap, double *d_sp, double *d_ap);
+/* The decoder with the demo's formant shift inside (world_class_io.h): wc_decode_features_device followed by
+ * wc_modify_parameters_frames_device(fs, fft_size, n_frames, NULL, d_sp, NULL, d_spectral_ratio) -- d_spectral_ratio holds one
+ * ratio per frame with that call's per-frame rules (0 = leave the row, an invalid value = a row of NaN); the aperiodicity rows
+ * are not modified.  fft_size 2048: the stretch happens inside the one-wavefront kernel, on the log envelope it holds before its
+ * exp (no extra pass over the rows, no log, no second exp; d_sp within 1e-12 relative of the two calls); 512, 1024, 4096: the
+ * two calls, bit for bit.  d_spectral_ratio == NULL: wc_decode_features_device, bit for bit. */
+int wc_decode_features_modified_device(int fs, int fft_size, long long n_frames, int number_of_dimensions,
+                                       const double *d_coded_sp, const double *d_coded_ap, const double *d_spectral_ratio,
+                                       double *d_sp, double *d_ap);
 /* Both coders in one pass: d_sp, d_ap (n_frames x (fft_size/2+1)) -> d_coded_sp (n_frames x number_of_dimensions),
  * d_coded_ap (n_frames x GetNumberOfAperiodicities(fs)).  d_ap and d_coded_ap may both be NULL (sp only; then any fs).
  * fft_size 2048, 4096: one wavefront per frame with the transform in registers; 512, 1024: the kernels of the two single coders.

@@ -62,6 +62,16 @@ int wc_double_to_pcm16_device(const double *d_y, long long n, int16_t *d_pcm);
  * bins from int(fft_size / 2.0 * ratio) upward repeat the bin just below. */
 int wc_modify_parameters_device(int fs, int fft_size, long long n_frames, double *d_f0, double *d_sp, double f0_scale,
 								double spectral_ratio);
+/* The same with a scale and a ratio per frame (a packed batch or a push of many streams holds many speakers, and a shift may
+ * change over time): d_f0_scale and d_spectral_ratio are device arrays of n_frames doubles.  f0[i] *= d_f0_scale[i] (a plain
+ * product: NaN in, NaN out); row i of d_sp is, bit for bit, what the call above writes with spectral_ratio =
+ * d_spectral_ratio[i].  Any of d_f0, d_sp, d_f0_scale, d_spectral_ratio may be NULL: that part is left alone.  The values live
+ * on the device, so the host cannot refuse them; per frame: 0 leaves the row as it is, a finite ratio >= 2.0 / fft_size is
+ * stretched (below that the fill for ratio < 1 would read bin -1), anything else -- negative, NaN, infinite, 0 < ratio <
+ * 2.0 / fft_size -- turns that frame's row into NaN and touches no other frame.  Stream-ordered, enqueue-only.
+ * n_frames <= 0xffffffff. */
+int wc_modify_parameters_frames_device(int fs, int fft_size, long long n_frames, double *d_f0, double *d_sp,
+									   const double *d_f0_scale, const double *d_spectral_ratio);
 
 #ifdef __cplusplus
 }

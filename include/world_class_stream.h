@@ -101,8 +101,8 @@ int wc_stream_push_device_ex(wc_stream *s, const void *d_chunk, int chunk_format
  * (and an fs of at least 12 kHz): non-NULL on a stream with it, NULL on one without (spectral envelope only); the other two
  * combinations are refused.  Arguments are checked and the buffers reserved before the push: a refused call leaves every stream's
  * state untouched.  Coded and plain pushes may alternate on a handle; frames, noise positions and accounting are those of the
- * plain push.  With wc_synth_stream_push_coded_device this closes the loop analysis -> modify -> synthesis in the coded domain
- * without a row leaving the device: 60 + 5 doubles per frame instead of 2 x 1025 at 48 kHz. */
+ * plain push.  With wc_synth_stream_push_coded_device and wc_synth_stream_set_modification this closes the loop analysis ->
+ * modify -> synthesis in the coded domain without a row leaving the device: 60 + 5 doubles per frame instead of 2 x 1025 at 48 kHz. */
 int wc_stream_push_coded_device(wc_stream *s, const void *d_chunk, int chunk_format, const int *n_new, const int *flush, double *d_tpos,
                                 double *d_f0, double *d_coded_sp, int number_of_dimensions, double *d_coded_ap, int *frames_out);
 /* D4C's noise position of stream u (0 after creation and reset) */
@@ -130,7 +130,7 @@ long long wc_stream_samples_received(const wc_stream *s, int stream);
  * is the first sample at or after (F - 1) frame periods and P the waiting pulse.  Latency bound (tested): committed >=
  * (F - 2) * frame_period * fs - gap - fft_size/2, with the pulse gap at most 2 fs / (fs/fft_size + 1) samples in voiced
  * stretches (the interpolated F0 stays above half the lowest F0) and fs/500 in unvoiced ones: about one frame period, plus the
- * current pulse gap, plus fft_size/2 samples.  A flush commits everything up to wc_synthesis_out_length; a stream with fewer
+ * current pulse gap (of the F0 that reaches Synthesis: f0 * f0_scale under wc_synth_stream_set_modification), plus fft_size/2 samples.  A flush commits everything up to wc_synthesis_out_length; a stream with fewer
  * than two frames when flushed is an error.  Streams need not move in lockstep; a push that fails leaves every stream as it
  * was.  A stream holds at most 2^31 samples (the reference's int indices).
  *
@@ -157,6 +157,19 @@ int wc_synth_stream_push_device(wc_synth_stream *s, const int *n_frames, const i
 int wc_synth_stream_push_coded_device(wc_synth_stream *s, const int *n_frames, const int *flush, const double *d_f0,
                                       const double *d_coded_sp, int number_of_dimensions, const double *d_coded_ap,
                                       double *d_y, int *samples_out);
+/* Pitch and formant shift of one stream (the demo's ParameterModification, world_class_io.h), a host-side setting: (1.0, 0.0) --
+ * neutral -- after wc_synth_stream_create and wc_synth_stream_reset.  Refused with WC_ERR_INVALID, the setting unchanged, unless
+ * f0_scale is finite and > 0 and spectral_ratio is 0 (none) or finite and >= 2.0 / fft_size.  It applies to the frames that later
+ * wc_synth_stream_push_coded_device calls give that stream, so a change between two pushes takes effect at a frame boundary: the
+ * push decodes those frames with wc_decode_features_modified_device at the stream's ratio and synthesises them with
+ * f0 * f0_scale (kept in a buffer of the handle, max_frames_per_push x n_streams doubles, reserved on first use; the caller's
+ * d_f0 is not written).  The per-frame values go up through page-locked staging of the handle with an asynchronous copy, without
+ * a host synchronisation of their own.  A push in which every stream that receives frames is neutral is the push without
+ * settings: the same samples and the same cost.  The pulse-gap bound of the header's latency statement is a bound on the F0 that
+ * reaches Synthesis: with a setting it holds for f0 * f0_scale.
+ * wc_synth_stream_push_device takes full rows as they are and applies no setting: while a stream that receives frames in that
+ * push has a setting other than (1.0, 0.0) the push is refused and every stream keeps its state. */
+int wc_synth_stream_set_modification(wc_synth_stream *s, int stream, double f0_scale, double spectral_ratio);
 /* noise position of stream u: where its next (or waiting) pulse takes its draws */
 unsigned long long wc_synth_stream_rng_position(const wc_synth_stream *s, int stream);
 int wc_synth_stream_set_rng_position(wc_synth_stream *s, int stream, unsigned long long position);

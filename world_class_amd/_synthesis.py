@@ -65,6 +65,17 @@ class Synthesis:
                                                        _ptr(d_coded_ap), _ints(out_lengths), _ptr(d_out), arg))
         return list(arr) if arr is not None else None
 
+    def compute_coded_modified_device(self, d_f0, f0_lengths, d_coded_sp, number_of_dimensions, d_coded_ap, d_spectral_ratio, out_lengths, d_out,
+                                      rng_pos=None):
+        """wc_synthesis_compute_coded_modified_device: compute_coded_device with a spectral ratio per frame, packed like d_f0
+        (0 = that frame as it is; None = compute_coded_device)"""
+        n = len(f0_lengths)
+        arr, arg = _rng_arg(rng_pos, n)
+        _check(lib().wc_synthesis_compute_coded_modified_device(self._h, n, _ptr(d_f0), _ints(f0_lengths), _ptr(d_coded_sp), int(number_of_dimensions),
+                                                                _ptr(d_coded_ap), None if d_spectral_ratio is None else _ptr(d_spectral_ratio),
+                                                                _ints(out_lengths), _ptr(d_out), arg))
+        return list(arr) if arr is not None else None
+
     def _coded_args(self, f0, csp, cap, what):
         from .codec import number_of_aperiodicities
         f, csp, cap = _c(f0), _c(csp), _c(cap)

@@ -19,6 +19,8 @@ CODEC_SIGNATURES = {
     "wc_code_aperiodicity_device": (C.c_int, [C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p]),
     "wc_decode_aperiodicity_device": (C.c_int, [C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p]),
     "wc_decode_features_device": (C.c_int, [C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "wc_decode_features_modified_device": (C.c_int, [C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p]),
     "wc_code_features_device": (C.c_int, [C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
@@ -94,6 +96,14 @@ def decode_features_device(fs, fft_size, n_frames, number_of_dimensions, d_coded
     """both coded rows of n_frames frames -> spectrogram and aperiodicity rows (fft_size/2+1 each), one pass on the device"""
     _check(_L().wc_decode_features_device(int(fs), int(fft_size), int(n_frames), int(number_of_dimensions), _ptr(d_coded_sp),
                                           _ptr(d_coded_ap), _ptr(d_sp), _ptr(d_ap)))
+
+
+def decode_features_modified_device(fs, fft_size, n_frames, number_of_dimensions, d_coded_sp, d_coded_ap, d_spectral_ratio, d_sp, d_ap):
+    """decode_features_device with the spectral rows stretched frame by frame (io.modify_parameters_frames_device's rules for
+    d_spectral_ratio, one double per frame); None: decode_features_device"""
+    _check(_L().wc_decode_features_modified_device(int(fs), int(fft_size), int(n_frames), int(number_of_dimensions), _ptr(d_coded_sp),
+                                                   _ptr(d_coded_ap), None if d_spectral_ratio is None else _ptr(d_spectral_ratio),
+                                                   _ptr(d_sp), _ptr(d_ap)))
 
 
 def code_features_device(fs, fft_size, n_frames, number_of_dimensions, d_sp, d_ap, d_coded_sp, d_coded_ap):

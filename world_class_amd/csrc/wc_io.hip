@@ -15,6 +15,7 @@
 #include "../../include/world_class_io.h"
 #include "wc_device.hpp"
 #include "wc_internal.hpp"
+#include "wc_stages.hpp"
 
 using namespace wc;
 
@@ -201,14 +202,29 @@ __global__ void double_to_pcm16_kernel(const double *__restrict__ y, long long n
 __global__ void scale_f0_kernel(double *__restrict__ f0, long long n, double s) {
 	for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) f0[i] *= s;
 }
+__global__ void scale_f0_frames_kernel(double *__restrict__ f0, long long n, const double *__restrict__ s) {
+	for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) f0[i] *= s[i];
+}
 
 // One workgroup per frame: the row's logarithm goes to LDS, every thread interpolates its bins (reference interp1,
 // src/world_matlabfunctions.cpp:157-182, with histc's clamp(#{x[j] <= xi}, 1, n - 1) and linear extrapolation).
+// PER_FRAME: the frame's own ratio out of `ratios` (wc_modify_parameters_frames_device) instead of the call's; 0 leaves the row,
+// a value the scalar call's host check or the fill below could not take (negative, NaN, infinite, cut < 1) makes the row NaN.
 constexpr int MOD_MAX_BINS = 4096 / 2 + 1;
-__global__ __launch_bounds__(256) void stretch_kernel(double *__restrict__ sp, int fs, int fft_size, double ratio) {
+template <bool PER_FRAME>
+__global__ __launch_bounds__(256) void stretch_kernel(double *__restrict__ sp, int fs, int fft_size, double ratio,
+													  const double *__restrict__ ratios) {
 	__shared__ double lg[MOD_MAX_BINS];
 	const int bins = fft_size / 2 + 1;
 	double *__restrict__ row = sp + (long long)blockIdx.x * bins;
+	if (PER_FRAME) {
+		ratio = ratios[blockIdx.x];
+		if (ratio == 0.0) return;
+		if (!wc::frame_ratio_valid(ratio, fft_size)) {
+			for (int j = threadIdx.x; j < bins; j += 256) row[j] = __builtin_nan("");
+			return;
+		}
+	}
 	for (int j = threadIdx.x; j < bins; j += 256) lg[j] = log(row[j]);
 	__syncthreads();
 	auto axis1 = [&](int j) { return ratio * j / fft_size * fs; };  // reference test/test.cpp:222
@@ -235,6 +251,19 @@ __global__ __launch_bounds__(256) void stretch_kernel(double *__restrict__ sp, i
 }
 
 }  // namespace
+
+int wc::modify_frames_enqueue(hipStream_t s, int fs, int fft_size, long long n_frames, double *d_f0, double *d_sp, const double *d_f0_scale,
+							  const double *d_spectral_ratio) {
+	if (n_frames == 0) return WC_OK;
+	if (d_f0 && d_f0_scale) {
+		const unsigned blocks = static_cast<unsigned>(std::min<long long>((n_frames + 255) / 256, 65536));
+		hipLaunchKernelGGL(scale_f0_frames_kernel, dim3(blocks), dim3(256), 0, s, d_f0, n_frames, d_f0_scale);
+	}
+	if (d_sp && d_spectral_ratio)
+		hipLaunchKernelGGL(stretch_kernel<true>, dim3(static_cast<unsigned>(n_frames)), dim3(256), 0, s, d_sp, fs, fft_size, 0.0, d_spectral_ratio);
+	WC_HIP(hipGetLastError());
+	return WC_OK;
+}
 
 extern "C" {
 
@@ -419,9 +448,20 @@ int wc_modify_parameters_device(int fs, int fft_size, long long n_frames, double
 		hipLaunchKernelGGL(scale_f0_kernel, dim3(blocks), dim3(256), 0, dev->active(), d_f0, n_frames, f0_scale);
 	}
 	if (d_sp && spectral_ratio != 0.0)
-		hipLaunchKernelGGL(stretch_kernel, dim3(static_cast<unsigned>(n_frames)), dim3(256), 0, dev->active(), d_sp, fs, fft_size, spectral_ratio);
+		hipLaunchKernelGGL(stretch_kernel<false>, dim3(static_cast<unsigned>(n_frames)), dim3(256), 0, dev->active(), d_sp, fs, fft_size, spectral_ratio,
+						   (const double *)nullptr);
 	WC_HIP(hipGetLastError());
 	return WC_OK;
+}
+
+int wc_modify_parameters_frames_device(int fs, int fft_size, long long n_frames, double *d_f0, double *d_sp, const double *d_f0_scale,
+									   const double *d_spectral_ratio) {
+	if (fs <= 0 || fft_size < 2 || fft_size / 2 + 1 > MOD_MAX_BINS || n_frames < 0 || n_frames > 0xffffffffll)
+		return fail(WC_ERR_INVALID, "modify_parameters_frames: bad argument (fft_size <= 4096, 0 <= n_frames < 2^32)");
+	Device *dev = current_device();
+	if (!dev) return WC_ERR_DEVICE;
+	DeviceLock lock(dev);
+	return modify_frames_enqueue(dev->active(), fs, fft_size, n_frames, d_f0, d_sp, d_f0_scale, d_spectral_ratio);
 }
 
 }  // extern "C"

@@ -61,9 +61,20 @@ void codec_decode_sp_plan(int fs, int fft_size, int nd, std::vector<int> &k, std
 // least one aperiodicity band)
 const char *decode_features_check(int fs, int fft_size, int nd);
 // Both coded rows of n_frames frames -> rows of fft_size/2+1 doubles (arguments already checked).  fft_size 2048: the one-wavefront
-// kernel, enqueued on s; other sizes: the codec's workgroup-per-frame kernels (wc_decode_*_device) on dev's active stream.
+// kernel, enqueued on s; other sizes: the codec's workgroup-per-frame kernels (wc_decode_*_device) on dev's active stream (s is that
+// stream).  d_spectral_ratio (per frame, or nullptr): the rows of d_sp stretched as by modify_frames_enqueue -- inside the
+// one-wavefront kernel at fft_size 2048, by that call behind the decoders at the other sizes.
 int decode_features_enqueue(Device *dev, hipStream_t s, int fs, int fft_size, long long n_frames, int nd, const double *d_coded_sp,
-							const double *d_coded_ap, double *d_sp, double *d_ap);
+							const double *d_coded_ap, const double *d_spectral_ratio, double *d_sp, double *d_ap);
+
+// Per-frame parameter modification (wc_io.hip; arguments already checked): f0[i] *= d_f0_scale[i], row i of d_sp stretched by
+// d_spectral_ratio[i]; any pointer may be nullptr
+int modify_frames_enqueue(hipStream_t s, int fs, int fft_size, long long n_frames, double *d_f0, double *d_sp, const double *d_f0_scale,
+						  const double *d_spectral_ratio);
+// what a frame's spectral ratio must be to stretch its row (0 = leave it is tested before): finite and cut = int(fft_size / 2 * ratio) >= 1
+__host__ __device__ inline bool frame_ratio_valid(double ratio, int fft_size) {
+	return ratio >= 2.0 / fft_size && ratio <= 1.7976931348623157e308;
+}
 
 // Feature coding (wc_codec.hip, wc_code_features.hip)
 // GetParametersForCoding (reference src/codec.cpp:125-142): the interp1 plan (k, s) from bins 0 .. fft_size/2 (in mel) onto the

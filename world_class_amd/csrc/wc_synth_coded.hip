@@ -1,7 +1,8 @@
-// Feature decoding for Synthesis from coded features (include/world_class_codec.h: wc_decode_features_device; world_class_c.h:
-// wc_synthesis_compute_coded_device; world_class_stream.h: wc_synth_stream_push_coded_device).
+// Feature decoding for Synthesis from coded features (include/world_class_codec.h: wc_decode_features_device,
+// wc_decode_features_modified_device; world_class_c.h: wc_synthesis_compute_coded_device, wc_synthesis_compute_coded_modified_device;
+// world_class_stream.h: wc_synth_stream_push_coded_device).
 //
-//   decode_features_wave_kernel   one 64-lane wavefront per frame at fft_size 2048, both rows of the frame in one pass:
+//   decode_features_wave_kernel<MOD>   one 64-lane wavefront per frame at fft_size 2048, both rows of the frame in one pass:
 //     spectral envelope (reference src/codec.cpp:63-85, :298-325): weights -> IDCTForCodec as a BACKWARD c2c transform of
 //       1024 points held in registers (wf_fft1024_dit, wc_wavefft.hpp; pruned first stage when nd <= 256) -> the even/odd
 //       interleave onto the mel axis in LDS -> interp1 onto the linear axis -> exp
@@ -13,8 +14,10 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstdlib>
 #include <map>
 #include <mutex>
+#include <string>
 #include <vector>
 
 #include "../../include/world_class_c.h"
@@ -35,9 +38,15 @@ struct DecPlan {
 	const double2 *w;    // 1024 IDCT weights
 };
 
+// MOD: the frame's row of sp stretched by rat[frame] (wc_decode_features_modified_device), the arithmetic of stretch_kernel
+// (wc_io.hip) on the log envelope the mel row holds before the exp: the interpolation from the mel axis and the one along the
+// stretched axis are both piecewise linear, so a bin takes the mel row's value at the two ends of its segment, interpolates and
+// takes the one exp.  ratio 0: the unmodified expression; a ratio stretch_kernel<true> would refuse: NaN.
+template <bool MOD>
 __global__ __launch_bounds__(64) void decode_features_wave_kernel(const double *__restrict__ csp, const double *__restrict__ cap,
 																  double *__restrict__ sp, double *__restrict__ ap, int nd, int n_ap,
-																  int fs, DecPlan p, const double2 *__restrict__ tw) {
+																  int fs, DecPlan p, const double2 *__restrict__ tw,
+																  const double *__restrict__ rat) {
 	constexpr int MD = 1024, BINS = MD + 1, FFT = 2 * MD;
 	__shared__ double L[kWfLds];  // the transform's exchange buffer, then the mel-axis row mel[0 .. MD + 1]
 	__shared__ double T2[kWfT2Lds];  // the second stage's twiddles: out of the registers, which then leave room for 3 waves per SIMD
@@ -80,10 +89,35 @@ __global__ __launch_bounds__(64) void decode_features_wave_kernel(const double *
 		}
 		wf_fence();
 		double *__restrict__ row = sp + f * BINS;
-		for (int j = lane; j < BINS; j += 64) {
-			const int k = p.k[j];
-			const double v = L[k - 1] + p.s[j] * (L[k] - L[k - 1]);
-			row[j] = exp(v / MD);
+		const double ratio = MOD ? rat[f] : 0.0;
+		if (!MOD || ratio == 0.0) {
+			for (int j = lane; j < BINS; j += 64) {
+				const int k = p.k[j];
+				const double v = L[k - 1] + p.s[j] * (L[k] - L[k - 1]);
+				row[j] = exp(v / MD);
+			}
+		} else if (!frame_ratio_valid(ratio, FFT)) {
+			for (int j = lane; j < BINS; j += 64) row[j] = __builtin_nan("");
+		} else {
+			auto axis1 = [&](int j) { return ratio * j / FFT * fs; };  // reference test/test.cpp:222
+			auto mel = [&](int b) {  // MD x the unstretched log envelope at bin b
+				const int k = p.k[b];
+				return L[k - 1] + p.s[b] * (L[k] - L[k - 1]);
+			};
+			const int cut = static_cast<int>(FFT / 2.0 * ratio);  // >= 1 for a valid ratio
+			for (int j = lane; j < BINS; j += 64) {
+				const int i = (ratio < 1.0 && j >= cut) ? cut - 1 : j;  // bins from `cut` upward repeat bin cut - 1 (reference :236-240)
+				const double xi = static_cast<double>(i) / FFT * fs;
+				int c = static_cast<int>(i / ratio) + 1;
+				c = c < 0 ? 0 : (c > BINS ? BINS : c);
+				while (c < BINS && axis1(c) <= xi) ++c;
+				while (c > 0 && !(axis1(c - 1) <= xi)) --c;
+				const int k = c < 1 ? 1 : (c > BINS - 1 ? BINS - 1 : c);
+				const double x0 = axis1(k - 1), x1 = axis1(k);
+				const double s = (xi - x0) / (x1 - x0);
+				const double a = mel(k - 1) / MD, b = mel(k) / MD;
+				row[j] = exp(a + s * (b - a));
+			}
 		}
 	}
 
@@ -160,33 +194,48 @@ const char *wc::decode_features_check(int fs, int fft_size, int nd) {
 }
 
 int wc::decode_features_enqueue(Device *dev, hipStream_t s, int fs, int fft_size, long long n_frames, int nd, const double *d_coded_sp,
-								const double *d_coded_ap, double *d_sp, double *d_ap) {
+								const double *d_coded_ap, const double *d_spectral_ratio, double *d_sp, double *d_ap) {
 	if (n_frames == 0) return WC_OK;
 	int rc;
+	// WC_DECODE_MOD=route: the stretch as a pass of its own behind the one-wavefront decoder (the measurement of DESIGN.md section 10)
+	static const bool route_mod = [] { const char *e = getenv("WC_DECODE_MOD"); return e && std::string(e) == "route"; }();
 	if (fft_size == 2048) {
 		DecPlan p;
 		if ((rc = wave_plan(dev, fs, &p))) return rc;
-		hipLaunchKernelGGL(decode_features_wave_kernel, dim3((unsigned)n_frames), dim3(64), 0, s, d_coded_sp, d_coded_ap, d_sp, d_ap, nd,
-						   GetNumberOfAperiodicities(fs), fs, p, (const double2 *)dev->twiddle);
+		if (d_spectral_ratio && !route_mod) {
+			hipLaunchKernelGGL(decode_features_wave_kernel<true>, dim3((unsigned)n_frames), dim3(64), 0, s, d_coded_sp, d_coded_ap, d_sp, d_ap, nd,
+							   GetNumberOfAperiodicities(fs), fs, p, (const double2 *)dev->twiddle, d_spectral_ratio);
+			WC_HIP(hipGetLastError());
+			return WC_OK;
+		}
+		hipLaunchKernelGGL(decode_features_wave_kernel<false>, dim3((unsigned)n_frames), dim3(64), 0, s, d_coded_sp, d_coded_ap, d_sp, d_ap, nd,
+						   GetNumberOfAperiodicities(fs), fs, p, (const double2 *)dev->twiddle, (const double *)nullptr);
 		WC_HIP(hipGetLastError());
-		return WC_OK;
+	} else {
+		OnDeviceOf here(dev);  // (the codec's entry points run on the calling thread's device)
+		if ((rc = wc_decode_spectral_envelope_device(fs, fft_size, n_frames, nd, d_coded_sp, d_sp))) return rc;
+		if ((rc = wc_decode_aperiodicity_device(fs, fft_size, n_frames, d_coded_ap, d_ap))) return rc;
 	}
-	OnDeviceOf here(dev);  // (the codec's entry points run on the calling thread's device)
-	if ((rc = wc_decode_spectral_envelope_device(fs, fft_size, n_frames, nd, d_coded_sp, d_sp))) return rc;
-	return wc_decode_aperiodicity_device(fs, fft_size, n_frames, d_coded_ap, d_ap);
+	return d_spectral_ratio ? modify_frames_enqueue(s, fs, fft_size, n_frames, nullptr, d_sp, nullptr, d_spectral_ratio) : WC_OK;
 }
 
 extern "C" {
 
-int wc_decode_features_device(int fs, int fft_size, long long n_frames, int number_of_dimensions, const double *d_coded_sp,
-							  const double *d_coded_ap, double *d_sp, double *d_ap) {
+int wc_decode_features_modified_device(int fs, int fft_size, long long n_frames, int number_of_dimensions, const double *d_coded_sp,
+									   const double *d_coded_ap, const double *d_spectral_ratio, double *d_sp, double *d_ap) {
 	if (const char *why = decode_features_check(fs, fft_size, number_of_dimensions)) return fail(WC_ERR_INVALID, why);
 	if (n_frames < 0 || n_frames > 0xffffffffll) return fail(WC_ERR_INVALID, "decode_features: n_frames out of range");
 	if (n_frames > 0 && (!d_coded_sp || !d_coded_ap || !d_sp || !d_ap)) return fail(WC_ERR_INVALID, "decode_features: null argument");
 	Device *dev = current_device();
 	if (!dev) return WC_ERR_DEVICE;
 	DeviceLock lock(dev);
-	return decode_features_enqueue(dev, dev->active(), fs, fft_size, n_frames, number_of_dimensions, d_coded_sp, d_coded_ap, d_sp, d_ap);
+	return decode_features_enqueue(dev, dev->active(), fs, fft_size, n_frames, number_of_dimensions, d_coded_sp, d_coded_ap, d_spectral_ratio,
+								   d_sp, d_ap);
+}
+
+int wc_decode_features_device(int fs, int fft_size, long long n_frames, int number_of_dimensions, const double *d_coded_sp,
+							  const double *d_coded_ap, double *d_sp, double *d_ap) {
+	return wc_decode_features_modified_device(fs, fft_size, n_frames, number_of_dimensions, d_coded_sp, d_coded_ap, nullptr, d_sp, d_ap);
 }
 
 }  // extern "C"

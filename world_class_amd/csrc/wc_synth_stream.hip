@@ -13,6 +13,7 @@
 //   ss_overlap_kernel    carried partial sums + the new responses in pulse order (the batch's syn_overlap_add_kernel order):
 //                        the committed prefix to the packed output, the rest to the other carry buffer
 #include <algorithm>
+#include <cfloat>
 #include <climits>
 #include <cmath>
 #include <cstring>
@@ -218,6 +219,8 @@ struct SsState {
 	unsigned long long rng_pos = 0;  // noise position of the pending (or next) pulse
 	long long frames = 0, samples = 0;
 	bool closed = false;
+	double mod_f0 = 1.0, mod_ratio = 0.0;  // wc_synth_stream_set_modification: what coded pushes apply to this stream's frames
+	bool neutral() const { return mod_f0 == 1.0 && mod_ratio == 0.0; }
 };
 }  // namespace
 
@@ -231,7 +234,10 @@ struct wc_synth_stream {
 	int parity = 0;
 	DevBuf wf0[2], wsp[2], wap[2], carry[2], work, inc, pulses, resp, meta, owner, aux;
 	DevBuf dsp, dap;  // wc_synth_stream_push_coded_device: the pushed frames' decoded rows (max_frames x n_streams, on first use)
-	HostBuf h_stage;
+	// a coded push with wc_synth_stream_set_modification settings: per-frame spectral ratios | F0 scales (2 x max_frames x n_streams,
+	// staged through h_mod, the coded push's own: the plain push behind it stages its metadata through h_stage) and the scaled F0
+	DevBuf dmod, sf0;
+	HostBuf h_stage, h_mod;
 };
 
 namespace {
@@ -261,6 +267,10 @@ int final_limit(const wc_synth_stream *s, int F) {
 }
 
 int frame_of(const wc_synth_stream *s, int i) { return (int)std::floor(i / (double)s->fs / s->frame_period); }
+
+__global__ void ss_scale_f0_kernel(const double *__restrict__ f0, const double *__restrict__ scale, long long n, double *__restrict__ out) {
+	for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) out[i] = f0[i] * scale[i];
+}
 }  // namespace
 
 extern "C" {
@@ -289,7 +299,7 @@ void wc_synth_stream_destroy(wc_synth_stream *s) {
 	if (!s) return;
 	s->dev->quiesce();
 	for (int k = 0; k < 2; ++k) { s->wf0[k].release(); s->wsp[k].release(); s->wap[k].release(); s->carry[k].release(); }
-	s->dsp.release(); s->dap.release();
+	s->dsp.release(); s->dap.release(); s->dmod.release(); s->sf0.release(); s->h_mod.release();
 	s->work.release(); s->inc.release(); s->pulses.release(); s->resp.release(); s->meta.release(); s->owner.release(); s->aux.release(); s->h_stage.release();
 	wc_synthesis_destroy(s->sy);
 	delete s;
@@ -316,8 +326,20 @@ int wc_synth_stream_set_rng_position(wc_synth_stream *s, int u, unsigned long lo
 long long wc_synth_stream_frames_received(const wc_synth_stream *s, int u) { return (s && u >= 0 && u < s->n_streams) ? s->st[u].frames : -1; }
 long long wc_synth_stream_samples_committed(const wc_synth_stream *s, int u) { return (s && u >= 0 && u < s->n_streams) ? s->st[u].samples : -1; }
 
-int wc_synth_stream_push_device(wc_synth_stream *s, const int *n_frames, const int *flush, const double *d_f0, const double *d_sp,
-								const double *d_ap, double *d_y, int *samples_out) {
+int wc_synth_stream_set_modification(wc_synth_stream *s, int u, double f0_scale, double spectral_ratio) {
+	if (!s || u < 0 || u >= s->n_streams) return fail(WC_ERR_INVALID, "synthesis stream: bad stream index");
+	if (!(f0_scale > 0.0 && f0_scale <= DBL_MAX)) return fail(WC_ERR_INVALID, "synthesis stream: f0_scale must be finite and positive");
+	if (!(spectral_ratio == 0.0 || frame_ratio_valid(spectral_ratio, s->fft_size)))
+		return fail(WC_ERR_INVALID, "synthesis stream: spectral_ratio must be 0 (none) or finite and at least 2 / fft_size");
+	DeviceLock lock(s->dev);
+	s->st[u].mod_f0 = f0_scale;
+	s->st[u].mod_ratio = spectral_ratio;
+	return WC_OK;
+}
+
+// the push on full rows: the body behind wc_synth_stream_push_device and wc_synth_stream_push_coded_device
+static int ss_push_rows(wc_synth_stream *s, const int *n_frames, const int *flush, const double *d_f0, const double *d_sp,
+						const double *d_ap, double *d_y, int *samples_out) {
 	if (!s || !n_frames || !samples_out) return fail(WC_ERR_INVALID, "synthesis stream push: null argument");
 	const int n = s->n_streams, N = s->fft_size, M = N / 2, bins = M + 1;
 	const double fp_ms = s->frame_period * 1000.0;
@@ -625,31 +647,73 @@ int wc_synth_stream_push_device(wc_synth_stream *s, const int *n_frames, const i
 	return WC_OK;
 }
 
+// Full rows are pushed as they are: the settings of wc_synth_stream_set_modification are applied where coded rows are decoded, so a
+// push that gives frames to a stream with a setting is refused rather than synthesised unmodified.
+int wc_synth_stream_push_device(wc_synth_stream *s, const int *n_frames, const int *flush, const double *d_f0, const double *d_sp,
+								const double *d_ap, double *d_y, int *samples_out) {
+	if (!s || !n_frames || !samples_out) return fail(WC_ERR_INVALID, "synthesis stream push: null argument");
+	for (int u = 0; u < s->n_streams; ++u)
+		if (n_frames[u] > 0 && !s->st[u].neutral())
+			return fail(WC_ERR_INVALID, "synthesis stream push: a stream with a modification setting takes coded frames only (wc_synth_stream_push_coded_device)");
+	return ss_push_rows(s, n_frames, flush, d_f0, d_sp, d_ap, d_y, samples_out);
+}
+
 // The pushed frames' coded rows are decoded (wc::decode_features_enqueue) into the handle's rows on the caller's stream, and the push
-// runs on them: the stream state is only touched by wc_synth_stream_push_device, which keeps it unchanged when it fails.
+// runs on them: the stream state is only touched by ss_push_rows, which keeps it unchanged when it fails.  Streams with a setting
+// of wc_synth_stream_set_modification: the settings expanded per frame go up through h_mod, the decoder stretches with them and the
+// push takes f0 * f0_scale out of sf0.
 int wc_synth_stream_push_coded_device(wc_synth_stream *s, const int *n_frames, const int *flush, const double *d_f0,
 									  const double *d_coded_sp, int number_of_dimensions, const double *d_coded_ap, double *d_y,
 									  int *samples_out) {
 	if (!s || !n_frames || !samples_out) return fail(WC_ERR_INVALID, "synthesis stream push: null argument");
 	if (const char *why = decode_features_check(s->fs, s->fft_size, number_of_dimensions)) return fail(WC_ERR_INVALID, why);
 	long long total_in = 0;
+	bool scaled = false, stretched = false;
 	for (int u = 0; u < s->n_streams; ++u) {
 		if (n_frames[u] < 0 || n_frames[u] > s->max_frames) return fail(WC_ERR_INVALID, "synthesis stream push: n_frames out of range");
 		total_in += n_frames[u];
+		if (n_frames[u] > 0) {
+			scaled = scaled || s->st[u].mod_f0 != 1.0;
+			stretched = stretched || s->st[u].mod_ratio != 0.0;
+		}
 	}
 	if (total_in > 0 && (!d_f0 || !d_coded_sp || !d_coded_ap)) return fail(WC_ERR_INVALID, "synthesis stream push: null frame arrays");
 	if (!d_y) return fail(WC_ERR_INVALID, "synthesis stream push: null output");
 	WC_HIP(hipSetDevice(s->dev->id));
 	DeviceLock lock(s->dev);
 	if (total_in > 0) {
-		const size_t rows = sizeof(double) * (size_t)s->max_frames * s->n_streams * (s->fft_size / 2 + 1);
+		const size_t cap = (size_t)s->max_frames * s->n_streams;
+		const size_t rows = sizeof(double) * cap * (s->fft_size / 2 + 1);
+		hipStream_t hs = s->dev->active();
 		int rc;
 		if ((rc = s->dsp.reserve(rows))) return rc;
 		if ((rc = s->dap.reserve(rows))) return rc;
-		if ((rc = decode_features_enqueue(s->dev, s->dev->active(), s->fs, s->fft_size, total_in, number_of_dimensions, d_coded_sp, d_coded_ap,
+		const double *d_ratio = nullptr;
+		if (scaled || stretched) {
+			if ((rc = s->dmod.reserve(sizeof(double) * 2 * cap)) || (rc = s->sf0.reserve(sizeof(double) * cap)) ||
+				(rc = s->h_mod.reserve(sizeof(double) * 2 * cap))) return rc;  // (waits for the staging buffer's earlier upload)
+			double *h_ratio = s->h_mod.as<double>(), *h_scale = h_ratio + total_in;
+			long long o = 0;
+			for (int u = 0; u < s->n_streams; ++u)
+				for (int i = 0; i < n_frames[u]; ++i, ++o) {
+					h_ratio[o] = s->st[u].mod_ratio;
+					h_scale[o] = s->st[u].mod_f0;
+				}
+			WC_HIP(hipMemcpyAsync(s->dmod.p, s->h_mod.p, sizeof(double) * 2 * (size_t)total_in, hipMemcpyHostToDevice, hs));
+			if ((rc = s->h_mod.mark(hs))) return rc;
+			if (stretched) d_ratio = s->dmod.as<double>();
+			if (scaled) {
+				const unsigned blocks = static_cast<unsigned>(std::min<long long>((total_in + 255) / 256, 65536));
+				hipLaunchKernelGGL(ss_scale_f0_kernel, dim3(blocks), dim3(256), 0, hs, d_f0, (const double *)(s->dmod.as<double>() + total_in), total_in,
+								   s->sf0.as<double>());
+				WC_HIP(hipGetLastError());
+				d_f0 = s->sf0.as<double>();
+			}
+		}
+		if ((rc = decode_features_enqueue(s->dev, hs, s->fs, s->fft_size, total_in, number_of_dimensions, d_coded_sp, d_coded_ap, d_ratio,
 										  s->dsp.as<double>(), s->dap.as<double>()))) return rc;
 	}
-	return wc_synth_stream_push_device(s, n_frames, flush, d_f0, s->dsp.as<double>(), s->dap.as<double>(), d_y, samples_out);
+	return ss_push_rows(s, n_frames, flush, d_f0, s->dsp.as<double>(), s->dap.as<double>(), d_y, samples_out);
 }
 
 }  // extern "C"

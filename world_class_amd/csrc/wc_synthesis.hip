@@ -2298,10 +2298,10 @@ int wc_synthesis_compute_device(wc_synthesis *s, int n_utt, const double *d_f0, 
 
 // Synthesis from coded features: the rows are decoded into the handle's dec_sp / dec_ap on the caller's stream, and the batch runs
 // on them as in wc_synthesis_compute_device.  (Decoding on a side stream beside the time base measured no faster: DESIGN.md
-// section 10.)
-int wc_synthesis_compute_coded_device(wc_synthesis *s, int n_utt, const double *d_f0, const int *f0_length, const double *d_coded_sp,
-									  int number_of_dimensions, const double *d_coded_ap, const int *out_length, double *d_out,
-									  uint64_t *rng_pos) {
+// section 10.)  d_spectral_ratio: per frame, packed like d_f0, or NULL (wc_decode_features_modified_device).
+int wc_synthesis_compute_coded_modified_device(wc_synthesis *s, int n_utt, const double *d_f0, const int *f0_length, const double *d_coded_sp,
+											   int number_of_dimensions, const double *d_coded_ap, const double *d_spectral_ratio,
+											   const int *out_length, double *d_out, uint64_t *rng_pos) {
 	if (!s || n_utt <= 0 || !d_f0 || !f0_length || !d_coded_sp || !d_coded_ap || !out_length || !d_out)
 		return fail(WC_ERR_INVALID, "synthesis coded: null argument");
 	if (const char *why = decode_features_check(s->fs, s->fft_size, number_of_dimensions)) return fail(WC_ERR_INVALID, why);
@@ -2319,8 +2319,15 @@ int wc_synthesis_compute_coded_device(wc_synthesis *s, int n_utt, const double *
 	if ((rc = s->dec_ap.reserve(rows))) return rc;
 	double *d_sp = s->dec_sp.as<double>(), *d_ap = s->dec_ap.as<double>();
 	if ((rc = decode_features_enqueue(s->dev, s->dev->active(), s->fs, s->fft_size, frames, number_of_dimensions, d_coded_sp, d_coded_ap,
-									  d_sp, d_ap))) return rc;
+									  d_spectral_ratio, d_sp, d_ap))) return rc;
 	return syn_run_device(s, n_utt, d_f0, f0_length, d_sp, d_ap, out_length, d_out, rng_pos);
+}
+
+int wc_synthesis_compute_coded_device(wc_synthesis *s, int n_utt, const double *d_f0, const int *f0_length, const double *d_coded_sp,
+									  int number_of_dimensions, const double *d_coded_ap, const int *out_length, double *d_out,
+									  uint64_t *rng_pos) {
+	return wc_synthesis_compute_coded_modified_device(s, n_utt, d_f0, f0_length, d_coded_sp, number_of_dimensions, d_coded_ap, nullptr,
+													  out_length, d_out, rng_pos);
 }
 
 int wc_synthesis_compute(wc_synthesis *s, const double *f0, int f0_length, const double *const *spectrogram,

@@ -26,6 +26,7 @@ IO_SIGNATURES = {
     "wc_float_to_double_device": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p]),
     "wc_double_to_pcm16_device": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p]),
     "wc_modify_parameters_device": (C.c_int, [C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_double, C.c_double]),
+    "wc_modify_parameters_frames_device": (C.c_int, [C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _bound = False
@@ -149,3 +150,15 @@ def modify_parameters_device(fs, fft_size, n_frames, d_f0, d_sp, f0_scale=1.0, s
     """reference test/test.cpp:201-243 on device-resident parameters (0 = leave the spectra alone)"""
     _check(_io().wc_modify_parameters_device(int(fs), int(fft_size), int(n_frames), _ptr(d_f0), _ptr(d_sp), float(f0_scale),
                                              float(spectral_ratio)))
+
+
+def _opt(obj):
+    return None if obj is None else _ptr(obj)
+
+
+def modify_parameters_frames_device(fs, fft_size, n_frames, d_f0, d_sp, d_f0_scale=None, d_spectral_ratio=None):
+    """modify_parameters_device with an F0 scale and a spectral ratio per frame (device arrays of n_frames doubles; None = leave
+    it, as for d_f0 / d_sp).  Per frame a ratio of 0 leaves the row, an invalid one (negative, NaN, infinite, below
+    2 / fft_size) makes it NaN."""
+    _check(_io().wc_modify_parameters_frames_device(int(fs), int(fft_size), int(n_frames), _opt(d_f0), _opt(d_sp), _opt(d_f0_scale),
+                                                    _opt(d_spectral_ratio)))

@@ -34,6 +34,7 @@ STREAM_SIGNATURES = {
     "wc_synth_stream_reset": (C.c_int, [_vp, C.c_int]),
     "wc_synth_stream_push_device": (C.c_int, [_vp, _ip, _ip, _vp, _vp, _vp, _vp, _ip]),
     "wc_synth_stream_push_coded_device": (C.c_int, [_vp, _ip, _ip, _vp, _vp, C.c_int, _vp, _vp, _ip]),
+    "wc_synth_stream_set_modification": (C.c_int, [_vp, C.c_int, C.c_double, C.c_double]),
     "wc_synth_stream_rng_position": (C.c_ulonglong, [_vp, C.c_int]),
     "wc_synth_stream_set_rng_position": (C.c_int, [_vp, C.c_int, C.c_ulonglong]),
     "wc_synth_stream_frames_received": (C.c_longlong, [_vp, C.c_int]),
@@ -282,6 +283,11 @@ class StreamSynthesizer:
 
     def reset(self, stream):
         _check(_lib().wc_synth_stream_reset(self._h, stream))
+
+    def set_modification(self, stream, f0_scale=1.0, spectral_ratio=0.0):
+        """pitch and formant shift of the frames that later coded pushes give this stream ((1.0, 0.0) = none, also after reset);
+        push_device takes no frames for a stream with a setting"""
+        _check(_lib().wc_synth_stream_set_modification(self._h, int(stream), float(f0_scale), float(spectral_ratio)))
 
     def rng_position(self, stream):
         return int(_lib().wc_synth_stream_rng_position(self._h, stream))
