@@ -169,6 +169,19 @@ int wc_synthesis_compute_coded_modified_device(wc_synthesis *s, int n_utt, const
                                                const double *d_coded_sp, int number_of_dimensions, const double *d_coded_ap,
                                                const double *d_spectral_ratio, const int *out_length, double *d_out,
                                                uint64_t *rng_pos);
+/* The same with a time map: the source rows are decoded (the unmodified decoder) into the handle's scratch, resampled by
+ * wc_retime_parameters_device (world_class_io.h) -- d_f0 with f0_length[u] source frames per utterance in, frames_out[u] frames out
+ * at d_position, scaled by d_f0_scale and stretched by d_spectral_ratio (one value per OUTPUT frame, either may be NULL) -- into a
+ * second pair of scratch rows and an F0 scratch, and synthesised as above on frames_out[u] frames per utterance, to which
+ * out_length[u] refers: the samples, the noise draws and rng_pos are those of wc_decode_features_device ->
+ * wc_retime_parameters_device -> wc_synthesis_compute_device.  Refused like the coded call and like the retime call, and for a
+ * frames_out[u] below 2; a refused call leaves rng_pos and d_out alone.  The scratch -- (frames in + frames out) x (fft_size/2+1)
+ * doubles twice -- grows on demand and goes with the handle. */
+int wc_synthesis_compute_coded_retimed_device(wc_synthesis *s, int n_utt, const double *d_f0, const int *f0_length,
+                                              const double *d_coded_sp, int number_of_dimensions, const double *d_coded_ap,
+                                              const int *frames_out, const double *d_position, const double *d_f0_scale,
+                                              const double *d_spectral_ratio, const int *out_length, double *d_out,
+                                              uint64_t *rng_pos);
 /* The same from host arrays: f0[u] (f0_length[u] doubles), coded_sp[u] (f0_length[u] x number_of_dimensions), coded_ap[u]
  * (f0_length[u] x GetNumberOfAperiodicities(fs)) -- what wc_pipeline_run_batch_host_coded returns -- gathered into page-locked
  * staging and sent up in one copy; y[u]: out_length[u] doubles, or int16 quantised like the reference's wavwrite when

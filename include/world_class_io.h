@@ -73,6 +73,28 @@ int wc_modify_parameters_device(int fs, int fft_size, long long n_frames, double
 int wc_modify_parameters_frames_device(int fs, int fft_size, long long n_frames, double *d_f0, double *d_sp,
 									   const double *d_f0_scale, const double *d_spectral_ratio);
 
+/* ---- time-scale modification ----------------------------------------------------------------------------------- */
+/* The frames of a packed batch resampled along a time map, out of place.  Utterance u has in_length[u] source frames and gets
+ * out_length[u] output frames (host arrays; the device arrays are packed in utterance order, source frames for the inputs, output
+ * frames for d_position, d_f0_scale, d_spectral_ratio and the outputs).  d_position[k] is output frame k's place in source
+ * frames, counted from its utterance's first frame; with n source frames:
+ *   not finite: F0 and both rows of that frame are NaN, no other frame is touched;
+ *   else p = min(max(position, 0), n - 1) (the end frames are held), i = floor(p), a = p - i;
+ *   a == 0: source frame i, bit for bit;  a > 0: row = (1 - a) * row[i] + a * row[i + 1] for sp and ap (the interpolation of
+ *   reference src/synthesis.cpp:346-393), F0 = (1 - a) * f0[i] + a * f0[i + 1] between two voiced frames, 0 between two unvoiced
+ *   ones, and next to one voiced frame that frame's F0 while it is the nearer one (a < 0.5 for i, a > 0.5 for i + 1), else 0:
+ *   voiced exactly where Synthesis' interpolated voicing is (:200-204).
+ * Then, per OUTPUT frame, f0 *= d_f0_scale[k] and the row of sp stretched by d_spectral_ratio[k] with the rules and the bits of
+ * wc_modify_parameters_frames_device (0 leaves the row, an invalid ratio makes it NaN); either array may be NULL.  The positions
+ * need not be monotone and out_length has no relation to in_length.  Each of the pairs (d_f0_in, d_f0_out), (d_sp_in, d_sp_out),
+ * (d_ap_in, d_ap_out) may be NULL together: that part is skipped.  Refused (WC_ERR_INVALID, nothing written): fft_size other than
+ * 512 / 1024 / 2048 / 4096, fs <= 0, n_utt < 0, a negative length, out_length[u] > 0 with in_length[u] < 1, more than 2^32 - 1
+ * frames in all on either side, NULL lengths or positions with frames to write, one half of a pair NULL, an output equal to its
+ * input.  out_length[u] == 0 and n_utt == 0 write nothing.  Stream-ordered, enqueue-only. */
+int wc_retime_parameters_device(int fs, int fft_size, int n_utt, const int *in_length, const double *d_f0_in, const double *d_sp_in,
+								const double *d_ap_in, const int *out_length, const double *d_position, const double *d_f0_scale,
+								const double *d_spectral_ratio, double *d_f0_out, double *d_sp_out, double *d_ap_out);
+
 #ifdef __cplusplus
 }
 #endif

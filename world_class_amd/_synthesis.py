@@ -76,6 +76,19 @@ class Synthesis:
                                                                 _ints(out_lengths), _ptr(d_out), arg))
         return list(arr) if arr is not None else None
 
+    def compute_coded_retimed_device(self, d_f0, f0_lengths, d_coded_sp, number_of_dimensions, d_coded_ap, frames_out, d_position, d_f0_scale,
+                                     d_spectral_ratio, out_lengths, d_out, rng_pos=None):
+        """wc_synthesis_compute_coded_retimed_device: compute_coded_device along a time map -- frames_out[u] output frames per
+        utterance at d_position (in source frames, io.time_map builds one), an F0 scale and a spectral ratio per output frame (None
+        = none); out_lengths refer to frames_out"""
+        n = len(f0_lengths)
+        arr, arg = _rng_arg(rng_pos, n)
+        opt = lambda a: None if a is None else _ptr(a)
+        _check(lib().wc_synthesis_compute_coded_retimed_device(self._h, n, _ptr(d_f0), _ints(f0_lengths), _ptr(d_coded_sp), int(number_of_dimensions),
+                                                               _ptr(d_coded_ap), _ints(frames_out), _ptr(d_position), opt(d_f0_scale),
+                                                               opt(d_spectral_ratio), _ints(out_lengths), _ptr(d_out), arg))
+        return list(arr) if arr is not None else None
+
     def _coded_args(self, f0, csp, cap, what):
         from .codec import number_of_aperiodicities
         f, csp, cap = _c(f0), _c(csp), _c(cap)

@@ -1,0 +1,240 @@
+// Time-scale modification (include/world_class_io.h: wc_retime_parameters_device; world_class_c.h:
+// wc_synthesis_compute_coded_retimed_device): the frames of a packed batch resampled along a position per OUTPUT frame.
+//
+//   retime_kernel<STRETCH>   one workgroup per output frame, one launch for the whole batch, out of place.  Output frame k of an
+//     utterance with n source frames sits at p = clamp(pos[k], 0, n - 1) source frames: i = floor(p), a = p - i; a == 0 copies
+//     frame i, a > 0 writes (1 - a) * row[i] + a * row[i + 1] for both rows (the interpolation reference src/synthesis.cpp:346-393
+//     applies between two frames, without its fabs and its aperiodicity clamp) and an F0 that is voiced exactly where Synthesis'
+//     own interpolated voicing (:200-204) is; a position that is not finite makes its own frame NaN.  A gather bound by memory
+//     traffic: up to four rows in, two out, two bins per lane and access (a row of fft_size/2+1 doubles starts on a 16-byte
+//     boundary on every other frame only, so the 16-byte accesses are issued with 8-byte alignment and the row's odd last bin is
+//     peeled); consecutive output frames sit on consecutive workgroups, so the source row two neighbours share comes out of L2.
+//     STRETCH: the interpolated row of sp goes to LDS as its logarithm and is stretched by the frame's ratio with the expressions of
+//     stretch_kernel (wc_io.hip) before its one write.
+//   The workgroup finds its utterance by bisection in the descriptors, which go up through page-locked staging kept per
+//   (device, stream): a call only enqueues.
+#include <hip/hip_runtime.h>
+
+#include <cstdlib>
+#include <map>
+#include <mutex>
+#include <string>
+
+#include "../../include/world_class_c.h"
+#include "../../include/world_class_io.h"
+#include "wc_stages.hpp"
+
+using namespace wc;
+
+namespace {
+
+constexpr int RT_MAX_BINS = 4096 / 2 + 1;
+constexpr int RT_T = 256;
+
+struct RtUtt {
+	long long in_off, out_off;  // first source / output frame in the packed arrays
+	int n;                      // source frames
+};
+
+struct RtArgs {
+	const RtUtt *utts;
+	int n_utt, fs, fft_size;
+	const double *pos, *f0_in, *sp_in, *ap_in, *scale, *ratio;
+	double *f0_out, *sp_out, *ap_out;
+};
+
+typedef double d2u __attribute__((ext_vector_type(2), aligned(8)));  // two bins of a row: 16 bytes at the row's 8-byte alignment
+
+// the two source bins b, b + 1 of the frame: row ri, or (1 - a) * ri + a * rj (two products and one sum, each rounded)
+__device__ __forceinline__ d2u rt_pair(const double *__restrict__ ri, const double *__restrict__ rj, double w0, double a, int b) {
+	d2u x = *reinterpret_cast<const d2u *>(ri + b);
+	if (a > 0.0) {
+		const d2u y = *reinterpret_cast<const d2u *>(rj + b);
+		x = w0 * x + a * y;
+	}
+	return x;
+}
+__device__ __forceinline__ double rt_one(const double *__restrict__ ri, const double *__restrict__ rj, double w0, double a, int b) {
+	return a > 0.0 ? w0 * ri[b] + a * rj[b] : ri[b];
+}
+
+__device__ __forceinline__ void rt_row(const double *__restrict__ ri, const double *__restrict__ rj, double w0, double a,
+									   double *__restrict__ out, int bins, int tid) {
+	for (int t = tid; t < bins / 2; t += RT_T) *reinterpret_cast<d2u *>(out + 2 * t) = rt_pair(ri, rj, w0, a, 2 * t);
+	if (tid == 0) out[bins - 1] = rt_one(ri, rj, w0, a, bins - 1);
+}
+__device__ __forceinline__ void rt_nan_row(double *__restrict__ out, int bins, int tid) {
+	for (int b = tid; b < bins; b += RT_T) out[b] = __builtin_nan("");
+}
+
+template <bool STRETCH>
+__global__ __launch_bounds__(RT_T) void retime_kernel(RtArgs A) {
+	const int tid = threadIdx.x;
+	const long long g = blockIdx.x;
+	int lo = 0, hi = A.n_utt;  // the last utterance that starts at or before g (empty ones in front of it share its offset)
+	while (hi - lo > 1) {
+		const int mid = (lo + hi) >> 1;
+		if (A.utts[mid].out_off <= g) lo = mid;
+		else hi = mid;
+	}
+	const RtUtt u = A.utts[lo];
+	const int bins = A.fft_size / 2 + 1;
+	const double pos = A.pos[g];
+	const bool finite = pos >= -1.7976931348623157e308 && pos <= 1.7976931348623157e308;
+	double p = pos < 0.0 ? 0.0 : pos;
+	p = p > u.n - 1 ? u.n - 1 : p;
+	const int i = finite ? static_cast<int>(floor(p)) : 0;
+	const double a = finite ? p - i : 0.0;
+	const int j = a > 0.0 ? i + 1 : i;  // (a > 0 implies p < n - 1: j stays inside the utterance)
+	const double w0 = 1.0 - a;
+
+	if (A.f0_out && tid == 0) {
+		double v = __builtin_nan("");
+		if (finite) {
+			const double fi = A.f0_in[u.in_off + i], fj = A.f0_in[u.in_off + j];
+			const bool vi = fi != 0.0, vj = fj != 0.0;
+			if (!(a > 0.0)) v = fi;
+			else if (vi && vj) v = w0 * fi + a * fj;
+			else if (vi) v = a < 0.5 ? fi : 0.0;
+			else if (vj) v = a > 0.5 ? fj : 0.0;
+			else v = 0.0;
+		}
+		if (A.scale) v *= A.scale[g];
+		A.f0_out[g] = v;
+	}
+	if (A.ap_out) {
+		double *__restrict__ out = A.ap_out + g * bins;
+		if (!finite) rt_nan_row(out, bins, tid);
+		else rt_row(A.ap_in + (u.in_off + i) * bins, A.ap_in + (u.in_off + j) * bins, w0, a, out, bins, tid);
+	}
+	if (!A.sp_out) return;
+	double *__restrict__ out = A.sp_out + g * bins;
+	const double *__restrict__ ri = A.sp_in + (u.in_off + i) * bins, *__restrict__ rj = A.sp_in + (u.in_off + j) * bins;
+	const double ratio = STRETCH ? A.ratio[g] : 0.0;
+	if (!finite || (STRETCH && ratio != 0.0 && !frame_ratio_valid(ratio, A.fft_size))) {
+		rt_nan_row(out, bins, tid);
+		return;
+	}
+	if (!STRETCH || ratio == 0.0) {
+		rt_row(ri, rj, w0, a, out, bins, tid);
+		return;
+	}
+	if constexpr (STRETCH) {
+		__shared__ double lg[RT_MAX_BINS];
+		__shared__ double fill;
+		for (int t = tid; t < bins / 2; t += RT_T) {
+			const d2u x = rt_pair(ri, rj, w0, a, 2 * t);
+			lg[2 * t] = log(x.x);
+			lg[2 * t + 1] = log(x.y);
+		}
+		if (tid == 0) lg[bins - 1] = log(rt_one(ri, rj, w0, a, bins - 1));
+		__syncthreads();
+		// stretch_kernel's expressions (wc_io.hip; reference test/test.cpp:222-240, interp1 with histc's clamp)
+		const int fft_size = A.fft_size, fs = A.fs;
+		auto axis1 = [&](int q) { return ratio * q / fft_size * fs; };
+		const int cut = static_cast<int>(fft_size / 2.0 * ratio);  // >= 1 for a valid ratio
+		const int top = ratio < 1.0 ? cut : bins;                 // bins from `cut` upward repeat bin cut - 1
+		for (int b = tid; b < top; b += RT_T) {
+			const double xi = static_cast<double>(b) / fft_size * fs;
+			int c = static_cast<int>(b / ratio) + 1;
+			c = c < 0 ? 0 : (c > bins ? bins : c);
+			while (c < bins && axis1(c) <= xi) ++c;
+			while (c > 0 && !(axis1(c - 1) <= xi)) --c;
+			const int k = c < 1 ? 1 : (c > bins - 1 ? bins - 1 : c);
+			const double x0 = axis1(k - 1), x1 = axis1(k);
+			const double s = (xi - x0) / (x1 - x0);
+			const double v = exp(lg[k - 1] + s * (lg[k] - lg[k - 1]));
+			out[b] = v;
+			if (b == top - 1) fill = v;
+		}
+		if (top < bins) {
+			__syncthreads();
+			const double f = fill;
+			for (int b = top + tid; b < bins; b += RT_T) out[b] = f;
+		}
+	}
+}
+
+// descriptor staging per (device, stream): calls on one stream are ordered behind each other, calls on different streams never
+// share a buffer.  A few dozen bytes per utterance, kept for the life of the process like the decoder's plans.
+std::mutex g_stage_mu;
+std::map<std::pair<int, hipStream_t>, Staging *> g_stage;
+
+}  // namespace
+
+const char *wc::retime_check(int fs, int fft_size, int n_utt, const int *in_length, const int *out_length, long long *total_out) {
+	if (!(fft_size == 512 || fft_size == 1024 || fft_size == 2048 || fft_size == 4096)) return "retime: fft_size must be 512, 1024, 2048 or 4096";
+	if (fs <= 0) return "retime: fs must be positive";
+	if (n_utt < 0) return "retime: negative n_utt";
+	if (n_utt > 0 && (!in_length || !out_length)) return "retime: null length array";
+	long long ti = 0, to = 0;
+	for (int u = 0; u < n_utt; ++u) {
+		if (in_length[u] < 0 || out_length[u] < 0) return "retime: negative length";
+		if (out_length[u] > 0 && in_length[u] < 1) return "retime: output frames of an utterance without source frames";
+		ti += in_length[u];
+		to += out_length[u];
+	}
+	if (ti > 0xffffffffll || to > 0xffffffffll) return "retime: more than 2^32 - 1 frames";
+	*total_out = to;
+	return nullptr;
+}
+
+int wc::retime_enqueue(Device *dev, hipStream_t s, int fs, int fft_size, int n_utt, const int *in_length, const double *d_f0_in,
+					   const double *d_sp_in, const double *d_ap_in, const int *out_length, const double *d_position,
+					   const double *d_f0_scale, const double *d_spectral_ratio, double *d_f0_out, double *d_sp_out, double *d_ap_out,
+					   long long total_out) {
+	if (total_out == 0 || (!d_f0_out && !d_sp_out && !d_ap_out)) return WC_OK;
+	// WC_RETIME_MOD=route: scale and stretch as wc_modify_parameters_frames_device behind the plain kernel (the measurement of
+	// DESIGN.md section 10)
+	static const bool route_mod = [] { const char *e = getenv("WC_RETIME_MOD"); return e && std::string(e) == "route"; }();
+	Staging *st;
+	{
+		std::lock_guard<std::mutex> g(g_stage_mu);
+		Staging *&slot = g_stage[{dev->id, s}];
+		if (!slot) slot = new Staging();
+		st = slot;
+	}
+	int rc;
+	const size_t bytes = sizeof(RtUtt) * (size_t)n_utt;
+	if ((rc = st->h.reserve(bytes))) return rc;
+	if ((rc = st->d.reserve(bytes))) return rc;
+	RtUtt *h = st->h.as<RtUtt>();
+	long long fi = 0, fo = 0;
+	for (int u = 0; u < n_utt; ++u) {
+		h[u].in_off = fi; h[u].out_off = fo; h[u].n = in_length[u];
+		fi += in_length[u];
+		fo += out_length[u];
+	}
+	WC_HIP(hipMemcpyAsync(st->d.p, h, bytes, hipMemcpyHostToDevice, s));
+	if ((rc = st->h.mark(s))) return rc;
+	RtArgs a;
+	a.utts = st->d.as<RtUtt>();
+	a.n_utt = n_utt; a.fs = fs; a.fft_size = fft_size;
+	a.pos = d_position; a.f0_in = d_f0_in; a.sp_in = d_sp_in; a.ap_in = d_ap_in;
+	a.f0_out = d_f0_out; a.sp_out = d_sp_out; a.ap_out = d_ap_out;
+	a.scale = route_mod ? nullptr : d_f0_scale;
+	a.ratio = route_mod ? nullptr : d_spectral_ratio;
+	if (a.ratio && d_sp_out) hipLaunchKernelGGL(retime_kernel<true>, dim3((unsigned)total_out), dim3(RT_T), 0, s, a);
+	else hipLaunchKernelGGL(retime_kernel<false>, dim3((unsigned)total_out), dim3(RT_T), 0, s, a);
+	WC_HIP(hipGetLastError());
+	if (route_mod) return modify_frames_enqueue(s, fs, fft_size, total_out, d_f0_out, d_sp_out, d_f0_scale, d_spectral_ratio);
+	return WC_OK;
+}
+
+extern "C" int wc_retime_parameters_device(int fs, int fft_size, int n_utt, const int *in_length, const double *d_f0_in, const double *d_sp_in,
+										   const double *d_ap_in, const int *out_length, const double *d_position, const double *d_f0_scale,
+										   const double *d_spectral_ratio, double *d_f0_out, double *d_sp_out, double *d_ap_out) {
+	long long total_out = 0;
+	if (const char *why = retime_check(fs, fft_size, n_utt, in_length, out_length, &total_out)) return fail(WC_ERR_INVALID, why);
+	const double *const in[3] = {d_f0_in, d_sp_in, d_ap_in}, *const out[3] = {d_f0_out, d_sp_out, d_ap_out};
+	for (int k = 0; k < 3; ++k) {
+		if (!in[k] != !out[k]) return fail(WC_ERR_INVALID, "retime: an input without its output (or the reverse)");
+		if (in[k] && in[k] == out[k]) return fail(WC_ERR_INVALID, "retime: in place is not supported (the output must not be the input)");
+	}
+	if (total_out > 0 && !d_position) return fail(WC_ERR_INVALID, "retime: null position array");
+	Device *dev = current_device();
+	if (!dev) return WC_ERR_DEVICE;
+	DeviceLock lock(dev);
+	return retime_enqueue(dev, dev->active(), fs, fft_size, n_utt, in_length, d_f0_in, d_sp_in, d_ap_in, out_length, d_position, d_f0_scale,
+						  d_spectral_ratio, d_f0_out, d_sp_out, d_ap_out, total_out);
+}

@@ -76,6 +76,14 @@ __host__ __device__ inline bool frame_ratio_valid(double ratio, int fft_size) {
 	return ratio >= 2.0 / fft_size && ratio <= 1.7976931348623157e308;
 }
 
+// Time-scale modification (wc_retime.hip).  retime_check: nullptr if wc_retime_parameters_device takes the sizes and the lengths, else
+// why not; the output frames of the batch come back.  retime_enqueue: the arguments already checked, the descriptors staged and the
+// kernel enqueued on s.
+const char *retime_check(int fs, int fft_size, int n_utt, const int *in_length, const int *out_length, long long *total_out);
+int retime_enqueue(Device *dev, hipStream_t s, int fs, int fft_size, int n_utt, const int *in_length, const double *d_f0_in,
+				   const double *d_sp_in, const double *d_ap_in, const int *out_length, const double *d_position, const double *d_f0_scale,
+				   const double *d_spectral_ratio, double *d_f0_out, double *d_sp_out, double *d_ap_out, long long total_out);
+
 // Feature coding (wc_codec.hip, wc_code_features.hip)
 // GetParametersForCoding (reference src/codec.cpp:125-142): the interp1 plan (k, s) from bins 0 .. fft_size/2 (in mel) onto the
 // fft_size/2 points of the mel axis and the DCT weights

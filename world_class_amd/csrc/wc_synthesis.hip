@@ -1845,6 +1845,7 @@ struct wc_synthesis {
 	bool serial_timebase;  // WC_SYN_TIMEBASE=serial: the one-wavefront sequential accumulation instead of the exact parallel one
 	HostBuf h_stage, h_rows;
 	DevBuf dec_sp, dec_ap;  // wc_synthesis_compute_coded_device: the decoded rows
+	DevBuf rt_f0, rt_sp, rt_ap;  // wc_synthesis_compute_coded_retimed_device: the retimed contour and rows
 	long long total_out = 0, cap_total = 0;  // of the most recent syn_prepare
 	int n_utt = 0, max_out = 0;
 };
@@ -2282,6 +2283,7 @@ void wc_synthesis_destroy(wc_synthesis *s) {
 	s->dc_remover.release(); s->utts.release(); s->meta.release(); s->pulses.release(); s->incs.release(); s->phase.release(); s->tile_cnt.release(); s->phase_seg.release(); s->resp.release(); s->pulse_utt.release();
 	s->d_f0.release(); s->d_sp.release(); s->d_ap.release(); s->d_out.release(); s->h_stage.release(); s->h_rows.release();
 	s->dec_sp.release(); s->dec_ap.release();
+	s->rt_f0.release(); s->rt_sp.release(); s->rt_ap.release();
 	delete s;
 }
 
@@ -2328,6 +2330,41 @@ int wc_synthesis_compute_coded_device(wc_synthesis *s, int n_utt, const double *
 									  uint64_t *rng_pos) {
 	return wc_synthesis_compute_coded_modified_device(s, n_utt, d_f0, f0_length, d_coded_sp, number_of_dimensions, d_coded_ap, nullptr,
 													  out_length, d_out, rng_pos);
+}
+
+// Synthesis from coded features along a time map: decode -> retime (wc_retime.hip) into a second pair of scratch rows -> the batch
+int wc_synthesis_compute_coded_retimed_device(wc_synthesis *s, int n_utt, const double *d_f0, const int *f0_length, const double *d_coded_sp,
+											  int number_of_dimensions, const double *d_coded_ap, const int *frames_out,
+											  const double *d_position, const double *d_f0_scale, const double *d_spectral_ratio,
+											  const int *out_length, double *d_out, uint64_t *rng_pos) {
+	if (!s || n_utt <= 0 || !d_f0 || !f0_length || !d_coded_sp || !d_coded_ap || !frames_out || !d_position || !out_length || !d_out)
+		return fail(WC_ERR_INVALID, "synthesis coded retimed: null argument");
+	if (const char *why = decode_features_check(s->fs, s->fft_size, number_of_dimensions)) return fail(WC_ERR_INVALID, why);
+	for (int u = 0; u < n_utt; ++u) {  // (checked here too: a refused call enqueues nothing)
+		if (f0_length[u] < 2 || frames_out[u] < 2)
+			return fail(WC_ERR_INVALID, "synthesis: f0_length and frames_out must be at least 2 (reference src/synthesis.cpp:241-242)");
+		if (out_length[u] < 0) return fail(WC_ERR_INVALID, "synthesis: negative out_length");
+	}
+	long long frames = 0, total = 0;
+	for (int u = 0; u < n_utt; ++u) frames += f0_length[u];
+	if (const char *why = retime_check(s->fs, s->fft_size, n_utt, f0_length, frames_out, &total)) return fail(WC_ERR_INVALID, why);
+	WC_HIP(hipSetDevice(s->dev->id));
+	DeviceLock lock(s->dev);
+	const size_t row = sizeof(double) * (size_t)(s->fft_size / 2 + 1);
+	int rc;
+	if ((rc = s->dec_sp.reserve(row * frames))) return rc;
+	if ((rc = s->dec_ap.reserve(row * frames))) return rc;
+	if ((rc = s->rt_sp.reserve(row * total))) return rc;
+	if ((rc = s->rt_ap.reserve(row * total))) return rc;
+	if ((rc = s->rt_f0.reserve(sizeof(double) * total))) return rc;
+	double *d_sp = s->dec_sp.as<double>(), *d_ap = s->dec_ap.as<double>();
+	double *r_f0 = s->rt_f0.as<double>(), *r_sp = s->rt_sp.as<double>(), *r_ap = s->rt_ap.as<double>();
+	hipStream_t st = s->dev->active();
+	if ((rc = decode_features_enqueue(s->dev, st, s->fs, s->fft_size, frames, number_of_dimensions, d_coded_sp, d_coded_ap, nullptr, d_sp, d_ap)))
+		return rc;
+	if ((rc = retime_enqueue(s->dev, st, s->fs, s->fft_size, n_utt, f0_length, d_f0, d_sp, d_ap, frames_out, d_position, d_f0_scale,
+							 d_spectral_ratio, r_f0, r_sp, r_ap, total))) return rc;
+	return syn_run_device(s, n_utt, r_f0, frames_out, r_sp, r_ap, out_length, d_out, rng_pos);
 }
 
 int wc_synthesis_compute(wc_synthesis *s, const double *f0, int f0_length, const double *const *spectrogram,

@@ -27,6 +27,8 @@ IO_SIGNATURES = {
     "wc_double_to_pcm16_device": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p]),
     "wc_modify_parameters_device": (C.c_int, [C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_double, C.c_double]),
     "wc_modify_parameters_frames_device": (C.c_int, [C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "wc_retime_parameters_device": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int),
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _bound = False
@@ -162,3 +164,52 @@ def modify_parameters_frames_device(fs, fft_size, n_frames, d_f0, d_sp, d_f0_sca
     2 / fft_size) makes it NaN."""
     _check(_io().wc_modify_parameters_frames_device(int(fs), int(fft_size), int(n_frames), _opt(d_f0), _opt(d_sp), _opt(d_f0_scale),
                                                     _opt(d_spectral_ratio)))
+
+
+def retime_parameters_device(fs, fft_size, in_lengths, d_f0_in, d_sp_in, d_ap_in, out_lengths, d_position, d_f0_scale=None,
+                             d_spectral_ratio=None, d_f0_out=None, d_sp_out=None, d_ap_out=None):
+    """wc_retime_parameters_device: the frames of a packed batch resampled along a position per output frame (in source frames,
+    from the utterance's first frame; the end frames are held, a position that is not finite makes its own frame NaN), then F0
+    scaled and sp stretched per OUTPUT frame as by modify_parameters_frames_device.  in_lengths / out_lengths: frames per
+    utterance (host lists); each of the pairs (d_f0_in, d_f0_out), (d_sp_in, d_sp_out), (d_ap_in, d_ap_out) may be None together."""
+    from . import _ints
+    if len(in_lengths) != len(out_lengths):
+        raise ValueError("retime_parameters_device: in_lengths and out_lengths must have one entry per utterance each")
+    _check(_io().wc_retime_parameters_device(int(fs), int(fft_size), len(in_lengths), _ints(in_lengths), _opt(d_f0_in), _opt(d_sp_in),
+                                             _opt(d_ap_in), _ints(out_lengths), _opt(d_position), _opt(d_f0_scale), _opt(d_spectral_ratio),
+                                             _opt(d_f0_out), _opt(d_sp_out), _opt(d_ap_out)))
+
+
+def retime_parameters(f0, sp, ap, position, fs, fft_size, f0_scale=None, spectral_ratio=None):
+    """one utterance, numpy in, numpy out: (f0, sp, ap) at the positions (see retime_parameters_device), through the device call"""
+    from . import DeviceArray
+    f0, sp, ap, position = _c(f0), _c(sp), _c(ap), _c(position)
+    n, m, bins = len(f0), len(position), int(fft_size) // 2 + 1
+    if sp.shape != (n, bins) or ap.shape != (n, bins) or position.ndim != 1:
+        raise ValueError(f"retime_parameters: sp and ap must be ({n}, {bins}), position a vector")
+    per_frame = [None if a is None else np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.float64), (m,))) for a in (f0_scale, spectral_ratio)]
+    held = [DeviceArray.from_host(a) for a in (f0, sp, ap, position)] + [None if a is None else DeviceArray.from_host(a) for a in per_frame]
+    outs = [DeviceArray(m), DeviceArray(m * bins), DeviceArray(m * bins)]
+    try:
+        retime_parameters_device(fs, fft_size, [n], held[0], held[1], held[2], [m], held[3], held[4], held[5], *outs)
+        _check(lib().wc_synchronize())
+        return outs[0].to_host()[:m], outs[1].to_host()[:m * bins].reshape(m, bins), outs[2].to_host()[:m * bins].reshape(m, bins)
+    finally:
+        for a in held + outs:
+            if a is not None:
+                a.free()
+
+
+def time_map(n_frames, speed):
+    """positions for retime_parameters*: `speed` source frames per output frame.  A positive scalar: arange(floor((n_frames - 1) /
+    speed) + 1) * speed (the whole utterance at that speed); an array of one speed per output frame: pos[0] = 0, pos[k] =
+    pos[k - 1] + speed[k - 1].  Host only."""
+    if np.ndim(speed) == 0:
+        speed = float(speed)
+        if not (speed > 0.0 and np.isfinite(speed)) or n_frames < 1:
+            raise ValueError("time_map: speed must be a positive finite number and n_frames at least 1")
+        return np.arange(int(np.floor((n_frames - 1) / speed)) + 1, dtype=np.float64) * speed
+    speed = np.asarray(speed, dtype=np.float64).ravel()
+    pos = np.zeros(len(speed))
+    np.cumsum(speed[:-1], out=pos[1:])
+    return pos
