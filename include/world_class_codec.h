@@ -32,7 +32,9 @@ void CodeSpectralEnvelope(const double *const *spectrogram, int f0_length, int f
 void DecodeSpectralEnvelope(const double *const *coded_spectral_envelope, int f0_length, int fs, int fft_size,
 							int number_of_dimensions, double **spectrogram);
 
-/* device-resident batches; all return 0 or a negative WC_ERR_* code (wc_last_error() has the message) */
+/* device-resident batches; all return 0 or a negative WC_ERR_* code (wc_last_error() has the message).  The two spectral-envelope
+ * calls return with their work complete (one synchronisation of the calling thread's stream at their end); their plan is built
+ * once per (device, fs, fft_size) and kept, as for the calls on both rows below. */
 int wc_code_spectral_envelope_device(int fs, int fft_size, long long n_frames, int number_of_dimensions, const double *d_sp,
 									 double *d_coded);
 int wc_decode_spectral_envelope_device(int fs, int fft_size, long long n_frames, int number_of_dimensions, const double *d_coded,
@@ -42,8 +44,8 @@ int wc_decode_aperiodicity_device(int fs, int fft_size, long long n_frames, cons
 /* Both decoders in one pass, the input of Synthesis from coded features: d_coded_sp (n_frames x number_of_dimensions) and
  * d_coded_ap (n_frames x GetNumberOfAperiodicities(fs)) -> d_sp, d_ap (n_frames x (fft_size/2+1) each).  fft_size 2048: one
  * wavefront per frame with the transform in registers; 512, 1024, 4096: the two kernels above.  fft_size 512..4096,
- * 1 <= number_of_dimensions <= fft_size/2, fs of at least 12 kHz.  Stream-ordered (enqueues only, after the first call at a
- * new fs). */
+ * 1 <= number_of_dimensions <= fft_size/2, fs of at least 12 kHz.  Stream-ordered at every size (enqueues only, after the first call at a
+ * new (fs, fft_size)). */
 int wc_decode_features_device(int fs, int fft_size, long long n_frames, int number_of_dimensions, const double *d_coded_sp,
                               const double *d_coded_ap, double *d_sp, double *d_ap);
 /* The decoder with the demo's formant shift inside (world_class_io.h): wc_decode_features_device followed by

@@ -232,6 +232,11 @@ def _ptr(obj):
     return int(obj)
 
 
+def _opt(obj):
+    """_ptr of an optional array: None stays None (NULL)"""
+    return None if obj is None else _ptr(obj)
+
+
 def _rng_arg(rng_pos, n):
     if rng_pos is None:
         return None, None

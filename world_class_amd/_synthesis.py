@@ -3,7 +3,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import (_c, _check, _handle, _ints, _p, _ptr, _ptr_array, _rng_arg, _row_tables, _rows, lib,
+from . import (_c, _check, _handle, _ints, _opt, _p, _ptr, _ptr_array, _rng_arg, _row_tables, _rows, lib,
                synthesis_out_length)
 
 
@@ -57,37 +57,33 @@ class Synthesis:
                                                 _ptr_array(ys), arg))
         return (ys, list(arr)) if rng_pos is not None else ys
 
-    def compute_coded_device(self, d_f0, f0_lengths, d_coded_sp, number_of_dimensions, d_coded_ap, out_lengths, d_out, rng_pos=None):
-        """wc_synthesis_compute_coded_device: device pointers, coded rows packed like d_f0"""
+    def _coded_device(self, call, d_f0, f0_lengths, d_coded_sp, number_of_dimensions, d_coded_ap, extra, out_lengths, d_out, rng_pos):
+        """the three coded device calls: the same arguments with `extra` between the coded rows and the output"""
         n = len(f0_lengths)
         arr, arg = _rng_arg(rng_pos, n)
-        _check(lib().wc_synthesis_compute_coded_device(self._h, n, _ptr(d_f0), _ints(f0_lengths), _ptr(d_coded_sp), int(number_of_dimensions),
-                                                       _ptr(d_coded_ap), _ints(out_lengths), _ptr(d_out), arg))
+        _check(call(self._h, n, _ptr(d_f0), _ints(f0_lengths), _ptr(d_coded_sp), int(number_of_dimensions), _ptr(d_coded_ap), *extra,
+                    _ints(out_lengths), _ptr(d_out), arg))
         return list(arr) if arr is not None else None
+
+    def compute_coded_device(self, d_f0, f0_lengths, d_coded_sp, number_of_dimensions, d_coded_ap, out_lengths, d_out, rng_pos=None):
+        """wc_synthesis_compute_coded_device: device pointers, coded rows packed like d_f0"""
+        return self._coded_device(lib().wc_synthesis_compute_coded_device, d_f0, f0_lengths, d_coded_sp, number_of_dimensions, d_coded_ap, (),
+                                  out_lengths, d_out, rng_pos)
 
     def compute_coded_modified_device(self, d_f0, f0_lengths, d_coded_sp, number_of_dimensions, d_coded_ap, d_spectral_ratio, out_lengths, d_out,
                                       rng_pos=None):
         """wc_synthesis_compute_coded_modified_device: compute_coded_device with a spectral ratio per frame, packed like d_f0
         (0 = that frame as it is; None = compute_coded_device)"""
-        n = len(f0_lengths)
-        arr, arg = _rng_arg(rng_pos, n)
-        _check(lib().wc_synthesis_compute_coded_modified_device(self._h, n, _ptr(d_f0), _ints(f0_lengths), _ptr(d_coded_sp), int(number_of_dimensions),
-                                                                _ptr(d_coded_ap), None if d_spectral_ratio is None else _ptr(d_spectral_ratio),
-                                                                _ints(out_lengths), _ptr(d_out), arg))
-        return list(arr) if arr is not None else None
+        return self._coded_device(lib().wc_synthesis_compute_coded_modified_device, d_f0, f0_lengths, d_coded_sp, number_of_dimensions, d_coded_ap,
+                                  (_opt(d_spectral_ratio),), out_lengths, d_out, rng_pos)
 
     def compute_coded_retimed_device(self, d_f0, f0_lengths, d_coded_sp, number_of_dimensions, d_coded_ap, frames_out, d_position, d_f0_scale,
                                      d_spectral_ratio, out_lengths, d_out, rng_pos=None):
         """wc_synthesis_compute_coded_retimed_device: compute_coded_device along a time map -- frames_out[u] output frames per
         utterance at d_position (in source frames, io.time_map builds one), an F0 scale and a spectral ratio per output frame (None
         = none); out_lengths refer to frames_out"""
-        n = len(f0_lengths)
-        arr, arg = _rng_arg(rng_pos, n)
-        opt = lambda a: None if a is None else _ptr(a)
-        _check(lib().wc_synthesis_compute_coded_retimed_device(self._h, n, _ptr(d_f0), _ints(f0_lengths), _ptr(d_coded_sp), int(number_of_dimensions),
-                                                               _ptr(d_coded_ap), _ints(frames_out), _ptr(d_position), opt(d_f0_scale),
-                                                               opt(d_spectral_ratio), _ints(out_lengths), _ptr(d_out), arg))
-        return list(arr) if arr is not None else None
+        return self._coded_device(lib().wc_synthesis_compute_coded_retimed_device, d_f0, f0_lengths, d_coded_sp, number_of_dimensions, d_coded_ap,
+                                  (_ints(frames_out), _ptr(d_position), _opt(d_f0_scale), _opt(d_spectral_ratio)), out_lengths, d_out, rng_pos)
 
     def _coded_args(self, f0, csp, cap, what):
         from .codec import number_of_aperiodicities

@@ -3,7 +3,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _check, _ptr, lib
+from . import _check, _opt, _ptr, lib
 
 _dp = C.POINTER(C.c_double)
 _rows_t = C.POINTER(_dp)
@@ -102,13 +102,11 @@ def decode_features_modified_device(fs, fft_size, n_frames, number_of_dimensions
     """decode_features_device with the spectral rows stretched frame by frame (io.modify_parameters_frames_device's rules for
     d_spectral_ratio, one double per frame); None: decode_features_device"""
     _check(_L().wc_decode_features_modified_device(int(fs), int(fft_size), int(n_frames), int(number_of_dimensions), _ptr(d_coded_sp),
-                                                   _ptr(d_coded_ap), None if d_spectral_ratio is None else _ptr(d_spectral_ratio),
-                                                   _ptr(d_sp), _ptr(d_ap)))
+                                                   _ptr(d_coded_ap), _opt(d_spectral_ratio), _ptr(d_sp), _ptr(d_ap)))
 
 
 def code_features_device(fs, fft_size, n_frames, number_of_dimensions, d_sp, d_ap, d_coded_sp, d_coded_ap):
     """spectrogram and aperiodicity rows of n_frames frames -> both coded rows, one pass on the device, enqueue-only;
     d_ap and d_coded_ap both None: the spectral envelope alone"""
     _check(_L().wc_code_features_device(int(fs), int(fft_size), int(n_frames), int(number_of_dimensions), _ptr(d_sp),
-                                        None if d_ap is None else _ptr(d_ap), _ptr(d_coded_sp),
-                                        None if d_coded_ap is None else _ptr(d_coded_ap)))
+                                        _opt(d_ap), _ptr(d_coded_sp), _opt(d_coded_ap)))

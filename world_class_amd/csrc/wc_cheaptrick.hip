@@ -18,6 +18,7 @@
 #include "wc_frames.hpp"
 #include "wc_wavefft.hpp"
 #include "wc_hostcopy.hpp"
+#include "wc_stages.hpp"
 
 namespace wc {
 
@@ -1444,7 +1445,7 @@ wc_cheaptrick *wc_cheaptrick_create(int fs, double q1, double f0_floor, int fft_
 		c->wave = !(impl && std::strcmp(impl, "block") == 0);
 		c->split = impl && std::strcmp(impl, "split") == 0;  // N = 2048 on eight points per lane (ct_wave_split_kernel; A/B)
 	}
-	if (c->fft_size != 512 && c->fft_size != 1024 && c->fft_size != 2048 && c->fft_size != 4096) {
+	if (!fft_size_supported(c->fft_size)) {
 		set_error("cheaptrick: fft_size must be 512, 1024, 2048 or 4096 (fs between 8 kHz and 96 kHz)");
 		delete c;
 		return nullptr;

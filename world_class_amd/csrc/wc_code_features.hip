@@ -12,14 +12,10 @@
 //   coefficients are held to; a coefficient is a sum of fft_size/2 logs times 2 / sqrt(fft_size * fft_size/2)); a bin that is zero, negative or
 //   not finite becomes NaN and with it the whole coded row of its frame, as code_sp_kernel's -inf / NaN does.
 //   fft_size 512 and 1024 take the codec's workgroup-per-frame kernels (wc_codec.hip) on the cached plan.
-//   The plan is built and uploaded once per (device, fs, fft_size) and kept: a call then only enqueues.
+//   The plan is wc::codec_plan's (wc_codec.hip), built and uploaded once per (device, fs, fft_size) and kept: a call then only enqueues.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <map>
-#include <mutex>
-#include <tuple>
-#include <vector>
 
 #include "../../include/world_class_c.h"
 #include "../../include/world_class_codec.h"
@@ -30,21 +26,13 @@ using namespace wc;
 
 namespace {
 
-constexpr double kFrequencyInterval = 3000.0;  // world_constantnumbers.hpp
-
-struct EncPlan {
-	const int *kp;      // fft_size/2 segment indices (1-based): entry (2 q + h) * 64 + lane belongs to waveform[2 (lane + 64 q) + h]
-	const double *sp;   // fft_size/2 fractions, same order
-	const double2 *w;   // fft_size/2 DCT weights
-};
-
 // MD = fft_size / 2 real points: 1024 (wf8_fft512_dit, eight complex points per lane) or 2048 (wf_fft1024_dit, sixteen).
 // SMALL: nd <= MD / 8, the wanted bins sit in the first slot of every group of the paired layout, so the last butterflies and
 // the unpacking of the other slots' outputs are dead code and leave the kernel
 template <int MD, bool SMALL>
 __global__ __launch_bounds__(64) void code_features_wave_kernel(const double *__restrict__ sp, const double *__restrict__ ap,
 																 double *__restrict__ csp, double *__restrict__ cap, int nd, int n_ap,
-																 int fs, EncPlan p, const double2 *__restrict__ tw) {
+																 int fs, CodecPlanArgs p, const double2 *__restrict__ tw) {
 	constexpr int BINS = MD + 1, FFT = 2 * MD, NS = MD / 128, NG = MD / 512;  // slots per lane, groups of four slots
 	__shared__ double L[BINS + 7];  // the row of logarithms, then the transform's exchange buffer
 	static_assert(BINS + 7 >= (MD == 1024 ? kWf8Lds : kWfLds), "exchange buffer");
@@ -81,8 +69,9 @@ __global__ __launch_bounds__(64) void code_features_wave_kernel(const double *__
 	double re[NS], im[NS];
 #pragma unroll
 	for (int q = 0; q < NS; ++q) {
-		const int ke = p.kp[(2 * q) * 64 + lane], ko = p.kp[(2 * q + 1) * 64 + lane];
-		const double se = p.sp[(2 * q) * 64 + lane], so = p.sp[(2 * q + 1) * 64 + lane];
+		// (the plan in the wavefront's order: entry (2 q + h) * 64 + lane belongs to waveform[2 (lane + 64 q) + h])
+		const int ke = p.k[(2 * q) * 64 + lane], ko = p.k[(2 * q + 1) * 64 + lane];
+		const double se = p.s[(2 * q) * 64 + lane], so = p.s[(2 * q + 1) * 64 + lane];
 		re[q] = L[ke - 1] + se * (L[ke] - L[ke - 1]);
 		im[q] = L[ko - 1] + so * (L[ko] - L[ko - 1]);
 	}
@@ -110,67 +99,10 @@ __global__ __launch_bounds__(64) void code_features_wave_kernel(const double *__
 	if (!SMALL && lane == 0 && nd > MD / 2) out[MD / 2] = ((0.5 * nyq) * p.w[MD / 2].x - 0.0 * p.w[MD / 2].y) / normalization;
 }
 
-// The coding plan per (device, fs, fft_size), built and uploaded on first use and kept for the life of the process (at most
-// 80 KB each): k, s, w in the order of code_sp_kernel, and at fft_size 2048 / 4096 k, s once more in the wavefront kernel's order.
-struct CodePlan {
-	DevBuf k, s, w, kp, sp;
-};
-std::mutex g_plan_mu;
-std::map<std::tuple<int, int, int>, CodePlan *> g_plans;
-
-int upload(DevBuf &b, const void *src, size_t bytes) {
-	int rc = b.reserve(bytes);
-	if (rc) return rc;
-	const hipError_t e = hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice);
-	if (e != hipSuccess) return fail(WC_ERR_DEVICE, std::string("code_features: plan upload: ") + hipGetErrorString(e));
-	return WC_OK;
-}
-
-int code_plan(Device *dev, int fs, int fft_size, const CodePlan **out) {
-	std::lock_guard<std::mutex> g(g_plan_mu);
-	CodePlan *&pl = g_plans[std::make_tuple(dev->id, fs, fft_size)];
-	if (!pl) {
-		std::vector<int> k;
-		std::vector<double> s;
-		std::vector<double2> w;
-		codec_code_sp_plan(fs, fft_size, k, s, w);
-		CodePlan *n = new CodePlan();
-		int rc = upload(n->k, k.data(), sizeof(int) * k.size());
-		if (!rc) rc = upload(n->s, s.data(), sizeof(double) * s.size());
-		if (!rc) rc = upload(n->w, w.data(), sizeof(double2) * w.size());
-		if (!rc && fft_size >= 2048) {
-			// waveform[i] = mel[2 i], waveform[i + md/2] = mel[md - 1 - 2 i] (DCTForCodec, reference :76-80); lane t's slot q holds
-			// waveform[2 m] + i waveform[2 m + 1], m = t + 64 q
-			const int md = fft_size / 2;
-			std::vector<int> kp(md);
-			std::vector<double> sp(md);
-			for (int q = 0; q < md / 128; ++q)
-				for (int h = 0; h < 2; ++h)
-					for (int t = 0; t < 64; ++t) {
-						const int pos = 2 * (t + 64 * q) + h;
-						const int mel = pos < md / 2 ? 2 * pos : 2 * md - 1 - 2 * pos;
-						kp[(2 * q + h) * 64 + t] = k[mel];
-						sp[(2 * q + h) * 64 + t] = s[mel];
-					}
-			rc = upload(n->kp, kp.data(), sizeof(int) * md);
-			if (!rc) rc = upload(n->sp, sp.data(), sizeof(double) * md);
-		}
-		if (rc) {
-			for (DevBuf *b : {&n->k, &n->s, &n->w, &n->kp, &n->sp}) b->release();
-			delete n;
-			g_plans.erase(std::make_tuple(dev->id, fs, fft_size));
-			return rc;
-		}
-		pl = n;
-	}
-	*out = pl;
-	return WC_OK;
-}
-
 }  // namespace
 
 const char *wc::code_features_check(int fs, int fft_size, int nd, bool with_ap) {
-	if (!(fft_size == 512 || fft_size == 1024 || fft_size == 2048 || fft_size == 4096)) return "code_features: fft_size must be 512, 1024, 2048 or 4096";
+	if (!fft_size_supported(fft_size)) return "code_features: fft_size must be 512, 1024, 2048 or 4096";
 	if (nd < 1 || nd > fft_size / 4 + 1) return "code_features: number_of_dimensions must be 1 .. fft_size/4+1";
 	if (fs <= 0) return "code_features: fs must be positive";
 	if (with_ap && GetNumberOfAperiodicities(fs) < 1) return "code_features: aperiodicity needs fs of at least 12 kHz (no band below)";
@@ -178,21 +110,18 @@ const char *wc::code_features_check(int fs, int fft_size, int nd, bool with_ap) 
 }
 
 int wc::code_features_prepare(Device *dev, int fs, int fft_size) {
-	const CodePlan *pl;
-	return code_plan(dev, fs, fft_size, &pl);
+	const CodecPlan *pl;
+	return codec_plan(dev, fs, fft_size, true, &pl);
 }
 
 int wc::code_features_enqueue(Device *dev, hipStream_t s, int fs, int fft_size, long long n_frames, int nd, const double *d_sp,
 							  const double *d_ap, double *d_coded_sp, double *d_coded_ap) {
 	if (n_frames == 0) return WC_OK;
-	const CodePlan *pl;
+	const CodecPlan *pl;
 	int rc;
-	if ((rc = code_plan(dev, fs, fft_size, &pl))) return rc;
+	if ((rc = codec_plan(dev, fs, fft_size, true, &pl))) return rc;
 	if (fft_size >= 2048) {
-		EncPlan p;
-		p.kp = pl->kp.as<int>();
-		p.sp = pl->sp.as<double>();
-		p.w = pl->w.as<double2>();
+		const CodecPlanArgs p = pl->wave_args();
 		const int n_ap = d_ap ? GetNumberOfAperiodicities(fs) : 0;
 		const dim3 grid((unsigned)n_frames), block(64);
 		const double2 *tw = (const double2 *)dev->twiddle;
@@ -207,8 +136,7 @@ int wc::code_features_enqueue(Device *dev, hipStream_t s, int fs, int fft_size, 
 		WC_HIP(hipGetLastError());
 		return WC_OK;
 	}
-	if ((rc = codec_code_sp_launch(dev, s, fft_size, n_frames, nd, d_sp, d_coded_sp, pl->k.as<int>(), pl->s.as<double>(), pl->w.as<double2>())))
-		return rc;
+	if ((rc = codec_code_sp_launch(dev, s, fft_size, n_frames, nd, d_sp, d_coded_sp, *pl))) return rc;
 	return d_ap ? codec_code_ap_launch(s, fs, fft_size, n_frames, d_ap, d_coded_ap) : WC_OK;
 }
 

@@ -8,11 +8,16 @@
 //                          mel axis in Hz onto the linear axis -> exp
 //   code_ap_kernel         thread per (frame, band): 20 log10 and interp1Q at 3 kHz multiples (:216-236)
 //   decode_ap_kernel       workgroup per frame: voiced/unvoiced test on the mean (:19-30), interp1 + 10^(v/20) (:32-40)
+// and the one store of their plans: built and uploaded once per (device, fs, fft_size) and direction, kept for the life of the
+// process, shared with the one-wavefront kernels of wc_code_features.hip and wc_synth_coded.hip.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <map>
+#include <mutex>
+#include <tuple>
 #include <vector>
 
 #include "../../include/world_class_c.h"
@@ -26,7 +31,7 @@ using namespace wc;
 namespace {
 
 constexpr double kM0 = 1127.01048, kF0c = 700.0, kFloorFrequency = 40.0, kCeilFrequency = 20000.0;  // world_constantnumbers.hpp
-constexpr double kUpperLimit = 15000.0, kFrequencyInterval = 3000.0, kSafeGuard = 0.000000000001;
+constexpr double kUpperLimit = 15000.0;
 constexpr double kPiH = 3.1415926535897932384;
 
 double frequency_to_mel(double f) { return kM0 * std::log(f / kF0c + 1.0); }          // reference :42-44
@@ -57,14 +62,8 @@ void interp1_plan(const std::vector<double> &x, const std::vector<double> &xi, s
 	for (size_t i = 0; i < xi.size(); ++i) s[i] = (xi[i] - x[k[i] - 1]) / (x[k[i]] - x[k[i] - 1]);
 }
 
-struct SpPlan {
-	int *k;
-	double *s;
-	double2 *w;
-};
-
 template <int MD>
-__global__ __launch_bounds__(256) void code_sp_kernel(const double *__restrict__ sp, double *__restrict__ coded, int nd, SpPlan p,
+__global__ __launch_bounds__(256) void code_sp_kernel(const double *__restrict__ sp, double *__restrict__ coded, int nd, CodecPlanArgs p,
 													  const double2 *__restrict__ tw) {
 	constexpr int M = MD / 2, T = 256;
 	__shared__ double lg[MD + 1];
@@ -95,7 +94,7 @@ __global__ __launch_bounds__(256) void code_sp_kernel(const double *__restrict__
 }
 
 template <int MD>
-__global__ __launch_bounds__(256) void decode_sp_kernel(const double *__restrict__ coded, double *__restrict__ sp, int nd, SpPlan p,
+__global__ __launch_bounds__(256) void decode_sp_kernel(const double *__restrict__ coded, double *__restrict__ sp, int nd, CodecPlanArgs p,
 														const double2 *__restrict__ tw) {
 	constexpr int T = 256;
 	__shared__ double2 A[fft_lds_size(MD)];
@@ -151,56 +150,18 @@ __global__ __launch_bounds__(256) void decode_ap_kernel(const double *__restrict
 	const int bins = fft_size / 2 + 1;
 	const double *__restrict__ c = coded + (long long)blockIdx.x * n_ap;
 	double *__restrict__ row = ap + (long long)blockIdx.x * bins;
-	double tmp = 0.0;
-	for (int i = 0; i < n_ap; ++i) tmp += c[i];
-	tmp /= n_ap;  // no band (fs below 12 kHz): 0 / 0 = NaN, voiced, and the row is the line from -60 dB at 0 Hz to fs/2
-	if (tmp > -0.5) {  // CheckVUV: treated as unvoiced, the initial value stays
+	if (coded_ap_unvoiced(c, n_ap)) {
 		for (int j = threadIdx.x; j < bins; j += 256) row[j] = 1.0 - kSafeGuard;
 		return;
 	}
-	const int na = n_ap + 2;
-	auto axis = [&](int q) { return q == na - 1 ? fs / 2.0 : q * kFrequencyInterval; };
-	auto val = [&](int q) { return q == 0 ? -60.0 : (q == na - 1 ? -kSafeGuard : c[q - 1]); };
-	for (int j = threadIdx.x; j < bins; j += 256) {
-		const double f = static_cast<double>(fs) / fft_size * j;
-		int k = 1;  // histc: clamp(#{q : axis(q) <= f}, 1, na - 1)
-		while (k < na && f >= axis(k)) ++k;
-		k = k < na - 1 ? k : na - 1;
-		const double x0 = axis(k - 1), x1 = axis(k);
-		const double s = (f - x0) / (x1 - x0);
-		const double v = val(k - 1) + s * (val(k) - val(k - 1));
-		row[j] = pow(10.0, v / 20.0);
-	}
+	for (int j = threadIdx.x; j < bins; j += 256) row[j] = pow(10.0, coded_ap_db(c, n_ap, fs, fft_size, j) / 20.0);
 }
 
 bool sp_sizes_ok(int fs, int fft_size, int nd, bool coding) {
-	if (fs <= 0 || !(fft_size == 512 || fft_size == 1024 || fft_size == 2048 || fft_size == 4096)) return false;
+	if (fs <= 0 || !fft_size_supported(fft_size)) return false;
 	// the reference reads spectrum[i] for i < number_of_dimensions out of fft_size/4+1 bins when coding and fills
 	// fft_size/2 inputs when decoding
 	return nd >= 1 && nd <= (coding ? fft_size / 4 + 1 : fft_size / 2);
-}
-
-struct ScopedBuf : DevBuf {  // per-call scratch: released on scope exit
-	~ScopedBuf() { release(); }
-};
-struct PlanBufs {
-	ScopedBuf k, s, w;
-};
-
-int upload_plan(Device *dev, PlanBufs &b, const std::vector<int> &k, const std::vector<double> &s, const std::vector<double2> &w,
-				SpPlan &out) {
-	int rc;
-	if ((rc = b.k.reserve(sizeof(int) * k.size()))) return rc;
-	if ((rc = b.s.reserve(sizeof(double) * s.size()))) return rc;
-	if ((rc = b.w.reserve(sizeof(double2) * w.size()))) return rc;
-	WC_HIP(hipMemcpyAsync(b.k.p, k.data(), sizeof(int) * k.size(), hipMemcpyHostToDevice, dev->active()));
-	WC_HIP(hipMemcpyAsync(b.s.p, s.data(), sizeof(double) * s.size(), hipMemcpyHostToDevice, dev->active()));
-	WC_HIP(hipMemcpyAsync(b.w.p, w.data(), sizeof(double2) * w.size(), hipMemcpyHostToDevice, dev->active()));
-	WC_HIP(hipStreamSynchronize(dev->active()));  // the host vectors go out of scope with the caller
-	out.k = b.k.as<int>();
-	out.s = b.s.as<double>();
-	out.w = b.w.as<double2>();
-	return WC_OK;
 }
 
 // host-pointer wrappers: rows <-> packed device buffers
@@ -225,15 +186,13 @@ void report(int rc) {
 	if (rc != WC_OK) std::fprintf(stderr, "world_class codec: %s\n", wc_last_error());
 }
 
-}  // namespace
-
-// GetParametersForDecoding, reference :144-166
-void wc::codec_decode_sp_plan(int fs, int fft_size, int nd, std::vector<int> &k, std::vector<double> &s, std::vector<double2> &w) {
+// GetParametersForDecoding, reference :144-166, with the weights of all fft_size/2 coefficients (the kernels drop those beyond nd)
+void decode_sp_plan(int fs, int fft_size, std::vector<int> &k, std::vector<double> &s, std::vector<double2> &w) {
 	const int md = fft_size / 2;
 	const double floor_mel = frequency_to_mel(kFloorFrequency);
 	const double ceil_mel = frequency_to_mel(fs / 2.0 < kCeilFrequency ? fs / 2.0 : kCeilFrequency);
 	w.assign(md, make_double2(0.0, 0.0));
-	for (int i = 0; i < nd; ++i)
+	for (int i = 0; i < md; ++i)
 		w[i] = make_double2(std::cos(i * kPiH / fft_size) * std::sqrt((double)fft_size), std::sin(i * kPiH / fft_size) * std::sqrt((double)fft_size));
 	w[0].x /= std::sqrt(2.0);
 	std::vector<double> mel_axis(md + 2), freq_axis(md + 1);
@@ -245,7 +204,7 @@ void wc::codec_decode_sp_plan(int fs, int fft_size, int nd, std::vector<int> &k,
 }
 
 // GetParametersForCoding, reference :125-142
-void wc::codec_code_sp_plan(int fs, int fft_size, std::vector<int> &k, std::vector<double> &s, std::vector<double2> &w) {
+void code_sp_plan(int fs, int fft_size, std::vector<int> &k, std::vector<double> &s, std::vector<double2> &w) {
 	const int md = fft_size / 2;
 	const double floor_mel = frequency_to_mel(kFloorFrequency);
 	const double ceil_mel = frequency_to_mel(fs / 2.0 < kCeilFrequency ? fs / 2.0 : kCeilFrequency);
@@ -264,19 +223,82 @@ void wc::codec_code_sp_plan(int fs, int fft_size, std::vector<int> &k, std::vect
 	interp1_plan(freq_axis, mel_axis, k, s);
 }
 
-// the workgroup-per-frame coders on a plan that lives on the device (wc_code_features.hip keeps one per (device, fs, fft_size))
+// The plans per (device, fs, fft_size, coding), built and uploaded on first use and kept for the life of the process (coding at most
+// 80 KB, decoding 56 KB each): a call then only enqueues.
+std::mutex g_plan_mu;
+std::map<std::tuple<int, int, int, bool>, CodecPlan> g_plans;
+
+}  // namespace
+
+int wc::codec_plan(Device *dev, int fs, int fft_size, bool coding, const CodecPlan **out) {
+	std::lock_guard<std::mutex> g(g_plan_mu);
+	const auto key = std::make_tuple(dev->id, fs, fft_size, coding);
+	auto it = g_plans.find(key);
+	if (it == g_plans.end()) {
+		const int md = fft_size / 2;
+		std::vector<int> k, kp;
+		std::vector<double> s, sp;
+		std::vector<double2> w;
+		if (coding) code_sp_plan(fs, fft_size, k, s, w);
+		else decode_sp_plan(fs, fft_size, k, s, w);
+		if (coding && fft_size >= 2048) {
+			// waveform[i] = mel[2 i], waveform[i + md/2] = mel[md - 1 - 2 i] (DCTForCodec, reference :76-80); lane t's slot q holds
+			// waveform[2 m] + i waveform[2 m + 1], m = t + 64 q
+			kp.resize(md);
+			sp.resize(md);
+			for (int q = 0; q < md / 128; ++q)
+				for (int h = 0; h < 2; ++h)
+					for (int t = 0; t < 64; ++t) {
+						const int pos = 2 * (t + 64 * q) + h;
+						const int mel = pos < md / 2 ? 2 * pos : 2 * md - 1 - 2 * pos;
+						kp[(2 * q + h) * 64 + t] = k[mel];
+						sp[(2 * q + h) * 64 + t] = s[mel];
+					}
+		}
+		CodecPlan n;
+		auto upload = [](DevBuf &b, const void *src, size_t bytes) {
+			int rc = b.reserve(bytes);
+			if (rc || !bytes) return rc;
+			const hipError_t e = hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice);
+			return e == hipSuccess ? WC_OK : fail(WC_ERR_DEVICE, std::string("codec: plan upload: ") + hipGetErrorString(e));
+		};
+		int rc = upload(n.k, k.data(), sizeof(int) * k.size());
+		if (!rc) rc = upload(n.s, s.data(), sizeof(double) * s.size());
+		if (!rc) rc = upload(n.w, w.data(), sizeof(double2) * w.size());
+		if (!rc) rc = upload(n.kp, kp.data(), sizeof(int) * kp.size());
+		if (!rc) rc = upload(n.sp, sp.data(), sizeof(double) * sp.size());
+		if (rc) {  // nothing half-built stays behind
+			for (DevBuf *b : {&n.k, &n.s, &n.w, &n.kp, &n.sp}) b->release();
+			return rc;
+		}
+		it = g_plans.emplace(key, n).first;
+	}
+	*out = &it->second;
+	return WC_OK;
+}
+
+// the workgroup-per-frame kernels enqueued on st with a plan of codec_plan (arguments already checked)
 int wc::codec_code_sp_launch(Device *dev, hipStream_t st, int fft_size, long long n_frames, int nd, const double *d_sp, double *d_coded,
-							 const int *d_k, const double *d_s, const double2 *d_w) {
-	SpPlan plan;
-	plan.k = const_cast<int *>(d_k);
-	plan.s = const_cast<double *>(d_s);
-	plan.w = const_cast<double2 *>(d_w);
+							 const CodecPlan &pl) {
 	const dim3 grid((unsigned)n_frames), block(256);
 	switch (fft_size / 2) {
-		case 256: hipLaunchKernelGGL(code_sp_kernel<256>, grid, block, 0, st, d_sp, d_coded, nd, plan, dev->twiddle); break;
-		case 512: hipLaunchKernelGGL(code_sp_kernel<512>, grid, block, 0, st, d_sp, d_coded, nd, plan, dev->twiddle); break;
-		case 1024: hipLaunchKernelGGL(code_sp_kernel<1024>, grid, block, 0, st, d_sp, d_coded, nd, plan, dev->twiddle); break;
-		default: hipLaunchKernelGGL(code_sp_kernel<2048>, grid, block, 0, st, d_sp, d_coded, nd, plan, dev->twiddle); break;
+		case 256: hipLaunchKernelGGL(code_sp_kernel<256>, grid, block, 0, st, d_sp, d_coded, nd, pl.args(), dev->twiddle); break;
+		case 512: hipLaunchKernelGGL(code_sp_kernel<512>, grid, block, 0, st, d_sp, d_coded, nd, pl.args(), dev->twiddle); break;
+		case 1024: hipLaunchKernelGGL(code_sp_kernel<1024>, grid, block, 0, st, d_sp, d_coded, nd, pl.args(), dev->twiddle); break;
+		default: hipLaunchKernelGGL(code_sp_kernel<2048>, grid, block, 0, st, d_sp, d_coded, nd, pl.args(), dev->twiddle); break;
+	}
+	WC_HIP(hipGetLastError());
+	return WC_OK;
+}
+
+int wc::codec_decode_sp_launch(Device *dev, hipStream_t st, int fft_size, long long n_frames, int nd, const double *d_coded, double *d_sp,
+							   const CodecPlan &pl) {
+	const dim3 grid((unsigned)n_frames), block(256);
+	switch (fft_size / 2) {
+		case 256: hipLaunchKernelGGL(decode_sp_kernel<256>, grid, block, 0, st, d_coded, d_sp, nd, pl.args(), dev->twiddle); break;
+		case 512: hipLaunchKernelGGL(decode_sp_kernel<512>, grid, block, 0, st, d_coded, d_sp, nd, pl.args(), dev->twiddle); break;
+		case 1024: hipLaunchKernelGGL(decode_sp_kernel<1024>, grid, block, 0, st, d_coded, d_sp, nd, pl.args(), dev->twiddle); break;
+		default: hipLaunchKernelGGL(decode_sp_kernel<2048>, grid, block, 0, st, d_coded, d_sp, nd, pl.args(), dev->twiddle); break;
 	}
 	WC_HIP(hipGetLastError());
 	return WC_OK;
@@ -290,6 +312,46 @@ int wc::codec_code_ap_launch(hipStream_t st, int fs, int fft_size, long long n_f
 	return WC_OK;
 }
 
+int wc::codec_decode_ap_launch(hipStream_t st, int fs, int fft_size, long long n_frames, const double *d_coded, double *d_ap) {
+	hipLaunchKernelGGL(decode_ap_kernel, dim3((unsigned)n_frames), dim3(256), 0, st, d_coded, d_ap, GetNumberOfAperiodicities(fs), fs, fft_size);
+	WC_HIP(hipGetLastError());
+	return WC_OK;
+}
+
+namespace {
+
+// the spectral-envelope calls: the plan, the kernel, and the work complete on return
+int sp_call(bool coding, int fs, int fft_size, long long n_frames, int nd, const double *d_in, double *d_out) {
+	Device *dev = current_device();
+	if (!dev) return WC_ERR_DEVICE;
+	DeviceLock lock(dev);
+	if (n_frames == 0) return WC_OK;
+	const CodecPlan *pl;
+	int rc;
+	if ((rc = codec_plan(dev, fs, fft_size, coding, &pl))) return rc;
+	if ((rc = (coding ? codec_code_sp_launch : codec_decode_sp_launch)(dev, dev->active(), fft_size, n_frames, nd, d_in, d_out, *pl))) return rc;
+	WC_HIP(hipStreamSynchronize(dev->active()));
+	return WC_OK;
+}
+
+// the host-pointer calls: n rows up into per-call scratch (w_in 0: nothing to read), the device call, the rows down
+template <class F>
+void host_call(const double *const *in_rows, int w_in, int n, double **out_rows, int w_out, F device_call) {
+	Device *dev = current_device();
+	if (!dev) { report(WC_ERR_DEVICE); return; }
+	if (n <= 0) return;
+	DevBuf in, out;
+	int rc = w_in > 0 ? rows_to_device(in_rows, n, w_in, in, dev->active()) : WC_OK;
+	if (!rc) rc = out.reserve(sizeof(double) * (size_t)n * w_out);
+	if (!rc) rc = device_call(in.as<double>(), out.as<double>());
+	if (!rc) rc = device_to_rows(out, n, w_out, out_rows, dev->active());
+	in.release();
+	out.release();
+	report(rc);
+}
+
+}  // namespace
+
 extern "C" {
 
 int GetNumberOfAperiodicities(int fs) {
@@ -300,57 +362,13 @@ int GetNumberOfAperiodicities(int fs) {
 int wc_code_spectral_envelope_device(int fs, int fft_size, long long n_frames, int nd, const double *d_sp, double *d_coded) {
 	if (!sp_sizes_ok(fs, fft_size, nd, true) || n_frames < 0)
 		return fail(WC_ERR_INVALID, "code_spectral_envelope: fft_size must be 512..4096 and 1 <= number_of_dimensions <= fft_size/4+1");
-	Device *dev = current_device();
-	if (!dev) return WC_ERR_DEVICE;
-	DeviceLock lock(dev);
-	if (n_frames == 0) return WC_OK;
-	const int md = fft_size / 2;
-	std::vector<int> k;
-	std::vector<double> s;
-	std::vector<double2> w;
-	codec_code_sp_plan(fs, fft_size, k, s, w);
-	PlanBufs bufs;
-	SpPlan plan;
-	int rc;
-	if ((rc = upload_plan(dev, bufs, k, s, w, plan))) return rc;
-	const dim3 grid((unsigned)n_frames), block(256);
-	switch (md) {
-		case 256: hipLaunchKernelGGL(code_sp_kernel<256>, grid, block, 0, dev->active(), d_sp, d_coded, nd, plan, dev->twiddle); break;
-		case 512: hipLaunchKernelGGL(code_sp_kernel<512>, grid, block, 0, dev->active(), d_sp, d_coded, nd, plan, dev->twiddle); break;
-		case 1024: hipLaunchKernelGGL(code_sp_kernel<1024>, grid, block, 0, dev->active(), d_sp, d_coded, nd, plan, dev->twiddle); break;
-		default: hipLaunchKernelGGL(code_sp_kernel<2048>, grid, block, 0, dev->active(), d_sp, d_coded, nd, plan, dev->twiddle); break;
-	}
-	WC_HIP(hipGetLastError());
-	WC_HIP(hipStreamSynchronize(dev->active()));  // the plan buffers are freed on return
-	return WC_OK;
+	return sp_call(true, fs, fft_size, n_frames, nd, d_sp, d_coded);
 }
 
 int wc_decode_spectral_envelope_device(int fs, int fft_size, long long n_frames, int nd, const double *d_coded, double *d_sp) {
 	if (!sp_sizes_ok(fs, fft_size, nd, false) || n_frames < 0)
 		return fail(WC_ERR_INVALID, "decode_spectral_envelope: fft_size must be 512..4096 and 1 <= number_of_dimensions <= fft_size/2");
-	Device *dev = current_device();
-	if (!dev) return WC_ERR_DEVICE;
-	DeviceLock lock(dev);
-	if (n_frames == 0) return WC_OK;
-	const int md = fft_size / 2;
-	std::vector<int> k;
-	std::vector<double> s;
-	std::vector<double2> w;
-	codec_decode_sp_plan(fs, fft_size, nd, k, s, w);
-	PlanBufs bufs;
-	SpPlan plan;
-	int rc;
-	if ((rc = upload_plan(dev, bufs, k, s, w, plan))) return rc;
-	const dim3 grid((unsigned)n_frames), block(256);
-	switch (md) {
-		case 256: hipLaunchKernelGGL(decode_sp_kernel<256>, grid, block, 0, dev->active(), d_coded, d_sp, nd, plan, dev->twiddle); break;
-		case 512: hipLaunchKernelGGL(decode_sp_kernel<512>, grid, block, 0, dev->active(), d_coded, d_sp, nd, plan, dev->twiddle); break;
-		case 1024: hipLaunchKernelGGL(decode_sp_kernel<1024>, grid, block, 0, dev->active(), d_coded, d_sp, nd, plan, dev->twiddle); break;
-		default: hipLaunchKernelGGL(decode_sp_kernel<2048>, grid, block, 0, dev->active(), d_coded, d_sp, nd, plan, dev->twiddle); break;
-	}
-	WC_HIP(hipGetLastError());
-	WC_HIP(hipStreamSynchronize(dev->active()));
-	return WC_OK;
+	return sp_call(false, fs, fft_size, n_frames, nd, d_coded, d_sp);
 }
 
 int wc_code_aperiodicity_device(int fs, int fft_size, long long n_frames, const double *d_ap, double *d_coded) {
@@ -360,75 +378,44 @@ int wc_code_aperiodicity_device(int fs, int fft_size, long long n_frames, const 
 	Device *dev = current_device();
 	if (!dev) return WC_ERR_DEVICE;
 	DeviceLock lock(dev);
-	if (n_frames == 0) return WC_OK;
-	const long long total = n_frames * n_ap;
-	hipLaunchKernelGGL(code_ap_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, dev->active(), d_ap, d_coded, n_frames, n_ap, fs, fft_size);
-	WC_HIP(hipGetLastError());
-	return WC_OK;
+	return n_frames ? codec_code_ap_launch(dev->active(), fs, fft_size, n_frames, d_ap, d_coded) : WC_OK;
 }
 
 int wc_decode_aperiodicity_device(int fs, int fft_size, long long n_frames, const double *d_coded, double *d_ap) {
-	const int n_ap = GetNumberOfAperiodicities(fs);  // 0 below 12 kHz: d_coded is not read (reference :238-267 fills every row)
+	// no band below 12 kHz: d_coded is not read (reference :238-267 fills every row)
 	if (fs <= 0 || fft_size < 2 || n_frames < 0) return fail(WC_ERR_INVALID, "decode_aperiodicity: bad argument");
 	Device *dev = current_device();
 	if (!dev) return WC_ERR_DEVICE;
 	DeviceLock lock(dev);
-	if (n_frames == 0) return WC_OK;
-	hipLaunchKernelGGL(decode_ap_kernel, dim3((unsigned)n_frames), dim3(256), 0, dev->active(), d_coded, d_ap, n_ap, fs, fft_size);
-	WC_HIP(hipGetLastError());
-	return WC_OK;
+	return n_frames ? codec_decode_ap_launch(dev->active(), fs, fft_size, n_frames, d_coded, d_ap) : WC_OK;
 }
 
 void CodeSpectralEnvelope(const double *const *spectrogram, int f0_length, int fs, int fft_size, int number_of_dimensions,
 						  double **coded_spectral_envelope) {
-	Device *dev = current_device();
-	if (!dev) { report(WC_ERR_DEVICE); return; }
-	if (f0_length <= 0) return;
-	ScopedBuf in, out;
-	int rc = rows_to_device(spectrogram, f0_length, fft_size / 2 + 1, in, dev->active());
-	if (!rc) rc = out.reserve(sizeof(double) * (size_t)f0_length * number_of_dimensions);
-	if (!rc) rc = wc_code_spectral_envelope_device(fs, fft_size, f0_length, number_of_dimensions, in.as<double>(), out.as<double>());
-	if (!rc) rc = device_to_rows(out, f0_length, number_of_dimensions, coded_spectral_envelope, dev->active());
-	report(rc);
+	host_call(spectrogram, fft_size / 2 + 1, f0_length, coded_spectral_envelope, number_of_dimensions, [&](const double *in, double *out) {
+		return wc_code_spectral_envelope_device(fs, fft_size, f0_length, number_of_dimensions, in, out);
+	});
 }
 
 void DecodeSpectralEnvelope(const double *const *coded_spectral_envelope, int f0_length, int fs, int fft_size,
 							int number_of_dimensions, double **spectrogram) {
-	Device *dev = current_device();
-	if (!dev) { report(WC_ERR_DEVICE); return; }
-	if (f0_length <= 0) return;
-	ScopedBuf in, out;
-	int rc = rows_to_device(coded_spectral_envelope, f0_length, number_of_dimensions, in, dev->active());
-	if (!rc) rc = out.reserve(sizeof(double) * (size_t)f0_length * (fft_size / 2 + 1));
-	if (!rc) rc = wc_decode_spectral_envelope_device(fs, fft_size, f0_length, number_of_dimensions, in.as<double>(), out.as<double>());
-	if (!rc) rc = device_to_rows(out, f0_length, fft_size / 2 + 1, spectrogram, dev->active());
-	report(rc);
+	host_call(coded_spectral_envelope, number_of_dimensions, f0_length, spectrogram, fft_size / 2 + 1, [&](const double *in, double *out) {
+		return wc_decode_spectral_envelope_device(fs, fft_size, f0_length, number_of_dimensions, in, out);
+	});
 }
 
 void CodeAperiodicity(const double *const *aperiodicity, int f0_length, int fs, int fft_size, double **coded_aperiodicity) {
-	Device *dev = current_device();
-	if (!dev) { report(WC_ERR_DEVICE); return; }
-	const int n_ap = GetNumberOfAperiodicities(fs);
-	if (f0_length <= 0 || n_ap < 1) return;  // no band below 12 kHz: the reference writes nothing either
-	ScopedBuf in, out;
-	int rc = rows_to_device(aperiodicity, f0_length, fft_size / 2 + 1, in, dev->active());
-	if (!rc) rc = out.reserve(sizeof(double) * (size_t)f0_length * n_ap);
-	if (!rc) rc = wc_code_aperiodicity_device(fs, fft_size, f0_length, in.as<double>(), out.as<double>());
-	if (!rc) rc = device_to_rows(out, f0_length, n_ap, coded_aperiodicity, dev->active());
-	report(rc);
+	const int n_ap = GetNumberOfAperiodicities(fs);  // no band below 12 kHz: the reference writes nothing either
+	host_call(aperiodicity, fft_size / 2 + 1, n_ap < 1 ? 0 : f0_length, coded_aperiodicity, n_ap, [&](const double *in, double *out) {
+		return wc_code_aperiodicity_device(fs, fft_size, f0_length, in, out);
+	});
 }
 
 void DecodeAperiodicity(const double *const *coded_aperiodicity, int f0_length, int fs, int fft_size, double **aperiodicity) {
-	Device *dev = current_device();
-	if (!dev) { report(WC_ERR_DEVICE); return; }
-	if (f0_length <= 0) return;
-	const int n_ap = GetNumberOfAperiodicities(fs);
-	ScopedBuf in, out;
-	int rc = n_ap >= 1 ? rows_to_device(coded_aperiodicity, f0_length, n_ap, in, dev->active()) : WC_OK;  // no band: nothing to read
-	if (!rc) rc = out.reserve(sizeof(double) * (size_t)f0_length * (fft_size / 2 + 1));
-	if (!rc) rc = wc_decode_aperiodicity_device(fs, fft_size, f0_length, in.as<double>(), out.as<double>());
-	if (!rc) rc = device_to_rows(out, f0_length, fft_size / 2 + 1, aperiodicity, dev->active());
-	report(rc);
+	// (no band: nothing to read)
+	host_call(coded_aperiodicity, GetNumberOfAperiodicities(fs), f0_length, aperiodicity, fft_size / 2 + 1, [&](const double *in, double *out) {
+		return wc_decode_aperiodicity_device(fs, fft_size, f0_length, in, out);
+	});
 }
 
 }  // extern "C"

@@ -206,15 +206,13 @@ __global__ void scale_f0_frames_kernel(double *__restrict__ f0, long long n, con
 	for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) f0[i] *= s[i];
 }
 
-// One workgroup per frame: the row's logarithm goes to LDS, every thread interpolates its bins (reference interp1,
-// src/world_matlabfunctions.cpp:157-182, with histc's clamp(#{x[j] <= xi}, 1, n - 1) and linear extrapolation).
+// One workgroup per frame: the row's logarithm goes to LDS, every thread takes its bins from wc::stretched_bin (wc_stretch.hpp).
 // PER_FRAME: the frame's own ratio out of `ratios` (wc_modify_parameters_frames_device) instead of the call's; 0 leaves the row,
 // a value the scalar call's host check or the fill below could not take (negative, NaN, infinite, cut < 1) makes the row NaN.
-constexpr int MOD_MAX_BINS = 4096 / 2 + 1;
 template <bool PER_FRAME>
 __global__ __launch_bounds__(256) void stretch_kernel(double *__restrict__ sp, int fs, int fft_size, double ratio,
 													  const double *__restrict__ ratios) {
-	__shared__ double lg[MOD_MAX_BINS];
+	__shared__ double lg[wc::kMaxBins];
 	const int bins = fft_size / 2 + 1;
 	double *__restrict__ row = sp + (long long)blockIdx.x * bins;
 	if (PER_FRAME) {
@@ -227,21 +225,8 @@ __global__ __launch_bounds__(256) void stretch_kernel(double *__restrict__ sp, i
 	}
 	for (int j = threadIdx.x; j < bins; j += 256) lg[j] = log(row[j]);
 	__syncthreads();
-	auto axis1 = [&](int j) { return ratio * j / fft_size * fs; };  // reference test/test.cpp:222
 	const int cut = static_cast<int>(fft_size / 2.0 * ratio);
-	for (int i = threadIdx.x; i < bins; i += 256) {
-		const double xi = static_cast<double>(i) / fft_size * fs;
-		// c = #{j : axis1(j) <= xi}: start from the real-number estimate and settle with the reference's expressions
-		int c = static_cast<int>(i / ratio) + 1;
-		c = c < 0 ? 0 : (c > bins ? bins : c);
-		while (c < bins && axis1(c) <= xi) ++c;
-		while (c > 0 && !(axis1(c - 1) <= xi)) --c;
-		const int k = c < 1 ? 1 : (c > bins - 1 ? bins - 1 : c);
-		const double x0 = axis1(k - 1), x1 = axis1(k);
-		const double s = (xi - x0) / (x1 - x0);
-		double v = exp(lg[k - 1] + s * (lg[k] - lg[k - 1]));
-		row[i] = v;
-	}
+	for (int i = threadIdx.x; i < bins; i += 256) row[i] = wc::stretched_bin(i, ratio, fs, fft_size, [&](int k) { return lg[k]; });
 	if (ratio < 1.0 && cut >= 1) {  // bins from `cut` upward repeat bin cut - 1 (reference :236-240)
 		__syncthreads();
 		const double fill = row[cut - 1];
@@ -437,7 +422,7 @@ int wc_double_to_pcm16_device(const double *d_y, long long n, int16_t *d_pcm) {
 
 int wc_modify_parameters_device(int fs, int fft_size, long long n_frames, double *d_f0, double *d_sp, double f0_scale,
 								double spectral_ratio) {
-	if (fs <= 0 || fft_size < 2 || fft_size / 2 + 1 > MOD_MAX_BINS || n_frames < 0 || spectral_ratio < 0.0)
+	if (fs <= 0 || fft_size < 2 || fft_size / 2 + 1 > wc::kMaxBins || n_frames < 0 || spectral_ratio < 0.0)
 		return fail(WC_ERR_INVALID, "modify_parameters: bad argument (fft_size <= 4096, ratio >= 0)");
 	Device *dev = current_device();
 	if (!dev) return WC_ERR_DEVICE;
@@ -456,7 +441,7 @@ int wc_modify_parameters_device(int fs, int fft_size, long long n_frames, double
 
 int wc_modify_parameters_frames_device(int fs, int fft_size, long long n_frames, double *d_f0, double *d_sp, const double *d_f0_scale,
 									   const double *d_spectral_ratio) {
-	if (fs <= 0 || fft_size < 2 || fft_size / 2 + 1 > MOD_MAX_BINS || n_frames < 0 || n_frames > 0xffffffffll)
+	if (fs <= 0 || fft_size < 2 || fft_size / 2 + 1 > wc::kMaxBins || n_frames < 0 || n_frames > 0xffffffffll)
 		return fail(WC_ERR_INVALID, "modify_parameters_frames: bad argument (fft_size <= 4096, 0 <= n_frames < 2^32)");
 	Device *dev = current_device();
 	if (!dev) return WC_ERR_DEVICE;

@@ -9,8 +9,8 @@
 //     traffic: up to four rows in, two out, two bins per lane and access (a row of fft_size/2+1 doubles starts on a 16-byte
 //     boundary on every other frame only, so the 16-byte accesses are issued with 8-byte alignment and the row's odd last bin is
 //     peeled); consecutive output frames sit on consecutive workgroups, so the source row two neighbours share comes out of L2.
-//     STRETCH: the interpolated row of sp goes to LDS as its logarithm and is stretched by the frame's ratio with the expressions of
-//     stretch_kernel (wc_io.hip) before its one write.
+//     STRETCH: the interpolated row of sp goes to LDS as its logarithm and is stretched by the frame's ratio (wc::stretched_bin,
+//     wc_stretch.hpp: the rule of stretch_kernel, wc_io.hip) before its one write.
 //   The workgroup finds its utterance by bisection in the descriptors, which go up through page-locked staging kept per
 //   (device, stream): a call only enqueues.
 #include <hip/hip_runtime.h>
@@ -28,7 +28,6 @@ using namespace wc;
 
 namespace {
 
-constexpr int RT_MAX_BINS = 4096 / 2 + 1;
 constexpr int RT_T = 256;
 
 struct RtUtt {
@@ -120,7 +119,7 @@ __global__ __launch_bounds__(RT_T) void retime_kernel(RtArgs A) {
 		return;
 	}
 	if constexpr (STRETCH) {
-		__shared__ double lg[RT_MAX_BINS];
+		__shared__ double lg[kMaxBins];
 		__shared__ double fill;
 		for (int t = tid; t < bins / 2; t += RT_T) {
 			const d2u x = rt_pair(ri, rj, w0, a, 2 * t);
@@ -129,21 +128,11 @@ __global__ __launch_bounds__(RT_T) void retime_kernel(RtArgs A) {
 		}
 		if (tid == 0) lg[bins - 1] = log(rt_one(ri, rj, w0, a, bins - 1));
 		__syncthreads();
-		// stretch_kernel's expressions (wc_io.hip; reference test/test.cpp:222-240, interp1 with histc's clamp)
-		const int fft_size = A.fft_size, fs = A.fs;
-		auto axis1 = [&](int q) { return ratio * q / fft_size * fs; };
+		const int fft_size = A.fft_size;
 		const int cut = static_cast<int>(fft_size / 2.0 * ratio);  // >= 1 for a valid ratio
 		const int top = ratio < 1.0 ? cut : bins;                 // bins from `cut` upward repeat bin cut - 1
 		for (int b = tid; b < top; b += RT_T) {
-			const double xi = static_cast<double>(b) / fft_size * fs;
-			int c = static_cast<int>(b / ratio) + 1;
-			c = c < 0 ? 0 : (c > bins ? bins : c);
-			while (c < bins && axis1(c) <= xi) ++c;
-			while (c > 0 && !(axis1(c - 1) <= xi)) --c;
-			const int k = c < 1 ? 1 : (c > bins - 1 ? bins - 1 : c);
-			const double x0 = axis1(k - 1), x1 = axis1(k);
-			const double s = (xi - x0) / (x1 - x0);
-			const double v = exp(lg[k - 1] + s * (lg[k] - lg[k - 1]));
+			const double v = stretched_bin(b, ratio, A.fs, fft_size, [&](int k) { return lg[k]; });
 			out[b] = v;
 			if (b == top - 1) fill = v;
 		}
@@ -163,7 +152,7 @@ std::map<std::pair<int, hipStream_t>, Staging *> g_stage;
 }  // namespace
 
 const char *wc::retime_check(int fs, int fft_size, int n_utt, const int *in_length, const int *out_length, long long *total_out) {
-	if (!(fft_size == 512 || fft_size == 1024 || fft_size == 2048 || fft_size == 4096)) return "retime: fft_size must be 512, 1024, 2048 or 4096";
+	if (!fft_size_supported(fft_size)) return "retime: fft_size must be 512, 1024, 2048 or 4096";
 	if (fs <= 0) return "retime: fs must be positive";
 	if (n_utt < 0) return "retime: negative n_utt";
 	if (n_utt > 0 && (!in_length || !out_length)) return "retime: null length array";

@@ -5,6 +5,10 @@
 #include <vector>
 
 #include "wc_internal.hpp"
+#include "wc_stretch.hpp"
+
+// the transform sizes of CheapTrick, Synthesis, the codec and the row calls
+inline bool fft_size_supported(int fft_size) { return fft_size == 512 || fft_size == 1024 || fft_size == 2048 || fft_size == 4096; }
 
 // part: 3 = the whole chain, 1 = its front only, 2 = the tail behind a front that an earlier call with the same arguments enqueued;
 // bp_done: recorded behind the band-pass; tail_after: the tail waits for it
@@ -52,18 +56,40 @@ wc::Device *syn_device(const wc_synthesis *sy);
 const double *syn_dc_remover(const wc_synthesis *sy);  // getDCRemover's table on the device (reference src/synthesis.cpp:290-303)
 int syn_fs(const wc_synthesis *sy);
 
-// Feature decoding for Synthesis from coded features (wc_codec.hip, wc_synth_coded.hip)
+// The feature codec's plans (wc_codec.hip) and feature decoding for Synthesis from coded features (wc_synth_coded.hip)
 namespace wc {
-// GetParametersForDecoding (reference src/codec.cpp:144-166): the interp1 plan (k, s) from the mel axis onto bins 0 .. fft_size/2
-// and the IDCT weights of the first nd coefficients (the rest 0)
-void codec_decode_sp_plan(int fs, int fft_size, int nd, std::vector<int> &k, std::vector<double> &s, std::vector<double2> &w);
+struct CodecPlanArgs {  // what a kernel takes: segment indices (1-based) and fractions of an interp1 between two fixed axes, DCT weights
+	const int *k;
+	const double *s;
+	const double2 *w;
+};
+// One direction's plan of (device, fs, fft_size) on the device.  Coding (GetParametersForCoding, reference src/codec.cpp:125-142):
+// k, s from bins 0 .. fft_size/2 (in mel) onto the fft_size/2 points of the mel axis, the DCT weights w, and at fft_size 2048 / 4096
+// k, s once more in the one-wavefront coder's order (kp, sp).  Decoding (GetParametersForDecoding, :144-166): k, s from the mel axis
+// onto bins 0 .. fft_size/2 and all fft_size/2 IDCT weights.
+struct CodecPlan {
+	DevBuf k, s, w, kp, sp;
+	CodecPlanArgs args() const { return {k.as<int>(), s.as<double>(), w.as<double2>()}; }
+	CodecPlanArgs wave_args() const { return {kp.as<int>(), sp.as<double>(), w.as<double2>()}; }
+};
+// the plan of (dev, fs, fft_size, coding), built and uploaded on first use (the only step of a codec call that allocates or waits)
+// and kept for the life of the process; a failure leaves no entry behind
+int codec_plan(Device *dev, int fs, int fft_size, bool coding, const CodecPlan **out);
+// the codec's workgroup-per-frame kernels enqueued on st (arguments already checked)
+int codec_code_sp_launch(Device *dev, hipStream_t st, int fft_size, long long n_frames, int nd, const double *d_sp, double *d_coded,
+						 const CodecPlan &pl);
+int codec_decode_sp_launch(Device *dev, hipStream_t st, int fft_size, long long n_frames, int nd, const double *d_coded, double *d_sp,
+						   const CodecPlan &pl);
+int codec_code_ap_launch(hipStream_t st, int fs, int fft_size, long long n_frames, const double *d_ap, double *d_coded);
+int codec_decode_ap_launch(hipStream_t st, int fs, int fft_size, long long n_frames, const double *d_coded, double *d_ap);
+
 // nullptr if (fs, fft_size, nd) can be decoded, else why not: fft_size 512 .. 4096, 1 <= nd <= fft_size/2, fs >= 12 kHz (at
 // least one aperiodicity band)
 const char *decode_features_check(int fs, int fft_size, int nd);
-// Both coded rows of n_frames frames -> rows of fft_size/2+1 doubles (arguments already checked).  fft_size 2048: the one-wavefront
-// kernel, enqueued on s; other sizes: the codec's workgroup-per-frame kernels (wc_decode_*_device) on dev's active stream (s is that
-// stream).  d_spectral_ratio (per frame, or nullptr): the rows of d_sp stretched as by modify_frames_enqueue -- inside the
-// one-wavefront kernel at fft_size 2048, by that call behind the decoders at the other sizes.
+// Both coded rows of n_frames frames -> rows of fft_size/2+1 doubles, enqueued on s at every size (arguments already checked): the
+// one-wavefront kernel at fft_size 2048, the codec's workgroup-per-frame kernels at the others, either on the cached plan.
+// d_spectral_ratio (per frame, or nullptr): the rows of d_sp stretched as by modify_frames_enqueue -- inside the one-wavefront kernel
+// at fft_size 2048, by that call behind the decoders at the other sizes.
 int decode_features_enqueue(Device *dev, hipStream_t s, int fs, int fft_size, long long n_frames, int nd, const double *d_coded_sp,
 							const double *d_coded_ap, const double *d_spectral_ratio, double *d_sp, double *d_ap);
 
@@ -71,10 +97,6 @@ int decode_features_enqueue(Device *dev, hipStream_t s, int fs, int fft_size, lo
 // d_spectral_ratio[i]; any pointer may be nullptr
 int modify_frames_enqueue(hipStream_t s, int fs, int fft_size, long long n_frames, double *d_f0, double *d_sp, const double *d_f0_scale,
 						  const double *d_spectral_ratio);
-// what a frame's spectral ratio must be to stretch its row (0 = leave it is tested before): finite and cut = int(fft_size / 2 * ratio) >= 1
-__host__ __device__ inline bool frame_ratio_valid(double ratio, int fft_size) {
-	return ratio >= 2.0 / fft_size && ratio <= 1.7976931348623157e308;
-}
 
 // Time-scale modification (wc_retime.hip).  retime_check: nullptr if wc_retime_parameters_device takes the sizes and the lengths, else
 // why not; the output frames of the batch come back.  retime_enqueue: the arguments already checked, the descriptors staged and the
@@ -84,14 +106,7 @@ int retime_enqueue(Device *dev, hipStream_t s, int fs, int fft_size, int n_utt, 
 				   const double *d_sp_in, const double *d_ap_in, const int *out_length, const double *d_position, const double *d_f0_scale,
 				   const double *d_spectral_ratio, double *d_f0_out, double *d_sp_out, double *d_ap_out, long long total_out);
 
-// Feature coding (wc_codec.hip, wc_code_features.hip)
-// GetParametersForCoding (reference src/codec.cpp:125-142): the interp1 plan (k, s) from bins 0 .. fft_size/2 (in mel) onto the
-// fft_size/2 points of the mel axis and the DCT weights
-void codec_code_sp_plan(int fs, int fft_size, std::vector<int> &k, std::vector<double> &s, std::vector<double2> &w);
-// code_sp_kernel / code_ap_kernel enqueued on st with a plan that already lives on the device (arguments already checked)
-int codec_code_sp_launch(Device *dev, hipStream_t st, int fft_size, long long n_frames, int nd, const double *d_sp, double *d_coded,
-						 const int *d_k, const double *d_s, const double2 *d_w);
-int codec_code_ap_launch(hipStream_t st, int fs, int fft_size, long long n_frames, const double *d_ap, double *d_coded);
+// Feature coding (wc_code_features.hip)
 // nullptr if (fs, fft_size, nd) can be coded, else why not: fft_size 512 .. 4096, 1 <= nd <= fft_size/4+1, and with the
 // aperiodicity fs >= 12 kHz (at least one band)
 const char *code_features_check(int fs, int fft_size, int nd, bool with_ap);

@@ -7,18 +7,16 @@
 //       1024 points held in registers (wf_fft1024_dit, wc_wavefft.hpp; pruned first stage when nd <= 256) -> the even/odd
 //       interleave onto the mel axis in LDS -> interp1 onto the linear axis -> exp
 //     aperiodicity (:19-40, :238-267): voiced/unvoiced test on the band mean -> interp1 at 3 kHz multiples -> 10^(v/20)
-//   The arithmetic of the codec's decode_sp_kernel / decode_ap_kernel (wc_codec.hip) with the plan of wc::codec_decode_sp_plan,
-//   except for the FFT's order of operations and 10^(v/20) as one exp: the rows differ from theirs in the last bits only.  The
-//   kernel is bound by its FP64 transcendentals (an exp per bin of either row), so the second stage's twiddles sit in LDS: 162
-//   VGPRs, 3 waves per SIMD.  Other fft sizes take those workgroup-per-frame kernels.
+//   The arithmetic of the codec's decode_sp_kernel / decode_ap_kernel (wc_codec.hip) on the same plan (wc::codec_plan) and the same
+//   band-aperiodicity row (wc_stretch.hpp), except for the FFT's order of operations and 10^(v/20) as one exp: the rows differ from
+//   theirs in the last bits only.  The kernel is bound by its FP64 transcendentals (an exp per bin of either row), so the second
+//   stage's twiddles sit in LDS: 162 VGPRs, 3 waves per SIMD.  Other fft sizes take those workgroup-per-frame kernels, enqueued
+//   on the same stream through the codec's launch helpers.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdlib>
-#include <map>
-#include <mutex>
 #include <string>
-#include <vector>
 
 #include "../../include/world_class_c.h"
 #include "../../include/world_class_codec.h"
@@ -29,23 +27,16 @@ using namespace wc;
 
 namespace {
 
-constexpr double kFrequencyInterval = 3000.0, kSafeGuard = 0.000000000001;  // world_constantnumbers.hpp
-constexpr double kLn10By20 = 0.11512925464970228420;                         // ln(10) / 20
+constexpr double kLn10By20 = 0.11512925464970228420;  // ln(10) / 20
 
-struct DecPlan {
-	const int *k;        // 1025 segment indices (1-based) on the mel axis
-	const double *s;     // 1025 fractions
-	const double2 *w;    // 1024 IDCT weights
-};
-
-// MOD: the frame's row of sp stretched by rat[frame] (wc_decode_features_modified_device), the arithmetic of stretch_kernel
-// (wc_io.hip) on the log envelope the mel row holds before the exp: the interpolation from the mel axis and the one along the
-// stretched axis are both piecewise linear, so a bin takes the mel row's value at the two ends of its segment, interpolates and
-// takes the one exp.  ratio 0: the unmodified expression; a ratio stretch_kernel<true> would refuse: NaN.
+// MOD: the frame's row of sp stretched by rat[frame] (wc_decode_features_modified_device), the rule of stretch_kernel
+// (wc::stretched_bin, wc_stretch.hpp) on the log envelope the mel row holds before the exp: the interpolation from the mel axis and
+// the one along the stretched axis are both piecewise linear, so a bin takes the mel row's value at the two ends of its segment,
+// interpolates and takes the one exp.  ratio 0: the unmodified expression; a ratio stretch_kernel<true> would refuse: NaN.
 template <bool MOD>
 __global__ __launch_bounds__(64) void decode_features_wave_kernel(const double *__restrict__ csp, const double *__restrict__ cap,
 																  double *__restrict__ sp, double *__restrict__ ap, int nd, int n_ap,
-																  int fs, DecPlan p, const double2 *__restrict__ tw,
+																  int fs, CodecPlanArgs p, const double2 *__restrict__ tw,
 																  const double *__restrict__ rat) {
 	constexpr int MD = 1024, BINS = MD + 1, FFT = 2 * MD;
 	__shared__ double L[kWfLds];  // the transform's exchange buffer, then the mel-axis row mel[0 .. MD + 1]
@@ -99,24 +90,14 @@ __global__ __launch_bounds__(64) void decode_features_wave_kernel(const double *
 		} else if (!frame_ratio_valid(ratio, FFT)) {
 			for (int j = lane; j < BINS; j += 64) row[j] = __builtin_nan("");
 		} else {
-			auto axis1 = [&](int j) { return ratio * j / FFT * fs; };  // reference test/test.cpp:222
-			auto mel = [&](int b) {  // MD x the unstretched log envelope at bin b
+			auto mel = [&](int b) {  // the unstretched log envelope at bin b
 				const int k = p.k[b];
-				return L[k - 1] + p.s[b] * (L[k] - L[k - 1]);
+				return (L[k - 1] + p.s[b] * (L[k] - L[k - 1])) / MD;
 			};
 			const int cut = static_cast<int>(FFT / 2.0 * ratio);  // >= 1 for a valid ratio
 			for (int j = lane; j < BINS; j += 64) {
 				const int i = (ratio < 1.0 && j >= cut) ? cut - 1 : j;  // bins from `cut` upward repeat bin cut - 1 (reference :236-240)
-				const double xi = static_cast<double>(i) / FFT * fs;
-				int c = static_cast<int>(i / ratio) + 1;
-				c = c < 0 ? 0 : (c > BINS ? BINS : c);
-				while (c < BINS && axis1(c) <= xi) ++c;
-				while (c > 0 && !(axis1(c - 1) <= xi)) --c;
-				const int k = c < 1 ? 1 : (c > BINS - 1 ? BINS - 1 : c);
-				const double x0 = axis1(k - 1), x1 = axis1(k);
-				const double s = (xi - x0) / (x1 - x0);
-				const double a = mel(k - 1) / MD, b = mel(k) / MD;
-				row[j] = exp(a + s * (b - a));
+				row[j] = stretched_bin(i, ratio, fs, std::integral_constant<int, FFT>(), mel);
 			}
 		}
 	}
@@ -124,70 +105,18 @@ __global__ __launch_bounds__(64) void decode_features_wave_kernel(const double *
 	// ---- aperiodicity ----
 	const double *__restrict__ c = cap + f * n_ap;
 	double *__restrict__ row = ap + f * BINS;
-	double tmp = 0.0;
-	for (int i = 0; i < n_ap; ++i) tmp += c[i];
-	tmp /= n_ap;
-	if (tmp > -0.5) {  // CheckVUV: treated as unvoiced, the initial value stays
+	if (coded_ap_unvoiced(c, n_ap)) {
 		for (int j = lane; j < BINS; j += 64) row[j] = 1.0 - kSafeGuard;
 		return;
 	}
-	const int na = n_ap + 2;
-	auto axis = [&](int q) { return q == na - 1 ? fs / 2.0 : q * kFrequencyInterval; };
-	auto val = [&](int q) { return q == 0 ? -60.0 : (q == na - 1 ? -kSafeGuard : c[q - 1]); };
-	for (int j = lane; j < BINS; j += 64) {
-		const double fj = static_cast<double>(fs) / FFT * j;
-		int k = 1;  // histc: clamp(#{q : axis(q) <= f}, 1, na - 1)
-		while (k < na && fj >= axis(k)) ++k;
-		k = k < na - 1 ? k : na - 1;
-		const double x0 = axis(k - 1), x1 = axis(k);
-		const double s = (fj - x0) / (x1 - x0);
-		const double v = val(k - 1) + s * (val(k) - val(k - 1));
-		row[j] = exp(v * kLn10By20);  // 10^(v/20): one exp instead of pow's log + exp (within 1e-15 of it: ap <= 1, |v| <= 60)
-	}
-}
-
-// The plan of fft_size 2048 per (device, fs), built and uploaded on first use and kept for the life of the process (28 KB each):
-// a call then only enqueues.
-struct WavePlan {
-	DevBuf k, s, w;
-};
-std::mutex g_plan_mu;
-std::map<std::pair<int, int>, WavePlan *> g_plans;
-
-int wave_plan(Device *dev, int fs, DecPlan *out) {
-	std::lock_guard<std::mutex> g(g_plan_mu);
-	WavePlan *&pl = g_plans[{dev->id, fs}];
-	if (!pl) {
-		std::vector<int> k;
-		std::vector<double> s;
-		std::vector<double2> w;
-		codec_decode_sp_plan(fs, 2048, 1024, k, s, w);  // all weights: the kernel drops the coefficients beyond nd
-		WavePlan *n = new WavePlan();
-		int rc = n->k.reserve(sizeof(int) * k.size());
-		if (!rc) rc = n->s.reserve(sizeof(double) * s.size());
-		if (!rc) rc = n->w.reserve(sizeof(double2) * w.size());
-		hipError_t e = hipSuccess;
-		if (!rc) e = hipMemcpy(n->k.p, k.data(), sizeof(int) * k.size(), hipMemcpyHostToDevice);
-		if (!rc && e == hipSuccess) e = hipMemcpy(n->s.p, s.data(), sizeof(double) * s.size(), hipMemcpyHostToDevice);
-		if (!rc && e == hipSuccess) e = hipMemcpy(n->w.p, w.data(), sizeof(double2) * w.size(), hipMemcpyHostToDevice);
-		if (!rc && e != hipSuccess) rc = fail(WC_ERR_DEVICE, std::string("decode_features: plan upload: ") + hipGetErrorString(e));
-		if (rc) {
-			n->k.release(); n->s.release(); n->w.release();
-			delete n;
-			return rc;
-		}
-		pl = n;
-	}
-	out->k = pl->k.as<int>();
-	out->s = pl->s.as<double>();
-	out->w = pl->w.as<double2>();
-	return WC_OK;
+	// 10^(v/20): one exp instead of pow's log + exp (within 1e-15 of it: ap <= 1, |v| <= 60)
+	for (int j = lane; j < BINS; j += 64) row[j] = exp(coded_ap_db(c, n_ap, fs, FFT, j) * kLn10By20);
 }
 
 }  // namespace
 
 const char *wc::decode_features_check(int fs, int fft_size, int nd) {
-	if (!(fft_size == 512 || fft_size == 1024 || fft_size == 2048 || fft_size == 4096)) return "decode_features: fft_size must be 512, 1024, 2048 or 4096";
+	if (!fft_size_supported(fft_size)) return "decode_features: fft_size must be 512, 1024, 2048 or 4096";
 	if (nd < 1 || nd > fft_size / 2) return "decode_features: number_of_dimensions must be 1 .. fft_size/2";
 	if (fs <= 0 || GetNumberOfAperiodicities(fs) < 1) return "decode_features: fs must be at least 12 kHz (no aperiodicity band below)";
 	return nullptr;
@@ -196,25 +125,27 @@ const char *wc::decode_features_check(int fs, int fft_size, int nd) {
 int wc::decode_features_enqueue(Device *dev, hipStream_t s, int fs, int fft_size, long long n_frames, int nd, const double *d_coded_sp,
 								const double *d_coded_ap, const double *d_spectral_ratio, double *d_sp, double *d_ap) {
 	if (n_frames == 0) return WC_OK;
+	const CodecPlan *pl;
 	int rc;
+	if ((rc = codec_plan(dev, fs, fft_size, false, &pl))) return rc;
 	// WC_DECODE_MOD=route: the stretch as a pass of its own behind the one-wavefront decoder (the measurement of DESIGN.md section 10)
 	static const bool route_mod = [] { const char *e = getenv("WC_DECODE_MOD"); return e && std::string(e) == "route"; }();
 	if (fft_size == 2048) {
-		DecPlan p;
-		if ((rc = wave_plan(dev, fs, &p))) return rc;
+		const dim3 grid((unsigned)n_frames), block(64);
+		const int n_ap = GetNumberOfAperiodicities(fs);
+		const double2 *tw = (const double2 *)dev->twiddle;
 		if (d_spectral_ratio && !route_mod) {
-			hipLaunchKernelGGL(decode_features_wave_kernel<true>, dim3((unsigned)n_frames), dim3(64), 0, s, d_coded_sp, d_coded_ap, d_sp, d_ap, nd,
-							   GetNumberOfAperiodicities(fs), fs, p, (const double2 *)dev->twiddle, d_spectral_ratio);
+			hipLaunchKernelGGL(decode_features_wave_kernel<true>, grid, block, 0, s, d_coded_sp, d_coded_ap, d_sp, d_ap, nd, n_ap, fs, pl->args(), tw,
+							   d_spectral_ratio);
 			WC_HIP(hipGetLastError());
 			return WC_OK;
 		}
-		hipLaunchKernelGGL(decode_features_wave_kernel<false>, dim3((unsigned)n_frames), dim3(64), 0, s, d_coded_sp, d_coded_ap, d_sp, d_ap, nd,
-						   GetNumberOfAperiodicities(fs), fs, p, (const double2 *)dev->twiddle, (const double *)nullptr);
+		hipLaunchKernelGGL(decode_features_wave_kernel<false>, grid, block, 0, s, d_coded_sp, d_coded_ap, d_sp, d_ap, nd, n_ap, fs, pl->args(), tw,
+						   (const double *)nullptr);
 		WC_HIP(hipGetLastError());
 	} else {
-		OnDeviceOf here(dev);  // (the codec's entry points run on the calling thread's device)
-		if ((rc = wc_decode_spectral_envelope_device(fs, fft_size, n_frames, nd, d_coded_sp, d_sp))) return rc;
-		if ((rc = wc_decode_aperiodicity_device(fs, fft_size, n_frames, d_coded_ap, d_ap))) return rc;
+		if ((rc = codec_decode_sp_launch(dev, s, fft_size, n_frames, nd, d_coded_sp, d_sp, *pl))) return rc;
+		if ((rc = codec_decode_ap_launch(s, fs, fft_size, n_frames, d_coded_ap, d_ap))) return rc;
 	}
 	return d_spectral_ratio ? modify_frames_enqueue(s, fs, fft_size, n_frames, nullptr, d_sp, nullptr, d_spectral_ratio) : WC_OK;
 }

@@ -2229,7 +2229,7 @@ extern "C" {
 
 wc_synthesis *wc_synthesis_create(int fs, int fft_size, double frame_period_ms) {
 	if (fs <= 0 || frame_period_ms <= 0) { set_error("synthesis: fs and frame_period must be positive"); return nullptr; }
-	if (fft_size != 512 && fft_size != 1024 && fft_size != 2048 && fft_size != 4096) {
+	if (!fft_size_supported(fft_size)) {
 		set_error("synthesis: fft_size must be 512, 1024, 2048 or 4096");
 		return nullptr;
 	}
@@ -2298,31 +2298,49 @@ int wc_synthesis_compute_device(wc_synthesis *s, int n_utt, const double *d_f0, 
 	return syn_run_device(s, n_utt, d_f0, f0_length, d_sp, d_ap, out_length, d_out, rng_pos);
 }
 
-// Synthesis from coded features: the rows are decoded into the handle's dec_sp / dec_ap on the caller's stream, and the batch runs
-// on them as in wc_synthesis_compute_device.  (Decoding on a side stream beside the time base measured no faster: DESIGN.md
-// section 10.)  d_spectral_ratio: per frame, packed like d_f0, or NULL (wc_decode_features_modified_device).
+// The front of the coded entry points behind their null checks: sizes and lengths (a refused call enqueues nothing), the device
+// lock, the handle's decoded rows -- with frames_out (the retimed call) the retimed ones too, `total` output frames -- and the decode
+// on the caller's stream.  d_spectral_ratio: per frame, packed like d_f0, or NULL (wc_decode_features_modified_device).
+static int syn_coded_front(wc_synthesis *s, int n_utt, const int *f0_length, const int *frames_out, const int *out_length,
+						   int number_of_dimensions, const double *d_coded_sp, const double *d_coded_ap, const double *d_spectral_ratio,
+						   std::unique_lock<std::recursive_mutex> &lock, long long *total) {
+	if (const char *why = decode_features_check(s->fs, s->fft_size, number_of_dimensions)) return fail(WC_ERR_INVALID, why);
+	long long frames = 0;
+	for (int u = 0; u < n_utt; ++u) {  // (checked here too: a refused call enqueues nothing)
+		if (f0_length[u] < 2 || (frames_out && frames_out[u] < 2))
+			return fail(WC_ERR_INVALID, frames_out ? "synthesis: f0_length and frames_out must be at least 2 (reference src/synthesis.cpp:241-242)"
+												   : "synthesis: f0_length must be at least 2 (reference src/synthesis.cpp:241-242)");
+		if (out_length[u] < 0) return fail(WC_ERR_INVALID, "synthesis: negative out_length");
+		frames += f0_length[u];
+	}
+	if (frames_out)
+		if (const char *why = retime_check(s->fs, s->fft_size, n_utt, f0_length, frames_out, total)) return fail(WC_ERR_INVALID, why);
+	WC_HIP(hipSetDevice(s->dev->id));
+	lock = std::unique_lock<std::recursive_mutex>(s->dev->mu);
+	const size_t row = sizeof(double) * (size_t)(s->fft_size / 2 + 1);
+	int rc;
+	if ((rc = s->dec_sp.reserve(row * frames))) return rc;
+	if ((rc = s->dec_ap.reserve(row * frames))) return rc;
+	if (frames_out) {
+		if ((rc = s->rt_sp.reserve(row * *total))) return rc;
+		if ((rc = s->rt_ap.reserve(row * *total))) return rc;
+		if ((rc = s->rt_f0.reserve(sizeof(double) * *total))) return rc;
+	}
+	return decode_features_enqueue(s->dev, s->dev->active(), s->fs, s->fft_size, frames, number_of_dimensions, d_coded_sp, d_coded_ap,
+								   d_spectral_ratio, s->dec_sp.as<double>(), s->dec_ap.as<double>());
+}
+
+// Synthesis from coded features: the batch runs on the decoded rows as in wc_synthesis_compute_device.  (Decoding on a side stream
+// beside the time base measured no faster: DESIGN.md section 10.)
 int wc_synthesis_compute_coded_modified_device(wc_synthesis *s, int n_utt, const double *d_f0, const int *f0_length, const double *d_coded_sp,
 											   int number_of_dimensions, const double *d_coded_ap, const double *d_spectral_ratio,
 											   const int *out_length, double *d_out, uint64_t *rng_pos) {
 	if (!s || n_utt <= 0 || !d_f0 || !f0_length || !d_coded_sp || !d_coded_ap || !out_length || !d_out)
 		return fail(WC_ERR_INVALID, "synthesis coded: null argument");
-	if (const char *why = decode_features_check(s->fs, s->fft_size, number_of_dimensions)) return fail(WC_ERR_INVALID, why);
-	long long frames = 0;
-	for (int u = 0; u < n_utt; ++u) {  // (checked here too: a refused call enqueues nothing)
-		if (f0_length[u] < 2) return fail(WC_ERR_INVALID, "synthesis: f0_length must be at least 2 (reference src/synthesis.cpp:241-242)");
-		if (out_length[u] < 0) return fail(WC_ERR_INVALID, "synthesis: negative out_length");
-		frames += f0_length[u];
-	}
-	WC_HIP(hipSetDevice(s->dev->id));
-	DeviceLock lock(s->dev);
-	const size_t rows = sizeof(double) * (size_t)frames * (s->fft_size / 2 + 1);
-	int rc;
-	if ((rc = s->dec_sp.reserve(rows))) return rc;
-	if ((rc = s->dec_ap.reserve(rows))) return rc;
-	double *d_sp = s->dec_sp.as<double>(), *d_ap = s->dec_ap.as<double>();
-	if ((rc = decode_features_enqueue(s->dev, s->dev->active(), s->fs, s->fft_size, frames, number_of_dimensions, d_coded_sp, d_coded_ap,
-									  d_spectral_ratio, d_sp, d_ap))) return rc;
-	return syn_run_device(s, n_utt, d_f0, f0_length, d_sp, d_ap, out_length, d_out, rng_pos);
+	std::unique_lock<std::recursive_mutex> lock;
+	if (int rc = syn_coded_front(s, n_utt, f0_length, nullptr, out_length, number_of_dimensions, d_coded_sp, d_coded_ap, d_spectral_ratio, lock,
+								 nullptr)) return rc;
+	return syn_run_device(s, n_utt, d_f0, f0_length, s->dec_sp.as<double>(), s->dec_ap.as<double>(), out_length, d_out, rng_pos);
 }
 
 int wc_synthesis_compute_coded_device(wc_synthesis *s, int n_utt, const double *d_f0, const int *f0_length, const double *d_coded_sp,
@@ -2339,31 +2357,14 @@ int wc_synthesis_compute_coded_retimed_device(wc_synthesis *s, int n_utt, const 
 											  const int *out_length, double *d_out, uint64_t *rng_pos) {
 	if (!s || n_utt <= 0 || !d_f0 || !f0_length || !d_coded_sp || !d_coded_ap || !frames_out || !d_position || !out_length || !d_out)
 		return fail(WC_ERR_INVALID, "synthesis coded retimed: null argument");
-	if (const char *why = decode_features_check(s->fs, s->fft_size, number_of_dimensions)) return fail(WC_ERR_INVALID, why);
-	for (int u = 0; u < n_utt; ++u) {  // (checked here too: a refused call enqueues nothing)
-		if (f0_length[u] < 2 || frames_out[u] < 2)
-			return fail(WC_ERR_INVALID, "synthesis: f0_length and frames_out must be at least 2 (reference src/synthesis.cpp:241-242)");
-		if (out_length[u] < 0) return fail(WC_ERR_INVALID, "synthesis: negative out_length");
-	}
-	long long frames = 0, total = 0;
-	for (int u = 0; u < n_utt; ++u) frames += f0_length[u];
-	if (const char *why = retime_check(s->fs, s->fft_size, n_utt, f0_length, frames_out, &total)) return fail(WC_ERR_INVALID, why);
-	WC_HIP(hipSetDevice(s->dev->id));
-	DeviceLock lock(s->dev);
-	const size_t row = sizeof(double) * (size_t)(s->fft_size / 2 + 1);
+	std::unique_lock<std::recursive_mutex> lock;
+	long long total = 0;
 	int rc;
-	if ((rc = s->dec_sp.reserve(row * frames))) return rc;
-	if ((rc = s->dec_ap.reserve(row * frames))) return rc;
-	if ((rc = s->rt_sp.reserve(row * total))) return rc;
-	if ((rc = s->rt_ap.reserve(row * total))) return rc;
-	if ((rc = s->rt_f0.reserve(sizeof(double) * total))) return rc;
-	double *d_sp = s->dec_sp.as<double>(), *d_ap = s->dec_ap.as<double>();
-	double *r_f0 = s->rt_f0.as<double>(), *r_sp = s->rt_sp.as<double>(), *r_ap = s->rt_ap.as<double>();
-	hipStream_t st = s->dev->active();
-	if ((rc = decode_features_enqueue(s->dev, st, s->fs, s->fft_size, frames, number_of_dimensions, d_coded_sp, d_coded_ap, nullptr, d_sp, d_ap)))
+	if ((rc = syn_coded_front(s, n_utt, f0_length, frames_out, out_length, number_of_dimensions, d_coded_sp, d_coded_ap, nullptr, lock, &total)))
 		return rc;
-	if ((rc = retime_enqueue(s->dev, st, s->fs, s->fft_size, n_utt, f0_length, d_f0, d_sp, d_ap, frames_out, d_position, d_f0_scale,
-							 d_spectral_ratio, r_f0, r_sp, r_ap, total))) return rc;
+	double *r_f0 = s->rt_f0.as<double>(), *r_sp = s->rt_sp.as<double>(), *r_ap = s->rt_ap.as<double>();
+	if ((rc = retime_enqueue(s->dev, s->dev->active(), s->fs, s->fft_size, n_utt, f0_length, d_f0, s->dec_sp.as<double>(), s->dec_ap.as<double>(),
+							 frames_out, d_position, d_f0_scale, d_spectral_ratio, r_f0, r_sp, r_ap, total))) return rc;
 	return syn_run_device(s, n_utt, r_f0, frames_out, r_sp, r_ap, out_length, d_out, rng_pos);
 }
 

@@ -4,7 +4,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import WorldClassError, _c, _check, _ptr, lib
+from . import WorldClassError, _c, _check, _opt, _ptr, lib
 
 _dp = C.POINTER(C.c_double)
 _i16p = C.POINTER(C.c_int16)
@@ -152,10 +152,6 @@ def modify_parameters_device(fs, fft_size, n_frames, d_f0, d_sp, f0_scale=1.0, s
     """reference test/test.cpp:201-243 on device-resident parameters (0 = leave the spectra alone)"""
     _check(_io().wc_modify_parameters_device(int(fs), int(fft_size), int(n_frames), _ptr(d_f0), _ptr(d_sp), float(f0_scale),
                                              float(spectral_ratio)))
-
-
-def _opt(obj):
-    return None if obj is None else _ptr(obj)
 
 
 def modify_parameters_frames_device(fs, fft_size, n_frames, d_f0, d_sp, d_f0_scale=None, d_spectral_ratio=None):
