@@ -170,6 +170,62 @@ int wc_synth_stream_push_coded_device(wc_synth_stream *s, const int *n_frames, c
  * wc_synth_stream_push_device takes full rows as they are and applies no setting: while a stream that receives frames in that
  * push has a setting other than (1.0, 0.0) the push is refused and every stream keeps its state. */
 int wc_synth_stream_set_modification(wc_synth_stream *s, int stream, double f0_scale, double spectral_ratio);
+/* Speed of one stream (time-scale modification, the streaming form of wc_retime_parameters_device and
+ * wc_synthesis_compute_coded_retimed_device), a host-side setting like wc_synth_stream_set_modification: 1.0 after
+ * wc_synth_stream_create and wc_synth_stream_reset; refused with WC_ERR_INVALID, the setting unchanged, unless it is finite and > 0
+ * (and, for a retimed stream, unless floor(last + speed) >= F - 1: below).
+ * The frames a caller pushes are SOURCE frames; what the stream synthesises are SYNTHESIS frames, formed along the time map
+ *   pos[0] = 0,  pos[k] = pos[k-1] + speed_k   (one double addition, speed_k the speed in effect at the push that forms frame k),
+ * cut at F - 1 for F source frames received.  A push that gives the stream n source frames makes F += n and then forms, one after
+ * the other, every frame whose position p = last + speed (0.0 for the first) satisfies p <= F - 1 -- the condition that source
+ * rows floor(p) and, for a fractional p, floor(p) + 1 are in; nothing formed is ever revised, a flush forms nothing extra (positions
+ * beyond F - 1 are dropped, the end frame is not held).  The frame at p is wc_retime_parameters_device's frame at that position,
+ * bit for bit: i = floor(p), a = p - i; a == 0 copies source frame i, a > 0 writes (1 - a) * row[i] + a * row[i + 1] for both rows
+ * with that call's voiced / unvoiced F0 rule; then f0 *= f0_scale and the sp row is stretched by the stream's spectral_ratio
+ * (wc_synth_stream_set_modification, coded pushes), per synthesis frame as in wc_synthesis_compute_coded_retimed_device.  The frames
+ * formed are appended to the stream as wc_synth_stream_push_device appends rows: the samples are those of ONE
+ * wc_synthesis_compute_coded_retimed_device (coded pushes) or wc_retime_parameters_device + wc_synthesis_compute_device (full rows)
+ * call over all source frames with the stream's positions, and the commit rule, the noise draws and the latency bound above hold
+ * in synthesis frames; in source frames a stream waits at most one frame longer, for frame ceil(p).
+ * Which streams are retimed: a stream becomes retimed at the first push that gives it frames while its speed is not 1.0 and stays
+ * so until wc_synth_stream_reset, also after the speed returns to 1.0.  A retimed stream in a coded push is decoded by the unmodified
+ * decoder, scale and ratio applied per synthesis frame behind the interpolation; wc_synth_stream_push_device takes full rows for it
+ * (retimed without scale or ratio; a stream with a modification setting is still refused there).  A stream that is not retimed is
+ * handled as without this setting whatever its neighbours do (in a coded push its ratio goes into the decoder; beside retimed streams
+ * its rows pass the retiming kernel at whole positions, a copy), no stream's samples depend on another stream's settings, and a
+ * push in which no stream that receives frames is retimed runs the code it ran before: no extra launch, copy or allocation (but
+ * for the kept coded frame of streams with a modification setting that called this function, below).
+ * Per retimed stream the handle carries `last`, F and ONE source row (frame F - 1: after a push the next position lies beyond
+ * F - 2); the carried rows are a ping-pong pair, the retimed rows (max_frames_per_push x n_streams, both matrices and F0) and the
+ * page-locked staging of descriptors, positions, scales and ratios are reserved on the first retimed push and released by
+ * wc_synth_stream_destroy.  Two things follow from the one carried row.  A stream that becomes retimed after frames at speed 1.0
+ * takes its carried row from its frame window; if its newest frame was decoded with a modification setting, that row is already
+ * scaled and stretched, so once wc_synth_stream_set_speed was called for a stream (any value, 1.0 included; until the next reset) the
+ * coded pushes that apply a setting to it while it is not retimed also keep its newest CODED frame in the handle (one small launch in
+ * such a push, fed by the staging copy the settings take anyway; a ping-pong pair, so a push that is refused leaves the frame of the
+ * push before; streams that never called this function do not run it) and the frame is decoded once more, unmodified, when the
+ * stream becomes retimed.  A stream with a setting whose newest frame was pushed before any call of this function has no such frame:
+ * the push that would make it retimed, and wc_synth_stream_frames_for_push, are refused with WC_ERR_INVALID; call this function with
+ * 1.0 before the first frame, or push once more at 1.0 after the call.  The frames formed
+ * before that were stretched inside the decoder: against the whole-utterance retimed call their rows differ as
+ * wc_decode_features_modified_device differs from decode + wc_modify_parameters_frames_device (1e-12 relative), the frames formed
+ * from then on not at all.  And the next position last + speed needs row floor(last + speed), while rows before F - 1 are gone: for
+ * a retimed stream that has formed a frame this function refuses a speed with floor(last + speed) < F - 1 (F source frames received)
+ * and keeps the setting.  That depends on the phase: at last = F - 1 every speed passes, at last = F - 1.5 none below 0.5; after a fast
+ * stretch a stream slows down over several pushes.  No push fails for it, of this stream or another.
+ * Refused with WC_ERR_INVALID on the host before anything is enqueued, every stream, carried row and kept frame as it was: a push
+ * that would form more than max_frames_per_push synthesis frames for one stream (the count stops at that bound: a speed of 1e-300
+ * costs nothing), and a flush that leaves a stream with fewer than two synthesis frames. */
+int wc_synth_stream_set_speed(wc_synth_stream *s, int stream, double speed);
+/* `last`: the position in source frames of the newest synthesis frame formed; NaN before the first one or for a bad index */
+double wc_synth_stream_source_position(const wc_synth_stream *s, int stream);
+/* synthesis frames formed so far (wc_synth_stream_frames_received counts the source frames pushed; equal unless retimed); -1 for a
+ * bad index */
+long long wc_synth_stream_frames_synthesised(const wc_synth_stream *s, int stream);
+/* synthesis frames a push of n_frames source frames would form for the stream at its current setting: host arithmetic only, capped
+ * at max_frames_per_push + 1 (a push that would be refused for its count); WC_ERR_INVALID (negative) for a bad argument and for a
+ * stream that cannot become retimed (no kept frame, above) */
+int wc_synth_stream_frames_for_push(const wc_synth_stream *s, int stream, int n_frames);
 /* noise position of stream u: where its next (or waiting) pulse takes its draws */
 unsigned long long wc_synth_stream_rng_position(const wc_synth_stream *s, int stream);
 int wc_synth_stream_set_rng_position(wc_synth_stream *s, int stream, unsigned long long position);

@@ -11,7 +11,11 @@
 //     peeled); consecutive output frames sit on consecutive workgroups, so the source row two neighbours share comes out of L2.
 //     STRETCH: the interpolated row of sp goes to LDS as its logarithm and is stretched by the frame's ratio (wc::stretched_bin,
 //     wc_stretch.hpp: the rule of stretch_kernel, wc_io.hip) before its one write.
-//   The workgroup finds its utterance by bisection in the descriptors, which go up through page-locked staging kept per
+//   retime_stream_kernel<STRETCH>   the same frame for the synthesis streams (wc_synth_stream_set_speed): positions in absolute source
+//     frames of a stream, the source rows those of one push plus one carried row per stream; it also keeps each stream's newest
+//     source row for the next push.  rt_pair / rt_row / rt_f0 / rt_stretched_row are shared by both kernels.
+//   A workgroup of retime_kernel finds its utterance by bisection in the descriptors (one of retime_stream_kernel reads its stream's
+//   index from a per-frame array of the host), which go up through page-locked staging kept per
 //   (device, stream): a call only enqueues.
 #include <hip/hip_runtime.h>
 
@@ -42,6 +46,15 @@ struct RtArgs {
 	double *f0_out, *sp_out, *ap_out;
 };
 
+struct RtStreamArgs {
+	const RtStreamDesc *desc;
+	const int *owner;
+	int n_desc, fs, fft_size;
+	long long total_out;
+	const double *pos, *f0_in, *sp_in, *ap_in, *scale, *ratio;
+	double *f0_out, *sp_out, *ap_out;
+};
+
 typedef double d2u __attribute__((ext_vector_type(2), aligned(8)));  // two bins of a row: 16 bytes at the row's 8-byte alignment
 
 // the two source bins b, b + 1 of the frame: row ri, or (1 - a) * ri + a * rj (two products and one sum, each rounded)
@@ -64,6 +77,43 @@ __device__ __forceinline__ void rt_row(const double *__restrict__ ri, const doub
 }
 __device__ __forceinline__ void rt_nan_row(double *__restrict__ out, int bins, int tid) {
 	for (int b = tid; b < bins; b += RT_T) out[b] = __builtin_nan("");
+}
+
+// the frame's F0: voiced exactly where Synthesis' own interpolated voicing is (the rule of tests/retime_rule.py)
+__device__ __forceinline__ double rt_f0(double fi, double fj, double w0, double a) {
+	const bool vi = fi != 0.0, vj = fj != 0.0;
+	if (!(a > 0.0)) return fi;
+	if (vi && vj) return w0 * fi + a * fj;
+	if (vi) return a < 0.5 ? fi : 0.0;
+	if (vj) return a > 0.5 ? fj : 0.0;
+	return 0.0;
+}
+
+// the interpolated row of sp to LDS as its logarithm, stretched by a valid ratio (wc::stretched_bin) before its one write
+__device__ __forceinline__ void rt_stretched_row(const double *__restrict__ ri, const double *__restrict__ rj, double w0, double a,
+												 double *__restrict__ out, double ratio, int fs, int fft_size, int tid) {
+	__shared__ double lg[kMaxBins];
+	__shared__ double fill;
+	const int bins = fft_size / 2 + 1;
+	for (int t = tid; t < bins / 2; t += RT_T) {
+		const d2u x = rt_pair(ri, rj, w0, a, 2 * t);
+		lg[2 * t] = log(x.x);
+		lg[2 * t + 1] = log(x.y);
+	}
+	if (tid == 0) lg[bins - 1] = log(rt_one(ri, rj, w0, a, bins - 1));
+	__syncthreads();
+	const int cut = static_cast<int>(fft_size / 2.0 * ratio);  // >= 1 for a valid ratio
+	const int top = ratio < 1.0 ? cut : bins;                 // bins from `cut` upward repeat bin cut - 1
+	for (int b = tid; b < top; b += RT_T) {
+		const double v = stretched_bin(b, ratio, fs, fft_size, [&](int k) { return lg[k]; });
+		out[b] = v;
+		if (b == top - 1) fill = v;
+	}
+	if (top < bins) {
+		__syncthreads();
+		const double f = fill;
+		for (int b = top + tid; b < bins; b += RT_T) out[b] = f;
+	}
 }
 
 template <bool STRETCH>
@@ -89,15 +139,7 @@ __global__ __launch_bounds__(RT_T) void retime_kernel(RtArgs A) {
 
 	if (A.f0_out && tid == 0) {
 		double v = __builtin_nan("");
-		if (finite) {
-			const double fi = A.f0_in[u.in_off + i], fj = A.f0_in[u.in_off + j];
-			const bool vi = fi != 0.0, vj = fj != 0.0;
-			if (!(a > 0.0)) v = fi;
-			else if (vi && vj) v = w0 * fi + a * fj;
-			else if (vi) v = a < 0.5 ? fi : 0.0;
-			else if (vj) v = a > 0.5 ? fj : 0.0;
-			else v = 0.0;
-		}
+		if (finite) v = rt_f0(A.f0_in[u.in_off + i], A.f0_in[u.in_off + j], w0, a);
 		if (A.scale) v *= A.scale[g];
 		A.f0_out[g] = v;
 	}
@@ -118,30 +160,54 @@ __global__ __launch_bounds__(RT_T) void retime_kernel(RtArgs A) {
 		rt_row(ri, rj, w0, a, out, bins, tid);
 		return;
 	}
-	if constexpr (STRETCH) {
-		__shared__ double lg[kMaxBins];
-		__shared__ double fill;
-		for (int t = tid; t < bins / 2; t += RT_T) {
-			const d2u x = rt_pair(ri, rj, w0, a, 2 * t);
-			lg[2 * t] = log(x.x);
-			lg[2 * t + 1] = log(x.y);
-		}
-		if (tid == 0) lg[bins - 1] = log(rt_one(ri, rj, w0, a, bins - 1));
-		__syncthreads();
-		const int fft_size = A.fft_size;
-		const int cut = static_cast<int>(fft_size / 2.0 * ratio);  // >= 1 for a valid ratio
-		const int top = ratio < 1.0 ? cut : bins;                 // bins from `cut` upward repeat bin cut - 1
-		for (int b = tid; b < top; b += RT_T) {
-			const double v = stretched_bin(b, ratio, A.fs, fft_size, [&](int k) { return lg[k]; });
-			out[b] = v;
-			if (b == top - 1) fill = v;
-		}
-		if (top < bins) {
-			__syncthreads();
-			const double f = fill;
-			for (int b = top + tid; b < bins; b += RT_T) out[b] = f;
-		}
+	if constexpr (STRETCH) rt_stretched_row(ri, rj, w0, a, out, ratio, A.fs, A.fft_size, tid);
+}
+
+// The streaming form (wc_synth_stream_set_speed, include/world_class_stream.h): the same frame at the same position, but the source
+// rows of a stream are the rows of this push and, for the frame before them, the stream's carried row.  Workgroups behind the
+// synthesis frames keep each stream's newest source row for the next push (the other side of the handle's ping-pong pair).
+template <bool STRETCH>
+__global__ __launch_bounds__(RT_T) void retime_stream_kernel(RtStreamArgs A) {
+	const int tid = threadIdx.x;
+	const long long g = blockIdx.x;
+	const int bins = A.fft_size / 2 + 1;
+	if (g >= A.total_out) {  // the newest source row of stream g - total_out is kept
+		const RtStreamDesc u = A.desc[g - A.total_out];
+		if (!u.keep_sp) return;
+		const long long r = u.in_off + u.n_in - 1;
+		if (tid == 0) *u.keep_f0 = A.f0_in[r];
+		rt_row(A.sp_in + r * bins, A.sp_in + r * bins, 1.0, 0.0, u.keep_sp, bins, tid);
+		rt_row(A.ap_in + r * bins, A.ap_in + r * bins, 1.0, 0.0, u.keep_ap, bins, tid);
+		return;
 	}
+	// the frame's stream comes from the host (no bisection: at fft 1024 a workgroup moves a few KB, and the chain of dependent
+	// loads in front of its rows is what it would wait for)
+	const RtStreamDesc u = A.desc[A.owner[g]];
+	const double p = A.pos[g];  // absolute source frames; the host keeps f_before - 1 <= floor(p) and ceil(p) < f_before + n_in
+	const long long i = static_cast<long long>(floor(p));
+	const double a = p - i;
+	const double w0 = 1.0 - a;
+	const long long ki = i - u.f_before, kj = a > 0.0 ? ki + 1 : ki;  // rows of this push; -1: the carried row
+	const double *__restrict__ fi = ki < 0 ? u.carry_f0 : A.f0_in + u.in_off + ki, *__restrict__ fj = kj < 0 ? u.carry_f0 : A.f0_in + u.in_off + kj;
+	if (tid == 0) A.f0_out[g] = rt_f0(*fi, *fj, w0, a) * A.scale[g];
+	{
+		const double *__restrict__ ri = ki < 0 ? u.carry_ap : A.ap_in + (u.in_off + ki) * bins;
+		const double *__restrict__ rj = kj < 0 ? u.carry_ap : A.ap_in + (u.in_off + kj) * bins;
+		rt_row(ri, rj, w0, a, A.ap_out + g * bins, bins, tid);
+	}
+	double *__restrict__ out = A.sp_out + g * bins;
+	const double *__restrict__ ri = ki < 0 ? u.carry_sp : A.sp_in + (u.in_off + ki) * bins;
+	const double *__restrict__ rj = kj < 0 ? u.carry_sp : A.sp_in + (u.in_off + kj) * bins;
+	const double ratio = STRETCH ? A.ratio[g] : 0.0;
+	if (STRETCH && ratio != 0.0 && !frame_ratio_valid(ratio, A.fft_size)) {
+		rt_nan_row(out, bins, tid);
+		return;
+	}
+	if (!STRETCH || ratio == 0.0) {
+		rt_row(ri, rj, w0, a, out, bins, tid);
+		return;
+	}
+	if constexpr (STRETCH) rt_stretched_row(ri, rj, w0, a, out, ratio, A.fs, A.fft_size, tid);
 }
 
 // descriptor staging per (device, stream): calls on one stream are ordered behind each other, calls on different streams never
@@ -208,6 +274,25 @@ int wc::retime_enqueue(Device *dev, hipStream_t s, int fs, int fft_size, int n_u
 	WC_HIP(hipGetLastError());
 	if (route_mod) return modify_frames_enqueue(s, fs, fft_size, total_out, d_f0_out, d_sp_out, d_f0_scale, d_spectral_ratio);
 	return WC_OK;
+}
+
+int wc::retime_stream_enqueue(Device *dev, hipStream_t s, int fs, int fft_size, int n_desc, const RtStreamDesc *d_desc, const int *d_owner,
+							  long long total_out, const double *d_position, const double *d_f0_scale, const double *d_spectral_ratio, const double *d_f0_in,
+							  const double *d_sp_in, const double *d_ap_in, double *d_f0_out, double *d_sp_out, double *d_ap_out) {
+	if (n_desc <= 0) return WC_OK;
+	RtStreamArgs a;
+	a.desc = d_desc;
+	a.owner = d_owner;
+	a.n_desc = n_desc; a.fs = fs; a.fft_size = fft_size; a.total_out = total_out;
+	a.pos = d_position; a.f0_in = d_f0_in; a.sp_in = d_sp_in; a.ap_in = d_ap_in; a.scale = d_f0_scale; a.ratio = d_spectral_ratio;
+	a.f0_out = d_f0_out; a.sp_out = d_sp_out; a.ap_out = d_ap_out;
+	int rc;
+	if ((rc = dev->time_begin("retime_stream_kernel", s))) return rc;
+	const dim3 grid((unsigned)(total_out + n_desc));
+	if (a.ratio) hipLaunchKernelGGL(retime_stream_kernel<true>, grid, dim3(RT_T), 0, s, a);
+	else hipLaunchKernelGGL(retime_stream_kernel<false>, grid, dim3(RT_T), 0, s, a);
+	WC_HIP(hipGetLastError());
+	return dev->time_end("retime_stream_kernel", s);
 }
 
 extern "C" int wc_retime_parameters_device(int fs, int fft_size, int n_utt, const int *in_length, const double *d_f0_in, const double *d_sp_in,

@@ -106,6 +106,22 @@ int retime_enqueue(Device *dev, hipStream_t s, int fs, int fft_size, int n_utt, 
 				   const double *d_sp_in, const double *d_ap_in, const int *out_length, const double *d_position, const double *d_f0_scale,
 				   const double *d_spectral_ratio, double *d_f0_out, double *d_sp_out, double *d_ap_out, long long total_out);
 
+// The streaming form (wc_synth_stream_set_speed): one descriptor per stream of the push, in the order of the packed arrays.  The
+// synthesis frames [out_off, next out_off) of the stream sit at d_position (absolute source frames); source frame f_before + k is
+// row in_off + k of the packed input, k < n_in, and source frame f_before - 1 is the carried row.  keep_*: where the newest source
+// row of the push is kept for the next one, or nullptr.  The descriptors and the per-frame arrays are already on the device (the
+// caller's staging), and so is d_owner, the index of its stream's descriptor per synthesis frame; one launch of total_out + n_desc
+// workgroups, d_spectral_ratio == nullptr: no stretch.
+struct RtStreamDesc {
+	long long out_off, in_off, f_before;
+	const double *carry_f0, *carry_sp, *carry_ap;
+	double *keep_f0, *keep_sp, *keep_ap;
+	int n_in;
+};
+int retime_stream_enqueue(Device *dev, hipStream_t s, int fs, int fft_size, int n_desc, const RtStreamDesc *d_desc, const int *d_owner,
+						  long long total_out, const double *d_position, const double *d_f0_scale, const double *d_spectral_ratio, const double *d_f0_in,
+						  const double *d_sp_in, const double *d_ap_in, double *d_f0_out, double *d_sp_out, double *d_ap_out);
+
 // Feature coding (wc_code_features.hip)
 // nullptr if (fs, fft_size, nd) can be coded, else why not: fft_size 512 .. 4096, 1 <= nd <= fft_size/4+1, and with the
 // aperiodicity fs >= 12 kHz (at least one band)

@@ -21,6 +21,7 @@
 
 #include "wc_stages.hpp"
 #include "wc_synthesis.hpp"
+#include "../../include/world_class_codec.h"
 #include "../../include/world_class_stream.h"
 
 namespace wc {
@@ -221,6 +222,19 @@ struct SsState {
 	bool closed = false;
 	double mod_f0 = 1.0, mod_ratio = 0.0;  // wc_synth_stream_set_modification: what coded pushes apply to this stream's frames
 	bool neutral() const { return mod_f0 == 1.0 && mod_ratio == 0.0; }
+	// wc_synth_stream_set_speed.  A stream that is not retimed has no state of its own here: its source frames are its frames.
+	double speed = 1.0;
+	bool retimed = false;   // formed along the time map since the first push with frames at a speed other than 1.0
+	bool speed_set = false;  // wc_synth_stream_set_speed was called since create / reset: the stream may become retimed mid-stream
+	// not retimed: the newest row of the window was scaled or stretched on its way in (tail_mod), so it is no source row to carry;
+	// for a stream with speed_set the frame's coded row is kept instead (tail_kept: tail_nd coefficients, on side tside of a
+	// ping-pong pair) and decoded if the stream becomes retimed
+	bool tail_mod = false, tail_kept = false;
+	int tail_nd = 0, tside = 0;
+	bool formed = false;    // retimed: a synthesis frame exists, at source position `last`
+	double last = 0.0;
+	long long src = 0;      // retimed: source frames received (F counts the synthesis frames)
+	int cside = 0;          // retimed: the side of the carried-row pair that holds source frame src - 1
 };
 }  // namespace
 
@@ -237,7 +251,13 @@ struct wc_synth_stream {
 	// a coded push with wc_synth_stream_set_modification settings: per-frame spectral ratios | F0 scales (2 x max_frames x n_streams,
 	// staged through h_mod, the coded push's own: the plain push behind it stages its metadata through h_stage) and the scaled F0
 	DevBuf dmod, sf0;
-	HostBuf h_stage, h_mod;
+	// retimed pushes (wc_synth_stream_set_speed), reserved on the first one: the carried source rows (two sides x n_streams), the
+	// retimed rows and F0 (max_frames x n_streams), descriptors | positions | scales | ratios | descriptor indices staged through h_rt
+	DevBuf cf0, csp, cap, rf0, rsp, rap, drt;
+	// the newest coded frame of every stream with a modification setting (F0 | fft_size/2 coefficients | the bands, per stream),
+	// kept by the coded pushes that apply a setting
+	DevBuf tf0, tcsp, tcap;  // (two sides x n_streams)
+	HostBuf h_stage, h_mod, h_rt;
 };
 
 namespace {
@@ -267,6 +287,66 @@ int final_limit(const wc_synth_stream *s, int F) {
 }
 
 int frame_of(const wc_synth_stream *s, int i) { return (int)std::floor(i / (double)s->fs / s->frame_period); }
+
+// The newest coded frame of the streams of a coded push that have a modification setting and may be given a speed later (tail[u]: its
+// index in the packed arrays, as a double; negative: none) to the handle: the source row such a stream carries if it becomes
+// retimed.  tail[n_streams + u]: the row of the pair it goes to (side * n_streams + u, the side the stream does not hold)
+__global__ void ss_keep_tail_kernel(const double *__restrict__ tail, const double *__restrict__ f0, const double *__restrict__ csp,
+									const double *__restrict__ cap, int nd, int n_ap, int stride, double *__restrict__ tf0,
+									double *__restrict__ tcsp, double *__restrict__ tcap) {
+	const int u = blockIdx.x;
+	if (tail[u] < 0.0) return;
+	const long long i = (long long)tail[u], r = (long long)tail[gridDim.x + u];
+	if (threadIdx.x == 0) tf0[r] = f0[i];
+	for (int k = threadIdx.x; k < nd; k += blockDim.x) tcsp[r * stride + k] = csp[i * nd + k];
+	for (int k = threadIdx.x; k < n_ap; k += blockDim.x) tcap[r * n_ap + k] = cap[i * n_ap + k];
+}
+
+// ---- wc_synth_stream_set_speed: the rule (host arithmetic, the same for every fft size) ----
+// whether a push of n source frames treats the stream along its time map
+bool ss_follows_map(const SsState &q, int n) { return q.retimed || (n > 0 && q.speed != 1.0); }
+
+// The stream takes n source frames and forms its synthesis frames: p = last + speed (0.0 for the first) while p <= F - 1.  Returns
+// their number, positions appended to pos, or limit + 1 as soon as there would be more than limit (q is then half way: callers work
+// on a copy or under a guard).
+int ss_form(SsState &q, int n, int limit, std::vector<double> *pos) {
+	if (!q.retimed) {  // becomes retimed: so far its frames sat at whole positions
+		q.retimed = true;
+		q.src = q.F;
+		q.formed = q.F > 0;
+		q.last = q.F - 1.0;
+		q.cside = 0;
+	}
+	q.src += n;
+	int c = 0;
+	for (;;) {
+		const double p = q.formed ? q.last + q.speed : 0.0;
+		if (!(p <= (double)(q.src - 1))) return c;
+		if (c == limit) return limit + 1;
+		if (pos) pos->push_back(p);
+		q.last = p;
+		q.formed = true;
+		++c;
+	}
+}
+
+// A stream about to become retimed whose newest frame was decoded with a modification setting and whose coded frame was not kept:
+// it has no source row to carry.  (The kept frame costs a launch per coded push, so only streams that called
+// wc_synth_stream_set_speed before that push pay for it.)
+bool ss_tail_missing(const SsState &q) { return !q.retimed && q.F > 0 && q.tail_mod && !q.tail_kept; }
+const char *const kTailMissing =
+	"synthesis stream: a stream whose frames were decoded with a modification setting becomes retimed mid-stream only if "
+	"wc_synth_stream_set_speed was called for it (1.0 will do) before its newest frame was pushed";
+
+// a push runs the retimed path if a stream that receives frames follows its map (or a lowered speed lets one form a frame without)
+bool ss_push_is_retimed(const wc_synth_stream *s, const int *n_frames) {
+	for (int u = 0; u < s->n_streams; ++u) {
+		const SsState &q = s->st[u];
+		if (q.closed) continue;
+		if (n_frames[u] > 0 ? ss_follows_map(q, n_frames[u]) : (q.retimed && q.formed && q.last + q.speed <= (double)(q.src - 1))) return true;
+	}
+	return false;
+}
 
 __global__ void ss_scale_f0_kernel(const double *__restrict__ f0, const double *__restrict__ scale, long long n, double *__restrict__ out) {
 	for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) out[i] = f0[i] * scale[i];
@@ -300,6 +380,8 @@ void wc_synth_stream_destroy(wc_synth_stream *s) {
 	s->dev->quiesce();
 	for (int k = 0; k < 2; ++k) { s->wf0[k].release(); s->wsp[k].release(); s->wap[k].release(); s->carry[k].release(); }
 	s->dsp.release(); s->dap.release(); s->dmod.release(); s->sf0.release(); s->h_mod.release();
+	s->cf0.release(); s->csp.release(); s->cap.release(); s->rf0.release(); s->rsp.release(); s->rap.release(); s->drt.release(); s->h_rt.release();
+	s->tf0.release(); s->tcsp.release(); s->tcap.release();
 	s->work.release(); s->inc.release(); s->pulses.release(); s->resp.release(); s->meta.release(); s->owner.release(); s->aux.release(); s->h_stage.release();
 	wc_synthesis_destroy(s->sy);
 	delete s;
@@ -323,7 +405,36 @@ int wc_synth_stream_set_rng_position(wc_synth_stream *s, int u, unsigned long lo
 	s->st[u].rng_pos = position;
 	return WC_OK;
 }
-long long wc_synth_stream_frames_received(const wc_synth_stream *s, int u) { return (s && u >= 0 && u < s->n_streams) ? s->st[u].frames : -1; }
+long long wc_synth_stream_frames_received(const wc_synth_stream *s, int u) {
+	if (!s || u < 0 || u >= s->n_streams) return -1;
+	return s->st[u].retimed ? s->st[u].src : s->st[u].frames;
+}
+long long wc_synth_stream_frames_synthesised(const wc_synth_stream *s, int u) { return (s && u >= 0 && u < s->n_streams) ? s->st[u].frames : -1; }
+double wc_synth_stream_source_position(const wc_synth_stream *s, int u) {
+	if (!s || u < 0 || u >= s->n_streams) return std::nan("");
+	const SsState &q = s->st[u];
+	if (q.retimed) return q.formed ? q.last : std::nan("");
+	return q.frames > 0 ? (double)(q.frames - 1) : std::nan("");
+}
+int wc_synth_stream_set_speed(wc_synth_stream *s, int u, double speed) {
+	if (!s || u < 0 || u >= s->n_streams) return fail(WC_ERR_INVALID, "synthesis stream: bad stream index");
+	if (!(speed > 0.0 && speed <= DBL_MAX)) return fail(WC_ERR_INVALID, "synthesis stream: speed must be finite and positive");
+	DeviceLock lock(s->dev);
+	SsState &q = s->st[u];
+	// one source row is carried (frame F - 1): the next position last + speed must not lie before it
+	if (q.retimed && q.formed && std::floor(q.last + speed) < (double)(q.src - 1))
+		return fail(WC_ERR_INVALID, "synthesis stream: speed so low that the stream's next position, last + speed, lies before its newest source frame");
+	q.speed = speed;
+	q.speed_set = true;
+	return WC_OK;
+}
+int wc_synth_stream_frames_for_push(const wc_synth_stream *s, int u, int n_frames) {
+	if (!s || u < 0 || u >= s->n_streams || n_frames < 0) return fail(WC_ERR_INVALID, "synthesis stream: bad stream index or frame count");
+	SsState q = s->st[u];
+	if (!ss_follows_map(q, n_frames)) return std::min(n_frames, s->max_frames + 1);
+	if (ss_tail_missing(q)) return fail(WC_ERR_INVALID, kTailMissing);
+	return ss_form(q, n_frames, s->max_frames, nullptr);
+}
 long long wc_synth_stream_samples_committed(const wc_synth_stream *s, int u) { return (s && u >= 0 && u < s->n_streams) ? s->st[u].samples : -1; }
 
 int wc_synth_stream_set_modification(wc_synth_stream *s, int u, double f0_scale, double spectral_ratio) {
@@ -647,60 +758,279 @@ static int ss_push_rows(wc_synth_stream *s, const int *n_frames, const int *flus
 	return WC_OK;
 }
 
+}  // extern "C"
+
+// ---- retimed pushes (wc_synth_stream_set_speed) ----
+namespace {
+struct RtLink {  // where a stream's carried row comes from and where its newest source row goes, resolved once the buffers exist
+	// carry: -1 none, 0 / 1 a side of the pair, 2 the frame window's newest row, 3 the kept coded frame (nd coefficients), decoded
+	// into side 0; keep: -1 none, else a side
+	int u, carry, keep, nd, tside;
+	long long wrow;  // carry == 2: the row of the window buffers
+};
+struct RtPlan {
+	std::vector<int> cnt;  // synthesis frames per stream
+	std::vector<RtStreamDesc> desc;
+	std::vector<RtLink> link;
+	std::vector<double> pos, scale, ratio;  // per synthesis frame
+	std::vector<int> owner;                 // per synthesis frame: its stream's index in desc
+	bool stretch = false;
+};
+
+// a failed retimed push gives back the rule's state and the sides of the carried rows (SynthStreamGuard, inside ss_push_rows,
+// only restores what ss_push_rows itself changed)
+struct SpeedGuard {
+	wc_synth_stream *s;
+	std::vector<SsState> st;
+	bool keep;
+	SpeedGuard(wc_synth_stream *x, bool armed) : s(x), keep(!armed) { if (armed) st = x->st; }  // (not armed: nothing is copied)
+	~SpeedGuard() { if (!keep) s->st = st; }
+};
+
+// Host arithmetic of a retimed push: the synthesis frames of every stream, their positions, scales and ratios, and every refusal.
+// Changes the rule's state of the streams (under the caller's SpeedGuard); enqueues and allocates nothing.
+int ss_plan_retimed(wc_synth_stream *s, const int *n_frames, const int *flush, bool coded, RtPlan &pl) {
+	const int n = s->n_streams;
+	pl.cnt.assign(n, 0);
+	long long in_off = 0;
+	for (int u = 0; u < n; ++u) {
+		const int nf = n_frames[u];
+		const bool fl = flush && flush[u];
+		SsState &q = s->st[u];
+		if (nf < 0 || nf > s->max_frames) return fail(WC_ERR_INVALID, "synthesis stream push: n_frames out of range");
+		if (q.closed && (nf > 0 || fl)) return fail(WC_ERR_INVALID, "synthesis stream push: stream was flushed; wc_synth_stream_reset it first");
+		if (q.closed) continue;
+		RtStreamDesc d;
+		std::memset(&d, 0, sizeof(d));
+		RtLink k{u, -1, -1, 0, 0, 0};
+		d.out_off = (long long)pl.pos.size();
+		d.in_off = in_off;
+		d.n_in = nf;
+		int c;
+		double sc = coded ? q.mod_f0 : 1.0, rt = 0.0;
+		if (ss_follows_map(q, nf)) {
+			const bool was = q.retimed;
+			const long long before = was ? q.src : q.F;
+			if (ss_tail_missing(q)) return fail(WC_ERR_INVALID, kTailMissing);
+			d.f_before = before;
+			c = ss_form(q, nf, s->max_frames, &pl.pos);
+			if (c > s->max_frames) return fail(WC_ERR_INVALID, "synthesis stream push: more than max_frames_per_push synthesis frames for one stream");
+			if (c > 0 && std::floor(pl.pos[d.out_off]) < (double)(before - 1))
+				return fail(WC_ERR_INVALID, "synthesis stream push: internal: the next position lies before the carried row");  // (wc_synth_stream_set_speed refuses such a speed)
+			if (before > 0) {
+				k.carry = was ? q.cside : q.tail_mod ? 3 : 2;
+				k.nd = q.tail_nd;
+				k.tside = q.tside;
+				k.wrow = (long long)u * s->wcap + (q.F - 1 - q.wbase);
+				if (!was && (q.F - 1 < q.wbase || q.F - 1 >= q.wbase + q.wlen)) return fail(WC_ERR_INVALID, "synthesis stream push: internal window arithmetic");
+			}
+			if (nf > 0) {
+				k.keep = 1 - q.cside;
+				q.cside = k.keep;
+			}
+			if (coded) rt = q.mod_ratio;
+		} else {  // not retimed: whole positions, its ratio (coded pushes) went into the decoder
+			d.f_before = q.F;
+			c = nf;
+			for (int i = 0; i < nf; ++i) pl.pos.push_back((double)(q.F + i));
+		}
+		if (fl && q.F + c < 2) return fail(WC_ERR_INVALID, "synthesis stream push: a stream needs at least two synthesis frames (reference src/synthesis.cpp:241-242)");
+		pl.scale.insert(pl.scale.end(), c, sc);
+		pl.ratio.insert(pl.ratio.end(), c, rt);
+		pl.owner.insert(pl.owner.end(), c, (int)pl.desc.size());  // (c > 0: the descriptor is pushed below)
+		pl.stretch = pl.stretch || (c > 0 && rt != 0.0);
+		pl.cnt[u] = c;
+		in_off += nf;
+		if (nf > 0 || c > 0) {
+			pl.desc.push_back(d);
+			pl.link.push_back(k);
+		}
+	}
+	return WC_OK;
+}
+
+// The device half: buffers on first use, descriptors and per-frame values up through h_rt, wc::retime_stream_enqueue on the source
+// rows of this push (the caller's full rows or the decoded ones), then the push on the retimed rows.
+int ss_run_retimed(wc_synth_stream *s, RtPlan &pl, const int *flush, const double *d_f0, const double *d_sp, const double *d_ap, double *d_y,
+				   int *samples_out) {
+	const int n = s->n_streams, bins = s->fft_size / 2 + 1;
+	const size_t cap = (size_t)s->max_frames * n, row = sizeof(double) * (size_t)bins;
+	const long long total = (long long)pl.pos.size();
+	const int nd = (int)pl.desc.size();
+	hipStream_t hs = s->dev->active();
+	int rc;
+	if ((rc = s->cf0.reserve(sizeof(double) * 2 * n)) || (rc = s->csp.reserve(row * 2 * n)) || (rc = s->cap.reserve(row * 2 * n)) ||
+		(rc = s->rf0.reserve(sizeof(double) * cap)) || (rc = s->rsp.reserve(row * cap)) || (rc = s->rap.reserve(row * cap))) return rc;
+	if (nd > 0) {
+		const size_t bytes = sizeof(RtStreamDesc) * (size_t)nd + (3 * sizeof(double) + sizeof(int)) * (size_t)total;
+		if ((rc = s->drt.reserve(sizeof(RtStreamDesc) * (size_t)n + (3 * sizeof(double) + sizeof(int)) * cap)) || (rc = s->h_rt.reserve(bytes))) return rc;
+		for (int a = 0; a < nd; ++a) {
+			const RtLink &k = pl.link[a];
+			RtStreamDesc &d = pl.desc[a];
+			if (k.carry == 2) {
+				d.carry_f0 = s->wf0[s->parity].as<double>() + k.wrow;
+				d.carry_sp = s->wsp[s->parity].as<double>() + k.wrow * bins;
+				d.carry_ap = s->wap[s->parity].as<double>() + k.wrow * bins;
+			} else if (k.carry >= 0) {
+				const long long r = (long long)(k.carry == 3 ? 0 : k.carry) * n + k.u;
+				if (k.carry == 3) {  // (once per stream and reset: the frame the decoder stretched is decoded again as it was)
+					const int n_ap = GetNumberOfAperiodicities(s->fs);
+					const long long t = (long long)k.tside * n + k.u;
+					WC_HIP(hipMemcpyAsync(s->cf0.as<double>() + r, s->tf0.as<double>() + t, sizeof(double), hipMemcpyDeviceToDevice, hs));
+					if ((rc = decode_features_enqueue(s->dev, hs, s->fs, s->fft_size, 1, k.nd, s->tcsp.as<double>() + t * (s->fft_size / 2),
+													  s->tcap.as<double>() + t * n_ap, nullptr, s->csp.as<double>() + r * bins,
+													  s->cap.as<double>() + r * bins))) return rc;
+				}
+				d.carry_f0 = s->cf0.as<double>() + r;
+				d.carry_sp = s->csp.as<double>() + r * bins;
+				d.carry_ap = s->cap.as<double>() + r * bins;
+			}
+			if (k.keep >= 0) {
+				const long long r = (long long)k.keep * n + k.u;
+				d.keep_f0 = s->cf0.as<double>() + r;
+				d.keep_sp = s->csp.as<double>() + r * bins;
+				d.keep_ap = s->cap.as<double>() + r * bins;
+			}
+		}
+		char *h = static_cast<char *>(s->h_rt.p);
+		double *hv = reinterpret_cast<double *>(h + sizeof(RtStreamDesc) * (size_t)nd);
+		std::memcpy(h, pl.desc.data(), sizeof(RtStreamDesc) * (size_t)nd);
+		if (total > 0) {
+			std::memcpy(hv, pl.pos.data(), sizeof(double) * total);
+			std::memcpy(hv + total, pl.scale.data(), sizeof(double) * total);
+			std::memcpy(hv + 2 * total, pl.ratio.data(), sizeof(double) * total);
+			std::memcpy(hv + 3 * total, pl.owner.data(), sizeof(int) * total);
+		}
+		WC_HIP(hipMemcpyAsync(s->drt.p, h, bytes, hipMemcpyHostToDevice, hs));
+		if ((rc = s->h_rt.mark(hs))) return rc;
+		const double *dv = reinterpret_cast<const double *>(static_cast<char *>(s->drt.p) + sizeof(RtStreamDesc) * (size_t)nd);
+		if ((rc = retime_stream_enqueue(s->dev, hs, s->fs, s->fft_size, nd, s->drt.as<RtStreamDesc>(), reinterpret_cast<const int *>(dv + 3 * total), total, dv, dv + total,
+										pl.stretch ? dv + 2 * total : nullptr, d_f0, d_sp, d_ap, s->rf0.as<double>(), s->rsp.as<double>(),
+										s->rap.as<double>()))) return rc;
+	}
+	return ss_push_rows(s, pl.cnt.data(), flush, s->rf0.as<double>(), s->rsp.as<double>(), s->rap.as<double>(), d_y, samples_out);
+}
+
+// whether a coded push keeps the newest coded frame of stream u (ss_keep_tail_kernel): not retimed, a modification setting, and
+// wc_synth_stream_set_speed was called for it
+bool ss_keeps_tail(const SsState &q, int nf) { return nf > 0 && !q.retimed && !q.neutral() && q.speed_set; }
+
+// what a push that succeeded leaves behind for a later change of speed: whether the newest row of a stream that is not retimed
+// reached its window unmodified, and the side of the pair its kept coded frame went to
+void ss_note_tails(wc_synth_stream *s, const int *n_frames, int coded_nd) {
+	for (int u = 0; u < s->n_streams; ++u) {
+		SsState &q = s->st[u];
+		if (n_frames[u] <= 0 || q.retimed) continue;
+		q.tail_mod = coded_nd > 0 && !q.neutral();
+		q.tail_kept = coded_nd > 0 && ss_keeps_tail(q, n_frames[u]);
+		q.tail_nd = coded_nd;
+		if (q.tail_kept) q.tside = 1 - q.tside;
+	}
+}
+}  // namespace
+
+extern "C" {
+
 // Full rows are pushed as they are: the settings of wc_synth_stream_set_modification are applied where coded rows are decoded, so a
-// push that gives frames to a stream with a setting is refused rather than synthesised unmodified.
+// push that gives frames to a stream with a setting is refused rather than synthesised unmodified.  Streams with a speed
+// (wc_synth_stream_set_speed): the rows are retimed without scale or ratio and the push runs on the retimed rows.
 int wc_synth_stream_push_device(wc_synth_stream *s, const int *n_frames, const int *flush, const double *d_f0, const double *d_sp,
 								const double *d_ap, double *d_y, int *samples_out) {
 	if (!s || !n_frames || !samples_out) return fail(WC_ERR_INVALID, "synthesis stream push: null argument");
-	for (int u = 0; u < s->n_streams; ++u)
+	DeviceLock lock(s->dev);  // (the settings are written under it)
+	long long total_in = 0;
+	for (int u = 0; u < s->n_streams; ++u) {
 		if (n_frames[u] > 0 && !s->st[u].neutral())
 			return fail(WC_ERR_INVALID, "synthesis stream push: a stream with a modification setting takes coded frames only (wc_synth_stream_push_coded_device)");
-	return ss_push_rows(s, n_frames, flush, d_f0, d_sp, d_ap, d_y, samples_out);
+		total_in += std::max(n_frames[u], 0);
+	}
+	int rc;
+	if (!ss_push_is_retimed(s, n_frames)) {
+		if ((rc = ss_push_rows(s, n_frames, flush, d_f0, d_sp, d_ap, d_y, samples_out))) return rc;
+		ss_note_tails(s, n_frames, 0);
+		return WC_OK;
+	}
+	if (total_in > 0 && (!d_f0 || !d_sp || !d_ap)) return fail(WC_ERR_INVALID, "synthesis stream push: null frame arrays");
+	if (!d_y) return fail(WC_ERR_INVALID, "synthesis stream push: null output");
+	WC_HIP(hipSetDevice(s->dev->id));
+	SpeedGuard guard(s, true);
+	RtPlan pl;
+	if ((rc = ss_plan_retimed(s, n_frames, flush, false, pl))) return rc;
+	if ((rc = ss_run_retimed(s, pl, flush, d_f0, d_sp, d_ap, d_y, samples_out))) return rc;
+	ss_note_tails(s, n_frames, 0);
+	guard.keep = true;
+	return WC_OK;
 }
 
 // The pushed frames' coded rows are decoded (wc::decode_features_enqueue) into the handle's rows on the caller's stream, and the push
 // runs on them: the stream state is only touched by ss_push_rows, which keeps it unchanged when it fails.  Streams with a setting
 // of wc_synth_stream_set_modification: the settings expanded per frame go up through h_mod, the decoder stretches with them and the
-// push takes f0 * f0_scale out of sf0.
+// push takes f0 * f0_scale out of sf0.  A retimed push (wc_synth_stream_set_speed) is planned and checked on the host first; the
+// decoder then stretches the frames of the streams that are not retimed only, and scale and ratio of the others -- and every
+// F0 scale -- are applied per synthesis frame by the retiming kernel.
 int wc_synth_stream_push_coded_device(wc_synth_stream *s, const int *n_frames, const int *flush, const double *d_f0,
 									  const double *d_coded_sp, int number_of_dimensions, const double *d_coded_ap, double *d_y,
 									  int *samples_out) {
 	if (!s || !n_frames || !samples_out) return fail(WC_ERR_INVALID, "synthesis stream push: null argument");
 	if (const char *why = decode_features_check(s->fs, s->fft_size, number_of_dimensions)) return fail(WC_ERR_INVALID, why);
 	long long total_in = 0;
-	bool scaled = false, stretched = false;
 	for (int u = 0; u < s->n_streams; ++u) {
 		if (n_frames[u] < 0 || n_frames[u] > s->max_frames) return fail(WC_ERR_INVALID, "synthesis stream push: n_frames out of range");
 		total_in += n_frames[u];
-		if (n_frames[u] > 0) {
-			scaled = scaled || s->st[u].mod_f0 != 1.0;
-			stretched = stretched || s->st[u].mod_ratio != 0.0;
-		}
 	}
 	if (total_in > 0 && (!d_f0 || !d_coded_sp || !d_coded_ap)) return fail(WC_ERR_INVALID, "synthesis stream push: null frame arrays");
 	if (!d_y) return fail(WC_ERR_INVALID, "synthesis stream push: null output");
 	WC_HIP(hipSetDevice(s->dev->id));
 	DeviceLock lock(s->dev);
+	const bool retimed = ss_push_is_retimed(s, n_frames);
+	SpeedGuard guard(s, retimed);
+	RtPlan pl;
+	int rc;
+	if (retimed && (rc = ss_plan_retimed(s, n_frames, flush, true, pl))) return rc;
+	// what the stages in front of the push apply per source frame
+	auto scale_of = [&](int u) { return retimed ? 1.0 : s->st[u].mod_f0; };
+	auto ratio_of = [&](int u) { return retimed && s->st[u].retimed ? 0.0 : s->st[u].mod_ratio; };
+	auto keeps_tail = [&](int u) { return ss_keeps_tail(s->st[u], n_frames[u]); };
+	bool scaled = false, stretched = false, tails = false;
+	for (int u = 0; u < s->n_streams; ++u)
+		if (n_frames[u] > 0) {
+			scaled = scaled || scale_of(u) != 1.0;
+			stretched = stretched || ratio_of(u) != 0.0;
+			tails = tails || keeps_tail(u);
+		}
 	if (total_in > 0) {
 		const size_t cap = (size_t)s->max_frames * s->n_streams;
 		const size_t rows = sizeof(double) * cap * (s->fft_size / 2 + 1);
 		hipStream_t hs = s->dev->active();
-		int rc;
 		if ((rc = s->dsp.reserve(rows))) return rc;
 		if ((rc = s->dap.reserve(rows))) return rc;
 		const double *d_ratio = nullptr;
-		if (scaled || stretched) {
-			if ((rc = s->dmod.reserve(sizeof(double) * 2 * cap)) || (rc = s->sf0.reserve(sizeof(double) * cap)) ||
-				(rc = s->h_mod.reserve(sizeof(double) * 2 * cap))) return rc;  // (waits for the staging buffer's earlier upload)
-			double *h_ratio = s->h_mod.as<double>(), *h_scale = h_ratio + total_in;
+		if (scaled || stretched || tails) {
+			const int ns = s->n_streams, n_ap = GetNumberOfAperiodicities(s->fs), stride = s->fft_size / 2;
+			const size_t extra = tails ? 2 * (size_t)ns : 0;  // the kept frames' indices | their rows in the pair, behind ratios | scales
+			if ((rc = s->dmod.reserve(sizeof(double) * (2 * cap + extra))) || (rc = s->sf0.reserve(sizeof(double) * cap)) ||
+				(rc = s->h_mod.reserve(sizeof(double) * (2 * cap + extra)))) return rc;  // (waits for the staging buffer's earlier upload)
+			if (tails && ((rc = s->tf0.reserve(sizeof(double) * 2 * ns)) || (rc = s->tcsp.reserve(sizeof(double) * 2 * (size_t)ns * stride)) ||
+						  (rc = s->tcap.reserve(sizeof(double) * 2 * (size_t)ns * std::max(n_ap, 1))))) return rc;
+			double *h_ratio = s->h_mod.as<double>(), *h_scale = h_ratio + total_in, *h_tail = h_scale + total_in;
+			if (tails)
+				for (long long u = 0, o = 0; u < ns; o += n_frames[u], ++u) {
+					h_tail[u] = keeps_tail((int)u) ? (double)(o + n_frames[u] - 1) : -1.0;
+					h_tail[ns + u] = (double)((long long)(1 - s->st[u].tside) * ns + u);  // a push that fails leaves the side it holds
+				}
 			long long o = 0;
 			for (int u = 0; u < s->n_streams; ++u)
 				for (int i = 0; i < n_frames[u]; ++i, ++o) {
-					h_ratio[o] = s->st[u].mod_ratio;
-					h_scale[o] = s->st[u].mod_f0;
+					h_ratio[o] = ratio_of(u);
+					h_scale[o] = scale_of(u);
 				}
-			WC_HIP(hipMemcpyAsync(s->dmod.p, s->h_mod.p, sizeof(double) * 2 * (size_t)total_in, hipMemcpyHostToDevice, hs));
+			WC_HIP(hipMemcpyAsync(s->dmod.p, s->h_mod.p, sizeof(double) * (2 * (size_t)total_in + extra), hipMemcpyHostToDevice, hs));
 			if ((rc = s->h_mod.mark(hs))) return rc;
+			if (tails) {
+				hipLaunchKernelGGL(ss_keep_tail_kernel, dim3(ns), dim3(64), 0, hs, (const double *)(s->dmod.as<double>() + 2 * total_in), d_f0, d_coded_sp,
+								   d_coded_ap, number_of_dimensions, n_ap, stride, s->tf0.as<double>(), s->tcsp.as<double>(), s->tcap.as<double>());
+				WC_HIP(hipGetLastError());
+			}
 			if (stretched) d_ratio = s->dmod.as<double>();
 			if (scaled) {
 				const unsigned blocks = static_cast<unsigned>(std::min<long long>((total_in + 255) / 256, 65536));
@@ -713,7 +1043,12 @@ int wc_synth_stream_push_coded_device(wc_synth_stream *s, const int *n_frames, c
 		if ((rc = decode_features_enqueue(s->dev, hs, s->fs, s->fft_size, total_in, number_of_dimensions, d_coded_sp, d_coded_ap, d_ratio,
 										  s->dsp.as<double>(), s->dap.as<double>()))) return rc;
 	}
-	return ss_push_rows(s, n_frames, flush, d_f0, s->dsp.as<double>(), s->dap.as<double>(), d_y, samples_out);
+	if (retimed) rc = ss_run_retimed(s, pl, flush, d_f0, s->dsp.as<double>(), s->dap.as<double>(), d_y, samples_out);
+	else rc = ss_push_rows(s, n_frames, flush, d_f0, s->dsp.as<double>(), s->dap.as<double>(), d_y, samples_out);
+	if (rc) return rc;
+	ss_note_tails(s, n_frames, number_of_dimensions);
+	guard.keep = true;
+	return WC_OK;
 }
 
 }  // extern "C"

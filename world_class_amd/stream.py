@@ -39,6 +39,10 @@ STREAM_SIGNATURES = {
     "wc_synth_stream_set_rng_position": (C.c_int, [_vp, C.c_int, C.c_ulonglong]),
     "wc_synth_stream_frames_received": (C.c_longlong, [_vp, C.c_int]),
     "wc_synth_stream_samples_committed": (C.c_longlong, [_vp, C.c_int]),
+    "wc_synth_stream_set_speed": (C.c_int, [_vp, C.c_int, C.c_double]),
+    "wc_synth_stream_source_position": (C.c_double, [_vp, C.c_int]),
+    "wc_synth_stream_frames_synthesised": (C.c_longlong, [_vp, C.c_int]),
+    "wc_synth_stream_frames_for_push": (C.c_int, [_vp, C.c_int, C.c_int]),
 }
 _bound = False
 
@@ -288,6 +292,28 @@ class StreamSynthesizer:
         """pitch and formant shift of the frames that later coded pushes give this stream ((1.0, 0.0) = none, also after reset);
         push_device takes no frames for a stream with a setting"""
         _check(_lib().wc_synth_stream_set_modification(self._h, int(stream), float(f0_scale), float(spectral_ratio)))
+
+    def set_speed(self, stream, speed):
+        """speed of the stream (1.0 = none, also after reset): the frames pushed from now on are source frames, and the stream
+        synthesises the frames at pos[k] = pos[k-1] + speed source frames (the rule of the header).  Refused for a retimed stream
+        while floor(source_position + speed) < frames_received - 1 (one source row is carried); a stream with a modification setting
+        that is to change speed mid-stream calls this (1.0 will do) before its first frame"""
+        _check(_lib().wc_synth_stream_set_speed(self._h, int(stream), float(speed)))
+
+    def source_position(self, stream):
+        """position in source frames of the newest synthesis frame formed (NaN before the first)"""
+        return float(_lib().wc_synth_stream_source_position(self._h, int(stream)))
+
+    def frames_synthesised(self, stream):
+        """synthesis frames formed so far (frames_received counts the source frames pushed)"""
+        return int(_lib().wc_synth_stream_frames_synthesised(self._h, int(stream)))
+
+    def frames_for_push(self, stream, n_frames):
+        """synthesis frames a push of n_frames source frames would form at the current setting (at most max_frames + 1)"""
+        c = _lib().wc_synth_stream_frames_for_push(self._h, int(stream), int(n_frames))
+        if c < 0:
+            _check(c)
+        return c
 
     def rng_position(self, stream):
         return int(_lib().wc_synth_stream_rng_position(self._h, stream))
