@@ -14,3 +14,12 @@ d = np.diff(v, axis=1)
 for i, n in enumerate(names):
     print("  %-40s %9.0f" % (n, d[:, i].mean()))
 print("  %-40s %9.0f (voiced) %9.0f (all)" % ("total", (v[:, 10] - v[:, 0]).mean(), (a[:, 10] - a[:, 0]).mean()))
+# pulses without a periodic part (the unvoiced kernel of the split launch, and voiced pulses whose aperiodic_ratio[0] > 0.999):
+# stamps 2 .. 5 are never written, the noise phase runs from stamp 1
+n = a[a[:, 5] == 0]
+if len(n):
+    print("%d pulses without a periodic part (mean):" % len(n))
+    c = n[:, [1, 6, 7, 8, 9, 10]]
+    for i, name in enumerate(names[5:]):
+        print("  %-40s %9.0f" % (name, (c[:, i + 1] - c[:, i]).mean()))
+    print("  %-40s %9.0f" % ("total", (n[:, 10] - n[:, 0]).mean()))

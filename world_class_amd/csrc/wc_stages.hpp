@@ -53,6 +53,7 @@ wc::Device *hv_device(const wc_harvest *h);
 wc::Device *ct_device(const wc_cheaptrick *c);
 wc::Device *d4c_device(const wc_d4c *d);
 wc::Device *syn_device(const wc_synthesis *sy);
+bool syn_split(const wc_synthesis *sy);  // voiced and unvoiced pulses in a launch each (N = 2048 rows; WC_SYN_SPLIT=0: off)
 const double *syn_dc_remover(const wc_synthesis *sy);  // getDCRemover's table on the device (reference src/synthesis.cpp:290-303)
 int syn_fs(const wc_synthesis *sy);
 

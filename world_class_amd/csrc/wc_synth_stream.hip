@@ -246,7 +246,7 @@ struct wc_synth_stream {
 	wc_synthesis *sy;
 	std::vector<SsState> st;
 	int parity = 0;
-	DevBuf wf0[2], wsp[2], wap[2], carry[2], work, inc, pulses, resp, meta, owner, aux;
+	DevBuf wf0[2], wsp[2], wap[2], carry[2], work, inc, pulses, resp, meta, owner, aux, cls;
 	DevBuf dsp, dap;  // wc_synth_stream_push_coded_device: the pushed frames' decoded rows (max_frames x n_streams, on first use)
 	// a coded push with wc_synth_stream_set_modification settings: per-frame spectral ratios | F0 scales (2 x max_frames x n_streams,
 	// staged through h_mod, the coded push's own: the plain push behind it stages its metadata through h_stage) and the scaled F0
@@ -382,7 +382,7 @@ void wc_synth_stream_destroy(wc_synth_stream *s) {
 	s->dsp.release(); s->dap.release(); s->dmod.release(); s->sf0.release(); s->h_mod.release();
 	s->cf0.release(); s->csp.release(); s->cap.release(); s->rf0.release(); s->rsp.release(); s->rap.release(); s->drt.release(); s->h_rt.release();
 	s->tf0.release(); s->tcsp.release(); s->tcap.release();
-	s->work.release(); s->inc.release(); s->pulses.release(); s->resp.release(); s->meta.release(); s->owner.release(); s->aux.release(); s->h_stage.release();
+	s->work.release(); s->inc.release(); s->pulses.release(); s->resp.release(); s->meta.release(); s->owner.release(); s->aux.release(); s->cls.release(); s->h_stage.release();
 	wc_synthesis_destroy(s->sy);
 	delete s;
 }
@@ -698,6 +698,9 @@ static int ss_push_rows(wc_synth_stream *s, const int *n_frames, const int *flus
 		WC_HIP(hipMemcpyAsync(pu.p, owner.data(), sizeof(int) * (size_t)total_p, hipMemcpyHostToDevice, hs));
 		WC_HIP(hipMemsetAsync(pu.as<int>() + total_p, 0, sizeof(int) * (size_t)total_p, hs));
 		WC_HIP(hipStreamSynchronize(hs));  // (owner is a host vector)
+		// the class lists of the split launch (N = 2048 rows), sized for the whole push: a launch per stream uses their front
+		const bool split = N == 2048 && !atomic && syn_split(s->sy);
+		if (split && (rc = s->cls.reserve(sizeof(int) * syn_class_ints(total_p, na)))) return rc;
 		if (atomic) {
 			std::vector<OlDesc> ex(ol);
 			for (auto &d : ex) { d.dst_off = d.src_off / s->ccap * s->wsz; d.cut = d.lo; }
@@ -721,6 +724,7 @@ static int ss_push_rows(wc_synth_stream *s, const int *n_frames, const int *flus
 			sa.rng_table = s->dev->rng_table.as<uint32_t>(); sa.rng_base = s->dev->rng_base;
 			sa.pulse_utt = pu.as<int>();
 			sa.total_pulses = total_p;
+			if (split && (rc = syn_launch_class_lists(sa, s->cls.as<int>(), nullptr, hs))) return rc;
 			if ((rc = syn_launch_responses(N, sa, hs))) return rc;
 		} else {
 			// streams whose noise positions lie further apart than one draw table covers: one launch per stream, each with its own
@@ -734,6 +738,7 @@ static int ss_push_rows(wc_synth_stream *s, const int *n_frames, const int *flus
 				one.pulse_utt = pu.as<int>() + total_p;
 				one.resp = atomic ? nullptr : s->resp.as<double>() + prefix[a] * N;
 				one.total_pulses = n_syn[a];
+				if (split && (rc = syn_launch_class_lists(one, s->cls.as<int>(), nullptr, hs))) return rc;
 				if ((rc = syn_launch_responses(N, one, hs))) return rc;
 				WC_HIP(hipStreamSynchronize(hs));  // (the next stream's table replaces this one)
 			}

@@ -1171,6 +1171,9 @@ __device__ __forceinline__ void minimum_phase_wave(double (&mr)[16], double (&mi
 #ifndef WC_SYN_WAVE_OCC
 #define WC_SYN_WAVE_OCC 2
 #endif
+#ifndef WC_SYN_UNV_OCC
+#define WC_SYN_UNV_OCC 2  // wavefronts per SIMD of the unvoiced kernel (CLS = 2); 3: both halves of the noise spectrum wait in the pulse's row, no P in LDS (11.8 KB), but 168 registers hold the kernel only with 224 B of scratch (187 without a bound): 5.21 against 4.45 ms, profiles/syn_split_ab.txt
+#endif
 #ifndef WC_SYN_ROWS_G
 #define WC_SYN_ROWS_G 2
 #endif
@@ -1195,9 +1198,25 @@ __device__ __forceinline__ void minimum_phase_wave(double (&mr)[16], double (&mi
 // order: no row written and read (32 KB per pulse), no parked periodic half (16 KB), no second kernel; the sums then carry the
 // order in which the atomics land (1e-16 of a sample, not the same bits on every run).  Only the noise spectrum's imaginary parts
 // still wait in global memory (a row of 1024 doubles per pulse).
-template <bool ATOMIC>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WC_SYN_WAVE_OCC, WC_SYN_WAVE_OCC))) void syn_pulse_wave_kernel(SynArgs a) {
+//
+// CLS (the split launch, WC_SYN_SPLIT): 0 walks all pulses of the compact numbering; 1 the voiced and 2 the unvoiced pulses of the
+// class lists (syn_class_lists_kernel), one launch each.  The rows stay at resp + gp * N and the arithmetic that is kept is
+// operation for operation that of CLS = 0, so y carries the same bits.
+//   2: the aperiodic log spectrum of an unvoiced pulse is log(env) / 2 and it has no periodic response whatever aperiodic_ratio[0]
+//      is: the aperiodicity rows are never touched, there is no periodic part, no DC term and no parked half in the mix.  Its
+//      noise_size is fs / 500 = 96 for all but the last pulse in front of a voiced stretch: up to 128 draws only slot 0 of the
+//      strided input is non-zero, and the leading 16-point DFT of one non-zero input is that input in every output -- a copy.
+//   1: the four rows are fetched and blended ONCE, by the periodic part, which leaves the aperiodic part's log spectrum
+//      log(env ar) / 2 in P (idle until the noise spectrum is parked there); the aperiodic part swaps it against the noise
+//      spectrum's real parts, value by value.  Bin 1024 waits in the last double of L, which no exchange touches (the
+//      transforms' padded indices end at 1086).  A voiced pulse without a periodic part (aperiodic_ratio[0] > 0.999) has a
+//      single part, which reads the rows itself.
+template <bool ATOMIC, int CLS = 0>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CLS == 2 ? WC_SYN_UNV_OCC : WC_SYN_WAVE_OCC, CLS == 2 ? WC_SYN_UNV_OCC : WC_SYN_WAVE_OCC)))
+void syn_pulse_wave_kernel(SynArgs a) {
 	constexpr int N = 2048, M = 1024;
+	constexpr bool kRowsOnce = CLS == 1 && WC_SYN_PARK_NOISE;
+	constexpr bool kParkRow = CLS == 2 && WC_SYN_UNV_OCC > 2 && !ATOMIC;  // (P is then never referenced and takes no LDS)
 	__shared__ __attribute__((aligned(16))) double L[kWfLds];
 	__shared__ __attribute__((aligned(16))) double T[kWfTabLds];
 #if WC_SYN_PARK_NOISE
@@ -1208,10 +1227,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WC_SYN_WAVE_
 	__shared__ double PAD[WC_SYN_LDS_PAD];
 	if (a.fs < 0) PAD[lane] = 0.0;
 #endif
-	const long long total_p = a.pulse_prefix[a.n_utt];
+	// (CLS != 0: the place in the class list instead of the pulse number; the lists keep pulse order, so an XCD still walks neighbours)
+	const long long total_p = CLS == 0 ? a.pulse_prefix[a.n_utt] : (long long)a.cls_count[CLS - 1];
 	if ((long long)blockIdx.x >= 8 * ((total_p + 7) / 8)) return;
-	const long long gp = xcd_frame(blockIdx.x, total_p);
-	if (gp >= total_p) return;
+	const long long place = xcd_frame(blockIdx.x, total_p);
+	if (place >= total_p) return;
+	const long long gp = CLS == 0 ? place : (long long)a.cls_list[(CLS - 1) * a.total_pulses + place];
 	if (a.only_pulse >= 0 && gp != a.only_pulse) return;
 	const int u = a.pulse_utt[gp];  // (one load instead of a bisection of the prefix: a chain of dependent loads in front of everything)
 	wf_tables_to_lds(T, a.tw, lane);  // (requested first: in flight while the pulse's own data are looked up)
@@ -1220,7 +1241,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WC_SYN_WAVE_
 	const int pidx = a.p.index[slot];
 	const double shift = a.p.shift[slot];
 	const int noise_size = a.p.noise_size[slot];
-	const double vuv = (double)a.p.vuv[slot];
+	const double vuv = CLS == 0 ? (double)a.p.vuv[slot] : (CLS == 1 ? 1.0 : 0.0);
 	const int fs = a.fs, Lf = ud.f_len;
 	const double fp = a.frame_period;
 	const double t = pidx / (double)fs;  // time_axis[ii] (reference :227)
@@ -1246,8 +1267,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WC_SYN_WAVE_
 			ar = s * s;
 		}
 	};
-	double ar0;  // aperiodic_ratio[0] decides whether there is a periodic response (reference :410)
-	{
+	auto blend_env = [&](double s0, double s1) { return same ? fabs(s0) : fma(1.0 - ipol, fabs(s0), ipol * fabs(s1)); };  // (blend's env alone)
+	double ar0 = 1.0;  // aperiodic_ratio[0] decides whether there is a periodic response (reference :410)
+	if constexpr (CLS != 2) {
 		double env;
 		blend(sf[0], sc[0], af[0], ac[0], env, ar0);
 		ar0 = uniform_d(ar0);
@@ -1281,9 +1303,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WC_SYN_WAVE_
 		if (o >= 0 && o < ylen) atomicAdd(yout + o, v0);
 		if (o + 1 >= 0 && o + 1 < ylen) atomicAdd(yout + o + 1, v1);
 	};
-	const bool has_periodic = !(vuv <= 0.5 || ar0 > 0.999);
+	const bool has_periodic = CLS != 2 && !(vuv <= 0.5 || ar0 > 0.999);
+	const int part_first = (CLS == 2 || !has_periodic) ? 1 : 0;
 #pragma unroll 1
-	for (int part = has_periodic ? 0 : 1; part < 2; ++part) {
+	for (int part = part_first; part < 2; ++part) {
 		int ln = lane;
 		WC_FRESH(ln);
 		double wr[16], wi[16];
@@ -1292,8 +1315,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WC_SYN_WAVE_
 			// the noise (reference :514-530): noise_size draws from the pulse's place in the stream, mean removed
 			const unsigned long long rstart = a.rng_start ? a.rng_start[u] : ud.rng_pos;
 			const uint32_t *__restrict__ rng = a.rng_table + (rstart + (unsigned long long)(pidx - a.first_index[u]) - a.rng_base);
+			const bool slot0_only = CLS == 2 && noise_size <= 128;  // (wave-uniform)
 			double s = 0.0;
-			{
+			if (slot0_only) {
+				const int i0 = 2 * ln;
+				const uint32_t raw0 = rng[i0 < noise_size ? i0 : 0], raw1 = rng[i0 + 1 < noise_size ? i0 + 1 : 0];
+				nr[0] = ni[0] = 0.0;
+				if (i0 < noise_size) nr[0] = raw0 / 268435456.0 - 6.0;
+				if (i0 + 1 < noise_size) ni[0] = raw1 / 268435456.0 - 6.0;
+				s += nr[0] + ni[0];
+			} else {
 				uint32_t raw[32];
 #pragma unroll
 				for (int q = 0; q < 16; ++q) {
@@ -1316,15 +1347,23 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WC_SYN_WAVE_
 			}
 			s = wave_sum_all(s);
 			const double avg = s / noise_size;
+			if (slot0_only) {
+				const int i0 = 2 * ln;
+				nr[0] = (i0 < noise_size) ? nr[0] - avg : 0.0;
+				ni[0] = (i0 + 1 < noise_size) ? ni[0] - avg : 0.0;
 #pragma unroll
-			for (int q = 0; q < 16; ++q) {
-				const int i0 = 2 * ln + 128 * q;
-				nr[q] = (i0 < noise_size) ? nr[q] - avg : 0.0;
-				ni[q] = (i0 + 1 < noise_size) ? ni[q] - avg : 0.0;
+				for (int q = 1; q < 16; ++q) { nr[q] = nr[0]; ni[q] = ni[0]; }  // wdft16<+1, 1> of (x, 0, .., 0)
+			} else {
+#pragma unroll
+				for (int q = 0; q < 16; ++q) {
+					const int i0 = 2 * ln + 128 * q;
+					nr[q] = (i0 < noise_size) ? nr[q] - avg : 0.0;
+					ni[q] = (i0 + 1 < noise_size) ? ni[q] - avg : 0.0;
+				}
+				if (noise_size <= 512) wdft16<+1, 1>(nr, ni);
+				else if (noise_size <= 1024) wdft16<+1, 2>(nr, ni);
+				else wdft16<+1, 4>(nr, ni);
 			}
-			if (noise_size <= 512) wdft16<+1, 1>(nr, ni);
-			else if (noise_size <= 1024) wdft16<+1, 2>(nr, ni);
-			else wdft16<+1, 4>(nr, ni);
 			wf_fft1024_dit_rest<+1>(nr, ni, L, a.tw, ln);
 			wf_r2c_unpack(nr, ni, nsM, a.tw, ln);  // twice the noise spectrum
 			SYN_STAMP(6);
@@ -1332,21 +1371,49 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WC_SYN_WAVE_
 			// The noise spectrum waits outside the registers while the minimum phase is worked out (held, it pushes the two
 			// transforms in between over 256 registers: 368 bytes of scratch per lane, half the kernel's memory traffic): its real
 			// parts in LDS, its imaginary parts in the first half of the pulse's own response row (free until the mix below).
+			// (kRowsOnce: P holds this part's log spectrum, left by the periodic part; it moves to the transform's input as the
+			// noise spectrum takes its place, every lane on places of its own)
+			const bool swap = kRowsOnce && has_periodic;
+			if (swap) wf_fence();
 #pragma unroll
 			for (int sI = 0; sI < 16; ++sI) {
-				P[64 * sI + ln] = nr[sI];
+				if constexpr (kParkRow) {
+					resp[M + 64 * sI + ln] = nr[sI];  // (an unvoiced pulse parks no periodic half there)
+				} else {
+					if (swap) L[64 * sI + ln] = P[64 * sI + ln];
+					P[64 * sI + ln] = nr[sI];
+				}
 				resp[64 * sI + ln] = ni[sI];
 			}
+			if (swap && ln == 0) L[M] = L[kWfLds - 1];
 			wf_fence();
 #endif
 		}
 		// the part's log spectrum from the two rows around the pulse: log(env (1 - ar) + safeguard) / 2 for the periodic part
 		// (reference :416-417), log(env ar) / 2 or, unvoiced, log(env) / 2 for the aperiodic one (:490-497)
 		double mM;
-		{
+		if constexpr (CLS == 2) {
+			// (the spectrogram's two rows alone)
+#pragma unroll
+			for (int g0 = 0; g0 < 4; g0 += WC_SYN_ROWS_G) {
+				double v[4 * WC_SYN_ROWS_G][2];
+#pragma unroll
+				for (int q = 0; q < 4 * WC_SYN_ROWS_G; ++q) {
+					const int k = wf_bin(ln, g0 + (q >> 2), q & 3);
+					v[q][0] = sf[k]; v[q][1] = sc[k];
+				}
+				WF_SCHED_FENCE();
+#pragma unroll
+				for (int q = 0; q < 4 * WC_SYN_ROWS_G; ++q)
+					L[wf_bin(ln, g0 + (q >> 2), q & 3)] = wf_log_l(blend_env(v[q][0], v[q][1]), T) / 2.0;
+			}
+			const double lsM = wf_log_l(blend_env(sf[M], sc[M]), T) / 2.0;
+			if (ln == 0) L[M] = lsM;
+		} else if (!kRowsOnce || part == part_first) {
 			auto logspec = [&](double env, double ar) {
 				return wf_log_l(part == 0 ? env * (1.0 - ar) + kSafe : (vuv != 0.0 ? env * ar : env), T) / 2.0;
 			};
+			const bool both = kRowsOnce && part == 0;  // (the aperiodic part's log spectrum from the same env and ar, into P)
 #pragma unroll
 			for (int g0 = 0; g0 < 4; g0 += WC_SYN_ROWS_G) {
 				// (the rows of WC_SYN_ROWS_G groups of four bins requested together: the first touch of a pulse's rows is an HBM round
@@ -1363,12 +1430,19 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WC_SYN_WAVE_
 					double env, ar;
 					blend(v[q][0], v[q][1], v[q][2], v[q][3], env, ar);
 					L[wf_bin(ln, g0 + (q >> 2), q & 3)] = logspec(env, ar);  // (straight to its place in the transform's input)
+#if WC_SYN_PARK_NOISE
+					if (both) P[wf_bin(ln, g0 + (q >> 2), q & 3)] = wf_log_l(env * ar, T) / 2.0;
+#endif
 				}
 			}
 			double env, ar;
 			blend(sf[M], sc[M], af[M], ac[M], env, ar);
 			const double lsM = logspec(env, ar);
 			if (ln == 0) L[M] = lsM;
+			if (both) {
+				const double lsM1 = wf_log_l(env * ar, T) / 2.0;
+				if (ln == 0) L[kWfLds - 1] = lsM1;
+			}
 		}
 		SYN_STAMP(part ? 7 : 2);
 		minimum_phase_wave(wr, wi, mM, L, T, a.tw, ln);
@@ -1400,7 +1474,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WC_SYN_WAVE_
 #pragma unroll
 				for (int sI = 0; sI < 16; ++sI) {
 					ni[sI] = rp[64 * sI + ln];
-					nr[sI] = P[64 * sI + ln];
+					if constexpr (kParkRow) nr[sI] = rp[M + 64 * sI + ln];
+					else nr[sI] = P[64 * sI + ln];
 				}
 				WF_SCHED_FENCE();
 			}
@@ -1453,6 +1528,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WC_SYN_WAVE_
 						add2(pidx + 1 + n, fma(dcs, dr[q].x, wr[q0 + q]) / N, fma(dcs, dr[q].y, wi[q0 + q]) / N);
 						add2(pidx + 1 - M + n, fma(dcs, dr[q].x, wr[q0 + q + 8]) / N, fma(dcs, dr[q].y, wi[q0 + q + 8]) / N);
 					}
+				}
+			} else if constexpr (CLS == 2) {
+				// (no DC term and no parked half: fma(0, remover, w) + 0 is w)
+#pragma unroll
+				for (int q = 0; q < 8; ++q) {
+					const int n = 2 * ln + 128 * q;
+					*reinterpret_cast<double2 *>(resp + n + M) = make_double2(wr[q] / N, wi[q] / N);
+					*reinterpret_cast<double2 *>(resp + n) = make_double2(wr[q + 8] / N, wi[q + 8] / N);
 				}
 			} else
 #pragma unroll
@@ -1768,6 +1851,76 @@ __global__ void syn_pulse_utt_kernel(const long long *__restrict__ prefix, int *
 	for (long long g = lo + threadIdx.x; g < hi; g += blockDim.x) pulse_utt[g] = u;
 }
 
+// The class lists of the split launch (syn_pulse_wave_kernel<., 1 / 2>): a stable partition of the compact pulse numbers by vuv, in
+// two steps of one workgroup per utterance.  First the utterance's voiced pulses are counted (and, where asked, pulse_utt filled:
+// what syn_pulse_utt_kernel does); then every workgroup sums the counts of the utterances in front of its own and deals its
+// pulses to the two lists in pulse order, 256 at a time (ballot ranks inside a wavefront, the wavefronts' counts through LDS).
+// The counts stay on the device: cls_count[0] voiced, cls_count[1] unvoiced pulses.
+constexpr int CL_T = 256;
+__global__ __launch_bounds__(CL_T) void syn_class_count_kernel(const long long *__restrict__ prefix, const long long *__restrict__ cap_off,
+															   const int *__restrict__ vuv, int *__restrict__ pulse_utt, int *__restrict__ voiced) {
+	__shared__ int tot;
+	const int u = blockIdx.x;
+	const long long lo = prefix[u];
+	const int n = (int)(prefix[u + 1] - lo);
+	const int *__restrict__ v = vuv + cap_off[u];
+	if (threadIdx.x == 0) tot = 0;
+	__syncthreads();
+	int c = 0;
+	for (int i = threadIdx.x; i < n; i += CL_T) {
+		c += v[i] != 0;
+		if (pulse_utt) pulse_utt[lo + i] = u;
+	}
+	if (c) atomicAdd(&tot, c);
+	__syncthreads();
+	if (threadIdx.x == 0) voiced[u] = tot;
+}
+__global__ __launch_bounds__(CL_T) void syn_class_lists_kernel(int n_utt, const long long *__restrict__ prefix, const long long *__restrict__ cap_off,
+															   const int *__restrict__ vuv, const int *__restrict__ voiced, long long cap,
+															   int *__restrict__ list, int *__restrict__ count) {
+	__shared__ int front, all, wv[CL_T / 64];
+	const int u = blockIdx.x, tid = threadIdx.x, w = tid >> 6;
+	const long long lo = prefix[u];
+	const int n = (int)(prefix[u + 1] - lo);
+	const int *__restrict__ v = vuv + cap_off[u];
+	if (tid == 0) front = all = 0;
+	__syncthreads();
+	{
+		int f = 0, t = 0;
+		for (int k = tid; k < n_utt; k += CL_T) {
+			const int c = voiced[k];
+			t += c;
+			if (k < u) f += c;
+		}
+		if (f) atomicAdd(&front, f);
+		if (t) atomicAdd(&all, t);
+	}
+	__syncthreads();
+	if (u == 0 && tid == 0) {
+		count[0] = all;
+		count[1] = (int)(prefix[n_utt] - all);
+	}
+	long long at_v = front, at_u = cap + (lo - front);  // the next free place of either list
+	for (int base = 0; base < n; base += CL_T) {
+		const int i = base + tid;
+		const bool in = i < n, vo = in && v[i] != 0;
+		const unsigned long long b = __ballot(vo);
+		if ((tid & 63) == 0) wv[w] = __popcll(b);
+		__syncthreads();
+		int rank = __popcll(b & ((1ull << (tid & 63)) - 1ull)), chunk_v = 0;  // voiced pulses of the chunk in front of this one
+#pragma unroll
+		for (int k = 0; k < CL_T / 64; ++k) {
+			if (k < w) rank += wv[k];
+			chunk_v += wv[k];
+		}
+		if (vo) list[at_v + rank] = (int)(lo + i);
+		else if (in) list[at_u + (tid - rank)] = (int)(lo + i);
+		at_v += chunk_v;
+		at_u += CL_T - chunk_v;  // (only the last chunk is short, and nothing follows it)
+		__syncthreads();
+	}
+}
+
 // Overlap-add of the response rows (reference :118-139: y[index + 1 + j] += response[j], pulse after pulse).  One workgroup per
 // tile of OA_TILE output samples: the pulses that reach into the tile are a contiguous run of the utterance's (sorted) pulse
 // list, found by bisection; every thread adds the rows' samples to its four outputs in pulse order, so y carries the
@@ -1835,11 +1988,12 @@ struct wc_synthesis {
 	hipStream_t s_twin = nullptr;
 	hipEvent_t e_twin = nullptr;
 	bool is_twin = false;
-	DevBuf dc_remover, utts, meta, pulses, incs, phase, phase_seg, tile_cnt, resp, pulse_utt, d_f0, d_sp, d_ap, d_out;
+	DevBuf dc_remover, utts, meta, pulses, incs, phase, phase_seg, tile_cnt, resp, pulse_utt, cls, d_f0, d_sp, d_ap, d_out;
 	bool pulses_by_utterance;  // WC_SYN_PULSES=utterance: one workgroup walks an utterance's tiles (A/B and the bit-identity test)
 	bool wave;  // N = 2048 / 1024: one wavefront per pulse (default; WC_SYN_IMPL=block: the workgroup-per-pulse kernel)
 	bool rows = false;  // of the most recent syn_prepare: pulses through response rows + syn_overlap_add_kernel (else atomics into the output)
 	bool wave_atomic = false;  // WC_SYN_OLA=atomic: the one-wavefront kernel (N = 2048) adds into the output itself (A/B variant)
+	bool split = true;  // N = 2048 rows: voiced and unvoiced pulses in a launch each (WC_SYN_SPLIT=0: one launch, the A/B and bit-identity twin)
 	size_t rows_budget = 0;  // bytes the response rows may take (an eighth of the device's memory; WC_SYN_ROWS_BUDGET_MB)
 	bool phase_single;  // WC_SYN_PHASE=single: the phase sum by one workgroup per utterance (A/B and the bit-identity test)
 	bool serial_timebase;  // WC_SYN_TIMEBASE=serial: the one-wavefront sequential accumulation instead of the exact parallel one
@@ -1860,6 +2014,18 @@ static void launch_pulses(const SynArgs &a, hipStream_t s) {
 	hipLaunchKernelGGL((syn_pulse_kernel<N, TP>), dim3((unsigned)(8 * ((a.total_pulses + 7) / 8))), dim3(TP), 0, s, a);
 }
 
+// the N = 2048 rows kernel: one launch per class list where the caller has built them (voiced first), else one over all pulses; the
+// grids are sized by the capacity, the blocks beyond a list's count leave
+static void launch_pulse_waves(const SynArgs &a, hipStream_t s) {
+	const dim3 grid((unsigned)(8 * ((a.total_pulses + 7) / 8)));
+	if (a.cls_list) {
+		hipLaunchKernelGGL((syn_pulse_wave_kernel<false, 1>), grid, dim3(64), 0, s, a);
+		hipLaunchKernelGGL((syn_pulse_wave_kernel<false, 2>), grid, dim3(64), 0, s, a);
+	} else {
+		hipLaunchKernelGGL((syn_pulse_wave_kernel<false, 0>), grid, dim3(64), 0, s, a);
+	}
+}
+
 int wc::syn_launch_responses(int fft_size, const SynArgs &a, hipStream_t s) {
 	switch (fft_size) {
 		case 512: launch_pulses<512>(a, s); break;
@@ -1868,11 +2034,23 @@ int wc::syn_launch_responses(int fft_size, const SynArgs &a, hipStream_t s) {
 			hipLaunchKernelGGL(syn_pulse_wave8_kernel, dim3((unsigned)(8 * ((per + kSyn8Waves - 1) / kSyn8Waves))), dim3(64 * kSyn8Waves), 0, s, a);
 			break;
 		}
-		case 2048: hipLaunchKernelGGL(syn_pulse_wave_kernel<false>, dim3((unsigned)(8 * ((a.total_pulses + 7) / 8))), dim3(64), 0, s, a); break;
+		case 2048: launch_pulse_waves(a, s); break;
 		case 4096: launch_pulses<4096>(a, s); break;
 		default: return fail(WC_ERR_UNSUPPORTED, "synthesis: fft_size must be 512, 1024, 2048 or 4096");
 	}
 	WC_HIP(hipGetLastError());
+	return WC_OK;
+}
+
+size_t wc::syn_class_ints(long long total_pulses, int n_utt) { return 2 * (size_t)total_pulses + 2 + (size_t)n_utt; }
+int wc::syn_launch_class_lists(SynArgs &a, int *buf, int *pulse_utt, hipStream_t s) {
+	int *count = buf + 2 * a.total_pulses, *voiced = count + 2;
+	hipLaunchKernelGGL(syn_class_count_kernel, dim3(a.n_utt), dim3(CL_T), 0, s, a.pulse_prefix, a.cap_off, (const int *)a.p.vuv, pulse_utt, voiced);
+	hipLaunchKernelGGL(syn_class_lists_kernel, dim3(a.n_utt), dim3(CL_T), 0, s, a.n_utt, a.pulse_prefix, a.cap_off, (const int *)a.p.vuv,
+					   (const int *)voiced, a.total_pulses, buf, count);
+	WC_HIP(hipGetLastError());
+	a.cls_list = buf;
+	a.cls_count = count;
 	return WC_OK;
 }
 
@@ -2065,6 +2243,7 @@ int syn_pulses(wc_synthesis *sy, hipStream_t s, const double *d_f0, const double
 	a.trace = nullptr;
 	a.resp = nullptr;
 	a.pulse_utt = nullptr;
+	a.cls_list = a.cls_count = nullptr;
 	if (sy->rows) {
 		// a response row per pulse slot of the rate bound (only the rows of real pulses are ever touched)
 		const bool atomic_rows = sy->wave_atomic && sy->fft_size == 2048;  // (only the parked noise half then: 1024 doubles per pulse)
@@ -2072,7 +2251,12 @@ int syn_pulses(wc_synthesis *sy, hipStream_t s, const double *d_f0, const double
 		a.resp = sy->resp.as<double>();
 		if ((rc = sy->pulse_utt.reserve(sizeof(int) * (size_t)co))) return rc;
 		a.pulse_utt = sy->pulse_utt.as<int>();
-		hipLaunchKernelGGL(syn_pulse_utt_kernel, dim3(n_utt), dim3(256), 0, s, (const long long *)d_prefix, sy->pulse_utt.as<int>());
+		if (sy->split && sy->fft_size == 2048 && !sy->wave_atomic) {
+			if ((rc = sy->cls.reserve(sizeof(int) * syn_class_ints(co, n_utt)))) return rc;
+			if ((rc = syn_launch_class_lists(a, sy->cls.as<int>(), sy->pulse_utt.as<int>(), s))) return rc;
+		} else {
+			hipLaunchKernelGGL(syn_pulse_utt_kernel, dim3(n_utt), dim3(256), 0, s, (const long long *)d_prefix, sy->pulse_utt.as<int>());
+		}
 	}
 #if WC_SYN_TRACE
 	static DevBuf tracebuf;
@@ -2097,7 +2281,7 @@ int syn_pulses(wc_synthesis *sy, hipStream_t s, const double *d_f0, const double
 				if (sy->wave_atomic) {
 					hipLaunchKernelGGL(syn_pulse_wave_kernel<true>, dim3((unsigned)(8 * ((a.total_pulses + 7) / 8))), dim3(64), 0, s, a);
 				} else {
-					hipLaunchKernelGGL(syn_pulse_wave_kernel<false>, dim3((unsigned)(8 * ((a.total_pulses + 7) / 8))), dim3(64), 0, s, a);
+					launch_pulse_waves(a, s);
 					hipLaunchKernelGGL(syn_overlap_add_kernel<2048>, dim3((unsigned)((sy->max_out + OA_TILE - 1) / OA_TILE), n_utt), dim3(OA_T), 0, s, a);
 				}
 			} else {
@@ -2224,6 +2408,7 @@ static int syn_run_device(wc_synthesis *sy, int n_utt, const double *d_f0, const
 wc::Device *syn_device(const wc_synthesis *sy) { return sy->dev; }
 int syn_fs(const wc_synthesis *sy) { return sy->fs; }
 const double *syn_dc_remover(const wc_synthesis *sy) { return sy->dc_remover.as<double>(); }
+bool syn_split(const wc_synthesis *sy) { return sy->split; }
 
 extern "C" {
 
@@ -2250,6 +2435,8 @@ wc_synthesis *wc_synthesis_create(int fs, int fft_size, double frame_period_ms) 
 		s->wave = !(impl && std::string(impl) == "block");
 		const char *ola = getenv("WC_SYN_OLA");
 		s->wave_atomic = ola && std::string(ola) == "atomic";
+		const char *sp = getenv("WC_SYN_SPLIT");
+		s->split = !(sp && sp[0] == '0');
 		size_t free_b = 0, total_b = 0;
 		if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) total_b = (size_t)64 << 30;
 		s->rows_budget = total_b / 8;
@@ -2280,7 +2467,7 @@ void wc_synthesis_destroy(wc_synthesis *s) {
 	if (s->twin) wc_synthesis_destroy(s->twin);
 	if (s->s_twin) (void)hipStreamDestroy(s->s_twin);
 	if (s->e_twin) (void)hipEventDestroy(s->e_twin);
-	s->dc_remover.release(); s->utts.release(); s->meta.release(); s->pulses.release(); s->incs.release(); s->phase.release(); s->tile_cnt.release(); s->phase_seg.release(); s->resp.release(); s->pulse_utt.release();
+	s->dc_remover.release(); s->utts.release(); s->meta.release(); s->pulses.release(); s->incs.release(); s->phase.release(); s->tile_cnt.release(); s->phase_seg.release(); s->resp.release(); s->pulse_utt.release(); s->cls.release();
 	s->d_f0.release(); s->d_sp.release(); s->d_ap.release(); s->d_out.release(); s->h_stage.release(); s->h_rows.release();
 	s->dec_sp.release(); s->dec_ap.release();
 	s->rt_f0.release(); s->rt_sp.release(); s->rt_ap.release();

@@ -157,6 +157,9 @@ struct SynArgs {
 	const double *dc_remover;
 	double *out;
 	const int *pulse_utt;  // the one-wavefront kernel: utterance of every pulse of the compact numbering (syn_pulse_utt_kernel)
+	// the split launch of the N = 2048 kernel (syn_launch_class_lists; NULL: one launch over all pulses): the compact numbers of the
+	// voiced pulses at cls_list[0 ..), of the unvoiced ones at cls_list[total_pulses ..), each in pulse order; cls_count[2]
+	const int *cls_list, *cls_count;
 	double *resp;  // the one-wavefront kernel: [pulse][N] responses in output order, summed by syn_overlap_add_kernel (NULL: atomics into out)
 	long long total_pulses;  // launch size (capacity); the real count is pulse_prefix[n_utt]
 	const unsigned long long *rng_start;  // per-utterance stream position (device), NULL = utts[u].rng_pos
@@ -169,6 +172,11 @@ struct SynArgs {
 // The per-pulse response kernels of wc_synthesis.hip for a pulse list that is already complete (index, shift, noise_size, vuv,
 // pulse_prefix, first_index): N = 1024 / 2048 write a response row per pulse to a.resp (a.pulse_utt filled), which the caller
 // sums in pulse order; N = 512 / 4096 add into a.out + utts[u].y_off with FP64 atomics (samples 0 <= o < y_len).
+// (N = 2048 with a.cls_list set: one launch per class, voiced first)
 int syn_launch_responses(int fft_size, const SynArgs &a, hipStream_t s);
+// The class lists of a complete pulse list, on the device (enqueue only): fills buf (syn_class_ints(a.total_pulses, a.n_utt) ints)
+// and points a.cls_list / a.cls_count into it; pulse_utt != NULL: filled as well (what syn_pulse_utt_kernel does).
+size_t syn_class_ints(long long total_pulses, int n_utt);
+int syn_launch_class_lists(SynArgs &a, int *buf, int *pulse_utt, hipStream_t s);
 
 }  // namespace wc
