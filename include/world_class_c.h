@@ -182,6 +182,21 @@ int wc_synthesis_compute_coded_retimed_device(wc_synthesis *s, int n_utt, const 
                                               const int *frames_out, const double *d_position, const double *d_f0_scale,
                                               const double *d_spectral_ratio, const int *out_length, double *d_out,
                                               uint64_t *rng_pos);
+/* Two voices morphed on their way: both sources -- d_f0_a with a_length[u] frames per utterance and its coded rows, the same for B,
+ * both coded with number_of_dimensions coefficients -- are decoded (the unmodified decoder) into the handle's scratch, blended by
+ * wc_morph_parameters_device (world_class_io.h) into frames_out[u] frames per utterance at d_position_a / d_position_b with
+ * d_weight, d_f0_weight, d_ratio_a, d_ratio_b (one value per OUTPUT frame; the last three may be NULL) in the retimed call's scratch
+ * rows, and synthesised as above on frames_out[u] frames, to which out_length[u] refers: the samples, the noise draws and rng_pos
+ * are those of wc_decode_features_device twice -> wc_morph_parameters_device -> wc_synthesis_compute_device.  Refused like the coded
+ * retimed call (either source's length or frames_out[u] below 2 included); a refused call leaves rng_pos and d_out alone.  The
+ * scratch -- (frames of A + frames of B + frames out) x (fft_size/2+1) doubles twice -- grows on demand and goes with the handle. */
+int wc_synthesis_compute_coded_morphed_device(wc_synthesis *s, int n_utt, const double *d_f0_a, const int *a_length,
+                                              const double *d_coded_sp_a, const double *d_coded_ap_a, const double *d_f0_b,
+                                              const int *b_length, const double *d_coded_sp_b, const double *d_coded_ap_b,
+                                              int number_of_dimensions, const int *frames_out, const double *d_position_a,
+                                              const double *d_position_b, const double *d_weight, const double *d_f0_weight,
+                                              const double *d_ratio_a, const double *d_ratio_b, const int *out_length,
+                                              double *d_out, uint64_t *rng_pos);
 /* The same from host arrays: f0[u] (f0_length[u] doubles), coded_sp[u] (f0_length[u] x number_of_dimensions), coded_ap[u]
  * (f0_length[u] x GetNumberOfAperiodicities(fs)) -- what wc_pipeline_run_batch_host_coded returns -- gathered into page-locked
  * staging and sent up in one copy; y[u]: out_length[u] doubles, or int16 quantised like the reference's wavwrite when

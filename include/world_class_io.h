@@ -95,6 +95,41 @@ int wc_retime_parameters_device(int fs, int fft_size, int n_utt, const int *in_l
 								const double *d_ap_in, const int *out_length, const double *d_position, const double *d_f0_scale,
 								const double *d_spectral_ratio, double *d_f0_out, double *d_sp_out, double *d_ap_out);
 
+/* ---- voice morphing --------------------------------------------------------------------------------------------------- */
+/* Two parameter sets blended along two time maps, out of place.  Pair u has a_length[u] source frames of A, b_length[u] of B and
+ * gets out_length[u] output frames (host arrays; the device arrays are packed in pair order as for wc_retime_parameters_device:
+ * source frames of A for A's inputs, source frames of B for B's, output frames for d_position_a, d_position_b, d_weight,
+ * d_f0_weight, d_ratio_a, d_ratio_b and the outputs).  Output frame k has pa = d_position_a[k], pb = d_position_b[k], w =
+ * d_weight[k] and wf = d_f0_weight[k] (NULL: wf = w):
+ *   pa, pb or w not finite: F0 and both rows of that frame are NaN, no other frame is touched; only wf not finite: only that
+ *   frame's F0 is NaN;
+ *   A_k = the frame (F0, sp row, ap row) wc_retime_parameters_device forms from A at pa without scale or ratio, B_k the same from B
+ *   at pb: the end frames are held, a whole position copies, otherwise two products and one sum, F0 voiced where Synthesis'
+ *   interpolated voicing is -- that rule and its bits;
+ *   ap: w == 0: A_k's row, w == 1: B_k's row, both bit for bit; else (1 - w) * apA + w * apB (two products and one sum, each
+ *   rounded; what a weight outside [0, 1] puts outside [0, 1] is left to Synthesis' own clamp, as in retime);
+ *   sp: la(b) is the log envelope of A_k at bin b: log(spA[b]) where d_ratio_a is NULL or 0 for this frame; with a valid ratio the
+ *   value whose exp wc_modify_parameters_frames_device writes for that row and ratio (log -> interp1 from the stretched axis; for
+ *   a ratio below 1 the bins from cut = int(fft_size / 2.0 * ratio) upward repeat the value of bin cut - 1); lb(b) the same for B
+ *   with d_ratio_b.  An invalid ratio of EITHER source (negative, NaN, infinite, 0 < ratio < 2.0 / fft_size) makes the sp row NaN
+ *   whatever the weight; F0 and ap of that frame are unaffected, as in retime.  w == 0: the row wc_retime_parameters_device writes
+ *   for A with that ratio, w == 1: the same for B, both bit for bit; else sp[b] = exp((1 - w) * la(b) + w * lb(b)) (two products,
+ *   one sum, one exp);
+ *   F0, with fA, fB the retimed values: wf == 0: fA, wf == 1: fB, both bit for bit; both voiced: exp((1 - wf) * log fA + wf *
+ *   log fB); neither: 0; only A voiced: fA while wf < 0.5, else 0; only B voiced: fB while wf > 0.5, else 0 -- the nearer-source
+ *   rule of retime across the two voices: F0 never glides towards 0 Hz.
+ * Weights need not lie in [0, 1] (extrapolation), positions need not be monotone, out_length has no relation to the source
+ * lengths.  Each of the triples (d_f0_a, d_f0_b, d_f0_out), (d_sp_a, d_sp_b, d_sp_out), (d_ap_a, d_ap_b, d_ap_out) may be NULL
+ * together: that part is skipped.  Refused (WC_ERR_INVALID, nothing written): fft_size other than 512 / 1024 / 2048 / 4096, fs <=
+ * 0, n_pairs < 0, a negative length, out_length[u] > 0 with a_length[u] < 1 or b_length[u] < 1, more than 2^32 - 1 frames in all
+ * on any side, NULL lengths, positions or weight with frames to write, a triple that is only partly NULL, an output equal to one
+ * of its inputs.  out_length[u] == 0 and n_pairs == 0 write nothing.  Stream-ordered, enqueue-only. */
+int wc_morph_parameters_device(int fs, int fft_size, int n_pairs, const int *a_length, const double *d_f0_a, const double *d_sp_a,
+							   const double *d_ap_a, const int *b_length, const double *d_f0_b, const double *d_sp_b,
+							   const double *d_ap_b, const int *out_length, const double *d_position_a, const double *d_position_b,
+							   const double *d_weight, const double *d_f0_weight, const double *d_ratio_a, const double *d_ratio_b,
+							   double *d_f0_out, double *d_sp_out, double *d_ap_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -63,6 +63,8 @@ _SIGNATURES = {
     "wc_synthesis_compute_coded_device": (C.c_int, [_vp, C.c_int, _vp, _ip, _vp, C.c_int, _vp, _ip, _vp, _u64p]),
     "wc_synthesis_compute_coded_modified_device": (C.c_int, [_vp, C.c_int, _vp, _ip, _vp, C.c_int, _vp, _vp, _ip, _vp, _u64p]),
     "wc_synthesis_compute_coded_retimed_device": (C.c_int, [_vp, C.c_int, _vp, _ip, _vp, C.c_int, _vp, _ip, _vp, _vp, _vp, _ip, _vp, _u64p]),
+    "wc_synthesis_compute_coded_morphed_device": (C.c_int, [_vp, C.c_int, _vp, _ip, _vp, _vp, _vp, _ip, _vp, _vp, C.c_int, _ip, _vp, _vp, _vp, _vp,
+                                                            _vp, _vp, _ip, _vp, _u64p]),
     "wc_synthesis_run_batch_host_coded": (C.c_int, [_vp, C.c_int, C.POINTER(_vp), _ip, C.POINTER(_vp), C.c_int, C.POINTER(_vp), _ip,
                                                     C.POINTER(_vp), C.c_int, _u64p]),
     "wc_pipeline_create": (_vp, [C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_double]),

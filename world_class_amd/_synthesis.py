@@ -85,6 +85,22 @@ class Synthesis:
         return self._coded_device(lib().wc_synthesis_compute_coded_retimed_device, d_f0, f0_lengths, d_coded_sp, number_of_dimensions, d_coded_ap,
                                   (_ints(frames_out), _ptr(d_position), _opt(d_f0_scale), _opt(d_spectral_ratio)), out_lengths, d_out, rng_pos)
 
+    def compute_coded_morphed_device(self, d_f0_a, a_lengths, d_coded_sp_a, d_coded_ap_a, d_f0_b, b_lengths, d_coded_sp_b, d_coded_ap_b,
+                                     number_of_dimensions, frames_out, d_position_a, d_position_b, d_weight, d_f0_weight, d_ratio_a, d_ratio_b,
+                                     out_lengths, d_out, rng_pos=None):
+        """wc_synthesis_compute_coded_morphed_device: two voices from coded features, blended frame by frame as by
+        io.morph_parameters_device -- frames_out[u] output frames per utterance at d_position_a / d_position_b with d_weight
+        (d_f0_weight, d_ratio_a, d_ratio_b: None = none) -- and synthesised; out_lengths refer to frames_out"""
+        n = len(frames_out)
+        if not (len(a_lengths) == len(b_lengths) == n):
+            raise ValueError("Synthesis.compute_coded_morphed_device: a_lengths, b_lengths and frames_out must have one entry per utterance each")
+        arr, arg = _rng_arg(rng_pos, n)
+        _check(lib().wc_synthesis_compute_coded_morphed_device(
+            self._h, n, _ptr(d_f0_a), _ints(a_lengths), _ptr(d_coded_sp_a), _ptr(d_coded_ap_a), _ptr(d_f0_b), _ints(b_lengths), _ptr(d_coded_sp_b),
+            _ptr(d_coded_ap_b), int(number_of_dimensions), _ints(frames_out), _ptr(d_position_a), _ptr(d_position_b), _ptr(d_weight),
+            _opt(d_f0_weight), _opt(d_ratio_a), _opt(d_ratio_b), _ints(out_lengths), _ptr(d_out), arg))
+        return list(arr) if arr is not None else None
+
     def _coded_args(self, f0, csp, cap, what):
         from .codec import number_of_aperiodicities
         f, csp, cap = _c(f0), _c(csp), _c(cap)

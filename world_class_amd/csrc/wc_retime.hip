@@ -13,7 +13,8 @@
 //     wc_stretch.hpp: the rule of stretch_kernel, wc_io.hip) before its one write.
 //   retime_stream_kernel<STRETCH>   the same frame for the synthesis streams (wc_synth_stream_set_speed): positions in absolute source
 //     frames of a stream, the source rows those of one push plus one carried row per stream; it also keeps each stream's newest
-//     source row for the next push.  rt_pair / rt_row / rt_f0 / rt_stretched_row are shared by both kernels.
+//     source row for the next push.  rt_pair / rt_row / rt_f0 / rt_stretched_row (wc_retime_rows.hpp) are shared by both kernels
+//     and by morph_kernel (wc_morph.hip).
 //   A workgroup of retime_kernel finds its utterance by bisection in the descriptors (one of retime_stream_kernel reads its stream's
 //   index from a per-frame array of the host), which go up through page-locked staging kept per
 //   (device, stream): a call only enqueues.
@@ -26,13 +27,12 @@
 
 #include "../../include/world_class_c.h"
 #include "../../include/world_class_io.h"
+#include "wc_retime_rows.hpp"
 #include "wc_stages.hpp"
 
 using namespace wc;
 
 namespace {
-
-constexpr int RT_T = 256;
 
 struct RtUtt {
 	long long in_off, out_off;  // first source / output frame in the packed arrays
@@ -55,65 +55,12 @@ struct RtStreamArgs {
 	double *f0_out, *sp_out, *ap_out;
 };
 
-typedef double d2u __attribute__((ext_vector_type(2), aligned(8)));  // two bins of a row: 16 bytes at the row's 8-byte alignment
-
-// the two source bins b, b + 1 of the frame: row ri, or (1 - a) * ri + a * rj (two products and one sum, each rounded)
-__device__ __forceinline__ d2u rt_pair(const double *__restrict__ ri, const double *__restrict__ rj, double w0, double a, int b) {
-	d2u x = *reinterpret_cast<const d2u *>(ri + b);
-	if (a > 0.0) {
-		const d2u y = *reinterpret_cast<const d2u *>(rj + b);
-		x = w0 * x + a * y;
-	}
-	return x;
-}
-__device__ __forceinline__ double rt_one(const double *__restrict__ ri, const double *__restrict__ rj, double w0, double a, int b) {
-	return a > 0.0 ? w0 * ri[b] + a * rj[b] : ri[b];
-}
-
-__device__ __forceinline__ void rt_row(const double *__restrict__ ri, const double *__restrict__ rj, double w0, double a,
-									   double *__restrict__ out, int bins, int tid) {
-	for (int t = tid; t < bins / 2; t += RT_T) *reinterpret_cast<d2u *>(out + 2 * t) = rt_pair(ri, rj, w0, a, 2 * t);
-	if (tid == 0) out[bins - 1] = rt_one(ri, rj, w0, a, bins - 1);
-}
-__device__ __forceinline__ void rt_nan_row(double *__restrict__ out, int bins, int tid) {
-	for (int b = tid; b < bins; b += RT_T) out[b] = __builtin_nan("");
-}
-
-// the frame's F0: voiced exactly where Synthesis' own interpolated voicing is (the rule of tests/retime_rule.py)
-__device__ __forceinline__ double rt_f0(double fi, double fj, double w0, double a) {
-	const bool vi = fi != 0.0, vj = fj != 0.0;
-	if (!(a > 0.0)) return fi;
-	if (vi && vj) return w0 * fi + a * fj;
-	if (vi) return a < 0.5 ? fi : 0.0;
-	if (vj) return a > 0.5 ? fj : 0.0;
-	return 0.0;
-}
-
-// the interpolated row of sp to LDS as its logarithm, stretched by a valid ratio (wc::stretched_bin) before its one write
-__device__ __forceinline__ void rt_stretched_row(const double *__restrict__ ri, const double *__restrict__ rj, double w0, double a,
+// the stretched row on this translation unit's one LDS row (rt_stretched_row, wc_retime_rows.hpp)
+__device__ __forceinline__ void rt_stretched_row_tu(const double *__restrict__ ri, const double *__restrict__ rj, double w0, double a,
 												 double *__restrict__ out, double ratio, int fs, int fft_size, int tid) {
 	__shared__ double lg[kMaxBins];
 	__shared__ double fill;
-	const int bins = fft_size / 2 + 1;
-	for (int t = tid; t < bins / 2; t += RT_T) {
-		const d2u x = rt_pair(ri, rj, w0, a, 2 * t);
-		lg[2 * t] = log(x.x);
-		lg[2 * t + 1] = log(x.y);
-	}
-	if (tid == 0) lg[bins - 1] = log(rt_one(ri, rj, w0, a, bins - 1));
-	__syncthreads();
-	const int cut = static_cast<int>(fft_size / 2.0 * ratio);  // >= 1 for a valid ratio
-	const int top = ratio < 1.0 ? cut : bins;                 // bins from `cut` upward repeat bin cut - 1
-	for (int b = tid; b < top; b += RT_T) {
-		const double v = stretched_bin(b, ratio, fs, fft_size, [&](int k) { return lg[k]; });
-		out[b] = v;
-		if (b == top - 1) fill = v;
-	}
-	if (top < bins) {
-		__syncthreads();
-		const double f = fill;
-		for (int b = top + tid; b < bins; b += RT_T) out[b] = f;
-	}
+	rt_stretched_row(ri, rj, w0, a, out, ratio, fs, fft_size, tid, lg, &fill);
 }
 
 template <bool STRETCH>
@@ -128,14 +75,10 @@ __global__ __launch_bounds__(RT_T) void retime_kernel(RtArgs A) {
 	}
 	const RtUtt u = A.utts[lo];
 	const int bins = A.fft_size / 2 + 1;
-	const double pos = A.pos[g];
-	const bool finite = pos >= -1.7976931348623157e308 && pos <= 1.7976931348623157e308;
-	double p = pos < 0.0 ? 0.0 : pos;
-	p = p > u.n - 1 ? u.n - 1 : p;
-	const int i = finite ? static_cast<int>(floor(p)) : 0;
-	const double a = finite ? p - i : 0.0;
-	const int j = a > 0.0 ? i + 1 : i;  // (a > 0 implies p < n - 1: j stays inside the utterance)
-	const double w0 = 1.0 - a;
+	const RtPlace q = rt_place(A.pos[g], u.n);
+	const bool finite = q.finite;
+	const int i = q.i, j = q.j;
+	const double a = q.a, w0 = q.w0;
 
 	if (A.f0_out && tid == 0) {
 		double v = __builtin_nan("");
@@ -160,7 +103,7 @@ __global__ __launch_bounds__(RT_T) void retime_kernel(RtArgs A) {
 		rt_row(ri, rj, w0, a, out, bins, tid);
 		return;
 	}
-	if constexpr (STRETCH) rt_stretched_row(ri, rj, w0, a, out, ratio, A.fs, A.fft_size, tid);
+	if constexpr (STRETCH) rt_stretched_row_tu(ri, rj, w0, a, out, ratio, A.fs, A.fft_size, tid);
 }
 
 // The streaming form (wc_synth_stream_set_speed, include/world_class_stream.h): the same frame at the same position, but the source
@@ -207,7 +150,7 @@ __global__ __launch_bounds__(RT_T) void retime_stream_kernel(RtStreamArgs A) {
 		rt_row(ri, rj, w0, a, out, bins, tid);
 		return;
 	}
-	if constexpr (STRETCH) rt_stretched_row(ri, rj, w0, a, out, ratio, A.fs, A.fft_size, tid);
+	if constexpr (STRETCH) rt_stretched_row_tu(ri, rj, w0, a, out, ratio, A.fs, A.fft_size, tid);
 }
 
 // descriptor staging per (device, stream): calls on one stream are ordered behind each other, calls on different streams never

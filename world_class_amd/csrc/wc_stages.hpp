@@ -123,6 +123,17 @@ int retime_stream_enqueue(Device *dev, hipStream_t s, int fs, int fft_size, int 
 						  long long total_out, const double *d_position, const double *d_f0_scale, const double *d_spectral_ratio, const double *d_f0_in,
 						  const double *d_sp_in, const double *d_ap_in, double *d_f0_out, double *d_sp_out, double *d_ap_out);
 
+// Voice morphing (wc_morph.hip).  morph_check: nullptr if wc_morph_parameters_device takes the sizes and the lengths, else why not;
+// the output frames of the batch come back.  morph_enqueue: the arguments already checked, the descriptors staged and the kernel
+// enqueued on s.
+const char *morph_check(int fs, int fft_size, int n_pairs, const int *a_length, const int *b_length, const int *out_length,
+						long long *total_out);
+int morph_enqueue(Device *dev, hipStream_t s, int fs, int fft_size, int n_pairs, const int *a_length, const double *d_f0_a,
+				  const double *d_sp_a, const double *d_ap_a, const int *b_length, const double *d_f0_b, const double *d_sp_b,
+				  const double *d_ap_b, const int *out_length, const double *d_position_a, const double *d_position_b,
+				  const double *d_weight, const double *d_f0_weight, const double *d_ratio_a, const double *d_ratio_b, double *d_f0_out,
+				  double *d_sp_out, double *d_ap_out, long long total_out);
+
 // Feature coding (wc_code_features.hip)
 // nullptr if (fs, fft_size, nd) can be coded, else why not: fft_size 512 .. 4096, 1 <= nd <= fft_size/4+1, and with the
 // aperiodicity fs >= 12 kHz (at least one band)

@@ -1,6 +1,6 @@
 // Row rules that kernels of several translation units share, each stated once:
 //   the spectral stretch of the reference demo (test/test.cpp:222-240): stretch_kernel (wc_io.hip), retime_kernel<true>
-//     (wc_retime.hip) and decode_features_wave_kernel<true> (wc_synth_coded.hip)
+//     (wc_retime.hip), decode_features_wave_kernel<true> (wc_synth_coded.hip) and, in the log domain, morph_kernel<true> (wc_morph.hip)
 //   the decoded band-aperiodicity row (reference src/codec.cpp:19-40): decode_ap_kernel (wc_codec.hip) and
 //     decode_features_wave_kernel
 #pragma once
@@ -17,13 +17,13 @@ __host__ __device__ inline bool frame_ratio_valid(double ratio, int fft_size) {
 	return ratio >= 2.0 / fft_size && ratio <= 1.7976931348623157e308;
 }
 
-// Bin i of a row stretched by `ratio`: reference interp1 (src/world_matlabfunctions.cpp:157-182) of the row's log envelope lg(k)
-// from the stretched axis onto the plain one, with histc's clamp(#{j : axis1(j) <= xi}, 1, bins - 1) and linear extrapolation,
-// then the one exp.  The fill of the bins from cut = int(fft_size / 2 * ratio) upward (:236-240), ratio 0 and invalid ratios are
+// Bin i of a row stretched by `ratio`, in the log domain: reference interp1 (src/world_matlabfunctions.cpp:157-182) of the row's
+// log envelope lg(k) from the stretched axis onto the plain one, with histc's clamp(#{j : axis1(j) <= xi}, 1, bins - 1) and linear
+// extrapolation.  The fill of the bins from cut = int(fft_size / 2 * ratio) upward (:236-240), ratio 0 and invalid ratios are
 // the caller's.  FftSize: int, or std::integral_constant where the kernel knows the size (the settling loops then compile as they do
 // written out in that kernel).
 template <class FftSize, class LogAt>
-__device__ __forceinline__ double stretched_bin(int i, double ratio, int fs, FftSize size, LogAt lg) {
+__device__ __forceinline__ double stretched_log_bin(int i, double ratio, int fs, FftSize size, LogAt lg) {
 	const int fft_size = size;
 	const int bins = fft_size / 2 + 1;
 	auto axis1 = [&](int j) { return ratio * j / fft_size * fs; };  // reference test/test.cpp:222
@@ -37,7 +37,13 @@ __device__ __forceinline__ double stretched_bin(int i, double ratio, int fs, Fft
 	const double x0 = axis1(k - 1), x1 = axis1(k);
 	const double s = (xi - x0) / (x1 - x0);
 	const double a = lg(k - 1), b = lg(k);
-	return exp(a + s * (b - a));
+	return a + s * (b - a);
+}
+
+// the bin itself: the one exp of its log-domain value (morph_kernel, wc_morph.hip, blends two such values before its exp)
+template <class FftSize, class LogAt>
+__device__ __forceinline__ double stretched_bin(int i, double ratio, int fs, FftSize size, LogAt lg) {
+	return exp(stretched_log_bin(i, ratio, fs, size, lg));
 }
 
 constexpr double kFrequencyInterval = 3000.0, kSafeGuard = 0.000000000001;  // world_constantnumbers.hpp

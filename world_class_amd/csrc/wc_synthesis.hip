@@ -1999,7 +1999,7 @@ struct wc_synthesis {
 	bool serial_timebase;  // WC_SYN_TIMEBASE=serial: the one-wavefront sequential accumulation instead of the exact parallel one
 	HostBuf h_stage, h_rows;
 	DevBuf dec_sp, dec_ap;  // wc_synthesis_compute_coded_device: the decoded rows
-	DevBuf rt_f0, rt_sp, rt_ap;  // wc_synthesis_compute_coded_retimed_device: the retimed contour and rows
+	DevBuf rt_f0, rt_sp, rt_ap;  // wc_synthesis_compute_coded_retimed_device / _morphed_device: the retimed (morphed) contour and rows
 	long long total_out = 0, cap_total = 0;  // of the most recent syn_prepare
 	int n_utt = 0, max_out = 0;
 };
@@ -2552,6 +2552,48 @@ int wc_synthesis_compute_coded_retimed_device(wc_synthesis *s, int n_utt, const 
 	double *r_f0 = s->rt_f0.as<double>(), *r_sp = s->rt_sp.as<double>(), *r_ap = s->rt_ap.as<double>();
 	if ((rc = retime_enqueue(s->dev, s->dev->active(), s->fs, s->fft_size, n_utt, f0_length, d_f0, s->dec_sp.as<double>(), s->dec_ap.as<double>(),
 							 frames_out, d_position, d_f0_scale, d_spectral_ratio, r_f0, r_sp, r_ap, total))) return rc;
+	return syn_run_device(s, n_utt, r_f0, frames_out, r_sp, r_ap, out_length, d_out, rng_pos);
+}
+
+// Synthesis from the coded features of two voices: decode both (the unmodified decoder; B's rows behind A's in the decoded scratch)
+// -> morph (wc_morph.hip) into the retimed call's scratch rows -> the batch
+int wc_synthesis_compute_coded_morphed_device(wc_synthesis *s, int n_utt, const double *d_f0_a, const int *a_length, const double *d_coded_sp_a,
+											  const double *d_coded_ap_a, const double *d_f0_b, const int *b_length, const double *d_coded_sp_b,
+											  const double *d_coded_ap_b, int number_of_dimensions, const int *frames_out,
+											  const double *d_position_a, const double *d_position_b, const double *d_weight,
+											  const double *d_f0_weight, const double *d_ratio_a, const double *d_ratio_b, const int *out_length,
+											  double *d_out, uint64_t *rng_pos) {
+	if (!s || n_utt <= 0 || !d_f0_a || !a_length || !d_coded_sp_a || !d_coded_ap_a || !d_f0_b || !b_length || !d_coded_sp_b || !d_coded_ap_b ||
+		!frames_out || !d_position_a || !d_position_b || !d_weight || !out_length || !d_out)
+		return fail(WC_ERR_INVALID, "synthesis coded morphed: null argument");
+	if (const char *why = decode_features_check(s->fs, s->fft_size, number_of_dimensions)) return fail(WC_ERR_INVALID, why);
+	long long fa = 0, fb = 0, total = 0;
+	for (int u = 0; u < n_utt; ++u) {  // (checked here too: a refused call enqueues nothing)
+		if (a_length[u] < 2 || b_length[u] < 2 || frames_out[u] < 2)
+			return fail(WC_ERR_INVALID, "synthesis: a_length, b_length and frames_out must be at least 2 (reference src/synthesis.cpp:241-242)");
+		if (out_length[u] < 0) return fail(WC_ERR_INVALID, "synthesis: negative out_length");
+		fa += a_length[u];
+		fb += b_length[u];
+	}
+	if (const char *why = morph_check(s->fs, s->fft_size, n_utt, a_length, b_length, frames_out, &total)) return fail(WC_ERR_INVALID, why);
+	WC_HIP(hipSetDevice(s->dev->id));
+	DeviceLock lock(s->dev);
+	const size_t bins = (size_t)(s->fft_size / 2 + 1), row = sizeof(double) * bins;
+	int rc;
+	if ((rc = s->dec_sp.reserve(row * (fa + fb)))) return rc;
+	if ((rc = s->dec_ap.reserve(row * (fa + fb)))) return rc;
+	if ((rc = s->rt_sp.reserve(row * total))) return rc;
+	if ((rc = s->rt_ap.reserve(row * total))) return rc;
+	if ((rc = s->rt_f0.reserve(sizeof(double) * total))) return rc;
+	hipStream_t st = s->dev->active();
+	double *sp_a = s->dec_sp.as<double>(), *ap_a = s->dec_ap.as<double>(), *sp_b = sp_a + bins * fa, *ap_b = ap_a + bins * fa;
+	if ((rc = decode_features_enqueue(s->dev, st, s->fs, s->fft_size, fa, number_of_dimensions, d_coded_sp_a, d_coded_ap_a, nullptr, sp_a, ap_a)))
+		return rc;
+	if ((rc = decode_features_enqueue(s->dev, st, s->fs, s->fft_size, fb, number_of_dimensions, d_coded_sp_b, d_coded_ap_b, nullptr, sp_b, ap_b)))
+		return rc;
+	double *r_f0 = s->rt_f0.as<double>(), *r_sp = s->rt_sp.as<double>(), *r_ap = s->rt_ap.as<double>();
+	if ((rc = morph_enqueue(s->dev, st, s->fs, s->fft_size, n_utt, a_length, d_f0_a, sp_a, ap_a, b_length, d_f0_b, sp_b, ap_b, frames_out,
+							d_position_a, d_position_b, d_weight, d_f0_weight, d_ratio_a, d_ratio_b, r_f0, r_sp, r_ap, total))) return rc;
 	return syn_run_device(s, n_utt, r_f0, frames_out, r_sp, r_ap, out_length, d_out, rng_pos);
 }
 

@@ -29,6 +29,8 @@ IO_SIGNATURES = {
     "wc_modify_parameters_frames_device": (C.c_int, [C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "wc_retime_parameters_device": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int),
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "wc_morph_parameters_device": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int),
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)] + [C.c_void_p] * 9),
 }
 
 _bound = False
@@ -194,6 +196,57 @@ def retime_parameters(f0, sp, ap, position, fs, fft_size, f0_scale=None, spectra
         for a in held + outs:
             if a is not None:
                 a.free()
+
+
+def morph_parameters_device(fs, fft_size, a_lengths, d_f0_a, d_sp_a, d_ap_a, b_lengths, d_f0_b, d_sp_b, d_ap_b, out_lengths, d_position_a,
+                            d_position_b, d_weight, d_f0_weight=None, d_ratio_a=None, d_ratio_b=None, d_f0_out=None, d_sp_out=None, d_ap_out=None):
+    """wc_morph_parameters_device: every output frame of a packed batch of pairs is the blend of A's frame at d_position_a and B's
+    frame at d_position_b (both as retime_parameters_device forms them) with d_weight -- log-F0 (d_f0_weight, None = d_weight),
+    log-envelope (each source's axis stretched by d_ratio_a / d_ratio_b first, None or 0 = as it is) and aperiodicity (linear);
+    weight 0 is A, 1 is B.  a_lengths / b_lengths / out_lengths: frames per pair (host lists); each of the triples (d_f0_a, d_f0_b,
+    d_f0_out), (d_sp_a, d_sp_b, d_sp_out), (d_ap_a, d_ap_b, d_ap_out) may be None together."""
+    from . import _ints
+    if not (len(a_lengths) == len(b_lengths) == len(out_lengths)):
+        raise ValueError("morph_parameters_device: a_lengths, b_lengths and out_lengths must have one entry per pair each")
+    _check(_io().wc_morph_parameters_device(int(fs), int(fft_size), len(a_lengths), _ints(a_lengths), _opt(d_f0_a), _opt(d_sp_a), _opt(d_ap_a),
+                                            _ints(b_lengths), _opt(d_f0_b), _opt(d_sp_b), _opt(d_ap_b), _ints(out_lengths), _opt(d_position_a),
+                                            _opt(d_position_b), _opt(d_weight), _opt(d_f0_weight), _opt(d_ratio_a), _opt(d_ratio_b),
+                                            _opt(d_f0_out), _opt(d_sp_out), _opt(d_ap_out)))
+
+
+def morph_parameters(a, b, position_a, position_b, weight, fs, fft_size, f0_weight=None, ratio_a=None, ratio_b=None):
+    """one pair, numpy in, numpy out: a and b are (f0, sp, ap); (f0, sp, ap) of the blend at the positions (see
+    morph_parameters_device), through the device call.  weight, f0_weight and the ratios: one value per output frame, or a scalar"""
+    from . import DeviceArray
+    bins = int(fft_size) // 2 + 1
+    srcs = []
+    for name, (f0, sp, ap) in (("a", a), ("b", b)):
+        f0, sp, ap = _c(f0), _c(sp), _c(ap)
+        if f0.ndim != 1 or sp.shape != (len(f0), bins) or ap.shape != (len(f0), bins):
+            raise ValueError(f"morph_parameters: {name} must be (f0, sp, ap) with sp and ap ({len(f0)}, {bins})")
+        srcs.append((f0, sp, ap))
+    position_a, position_b = _c(position_a), _c(position_b)
+    if position_a.ndim != 1 or position_a.shape != position_b.shape:
+        raise ValueError("morph_parameters: position_a and position_b must be vectors of one length")
+    m = len(position_a)
+    per_frame = [None if v is None else np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (m,)))
+                 for v in (weight, f0_weight, ratio_a, ratio_b)]
+    if per_frame[0] is None:
+        raise ValueError("morph_parameters: weight is required")
+    held, outs = [], []
+    try:
+        for v in srcs[0] + srcs[1] + (position_a, position_b) + tuple(per_frame):
+            held.append(None if v is None else DeviceArray.from_host(v))
+        for n in (m, m * bins, m * bins):
+            outs.append(DeviceArray(n))
+        morph_parameters_device(fs, fft_size, [len(srcs[0][0])], held[0], held[1], held[2], [len(srcs[1][0])], held[3], held[4], held[5], [m],
+                                held[6], held[7], held[8], held[9], held[10], held[11], *outs)
+        _check(lib().wc_synchronize())
+        return outs[0].to_host()[:m], outs[1].to_host()[:m * bins].reshape(m, bins), outs[2].to_host()[:m * bins].reshape(m, bins)
+    finally:
+        for v in held + outs:
+            if v is not None:
+                v.free()
 
 
 def time_map(n_frames, speed):
