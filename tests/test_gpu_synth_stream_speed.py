@@ -306,20 +306,24 @@ def test_a_neutral_stream_is_todays_stream(env, explicit):
         L.wc_set_kernel_timing(0)
 
 
-def test_refusals_leave_every_stream_as_it_was(env):
+@pytest.mark.parametrize("coded", [True, False])
+def test_refusals_leave_every_stream_as_it_was(env, coded):
     """8. bad speeds, a push that would form max_frames + 1 frames, a flush with one synthesis frame, a refusal for stream 1 that
-    leaves stream 0 untouched; the streams then continue to the whole call's samples; reset returns the speed to 1.0"""
+    leaves stream 0 untouched; the streams then continue to the whole call's samples -- through push_coded and through push (full
+    rows); reset returns the speed to 1.0"""
     from world_class_amd.stream import StreamSynthesizer
     fs, fft, fp, mf = 16000, 1024, 5.0, 16
-    srcs = [_code(env, fs, fft, p) for p in (_params(fs, fft, 40, 390), _params(fs, fft, 40, 391))]
+    srcs = [_params(fs, fft, 40, 390), _params(fs, fft, 40, 391)]
+    if coded:
+        srcs = [_code(env, fs, fft, p) for p in srcs]
     st = StreamSynthesizer(fs, fft, fp, 2, mf)
     state = lambda: [(st.samples_committed(u), st.frames_received(u), st.frames_synthesised(u), repr(st.source_position(u)), st.rng_position(u))
                      for u in range(2)]
-    e = [np.zeros(0), np.zeros((0, ND)), np.zeros((0, srcs[0][2].shape[1]))]
+    e = [np.zeros(0), np.zeros((0, srcs[0][1].shape[1])), np.zeros((0, srcs[0][2].shape[1]))]  # (full rows: fft // 2 + 1 columns)
     cut = lambda u, a, b: [srcs[u][q][a:b] for q in range(3)]
 
     def push(a, b, flush=None):
-        return st.push_coded(*[[a[q], b[q]] for q in range(3)], flush)
+        return (st.push_coded if coded else st.push)(*[[a[q], b[q]] for q in range(3)], flush)
 
     st.set_speed(0, 0.5)
     st.set_speed(1, 3.0)
@@ -351,9 +355,11 @@ def test_refusals_leave_every_stream_as_it_was(env):
         acc[0].append(r[0]); acc[1].append(r[1])
     for u, speed in enumerate((0.5, 3.0)):
         pos = list(np.arange(int(39 / speed) + 1) * speed)
-        want, end = whole_coded(env, fs, fft, fp, srcs[u], pos, 1.0, 0.0)
+        want, end = whole_coded(env, fs, fft, fp, srcs[u], pos, 1.0, 0.0) if coded else whole_rows(env, fs, fft, fp, srcs[u], pos)
         assert np.array_equal(np.concatenate(acc[u]), want), u
         assert st.rng_position(u) == end and st.frames_synthesised(u) == len(pos) and st.frames_received(u) == 40
+    if not coded:
+        return  # (the reset below is the handle's, the same for both kinds of rows)
     st.reset(0)
     assert st.frames_for_push(0, 5) == 5 and math.isnan(st.source_position(0)) and st.frames_received(0) == 0
     one = StreamSynthesizer(fs, fft, fp, 1, 40)
