@@ -232,6 +232,79 @@ int wc_synth_stream_set_rng_position(wc_synth_stream *s, int stream, unsigned lo
 long long wc_synth_stream_frames_received(const wc_synth_stream *s, int stream);
 long long wc_synth_stream_samples_committed(const wc_synth_stream *s, int stream);
 
+/* ---- Morph streams: two voices per stream, blended push by push into synthesis frames (extension) ----
+ *
+ * The streaming form of wc_morph_parameters_device (world_class_io.h), as wc_synth_stream_set_speed is that of
+ * wc_retime_parameters_device.  The handle sits IN FRONT of a synthesis stream: a push takes source frames of voice A and of voice B
+ * for every stream and writes the morphed frames they now allow as full rows (F0, sp row, ap row of fft_size/2+1) into the caller's
+ * buffers; the caller hands those rows to wc_synth_stream_push_device, which is unchanged.  Nothing of wc_synth_stream is touched, and
+ * the rows take the trip through device memory that the retimed rows of a synthesis stream take.
+ *
+ * The rule (host arithmetic).  Per stream the handle keeps Fa and Fb, the source frames received from each voice; whether a frame
+ * has been formed; last_a and last_b, the positions of the newest formed frame; and the settings speed_a, speed_b (1.0), weight,
+ * f0_weight (0.0), ratio_a, ratio_b (0.0: none) -- host-side settings that take effect at the next push.  A push gives stream u
+ * n_a[u] frames of A and n_b[u] frames of B (either may be 0): Fa += n_a, Fb += n_b, and then frames are formed one after the other:
+ *   pa = last_a + speed_a,  pb = last_b + speed_b   (one double addition each; 0.0 and 0.0 for the first frame of the stream),
+ * while pa <= Fa - 1 and pb <= Fb - 1; each frame takes the weight, F0 weight and ratios in effect at this push, and last_a = pa,
+ * last_b = pb.  Nothing formed is ever revised and there is no flush: positions past the last row are dropped and end frames are not
+ * held, as in wc_synth_stream_set_speed.
+ * Every formed frame is, bit for bit, the frame wc_morph_parameters_device writes for ONE pair (all of A, all of B) at
+ * d_position_a = pa, d_position_b = pb, d_weight, d_f0_weight, d_ratio_a, d_ratio_b: its copy paths at a weight of 0 or 1 and at
+ * whole positions, its nearer-source F0 rule, its log-domain stretch.  (Positions never need that call's end clamp: p <= F - 1.)
+ * No stream's frames depend on another stream's counts or settings.
+ *
+ * The backlog.  Two voices are consumed at two rates, so rows of the voice that is fed faster wait for the other.  After a push
+ * voice x keeps rows keep_x .. Fx - 1, keep_x = floor(last_x) (0 before the first frame): no positive speed can ask for an older
+ * row; backlog_x = Fx - keep_x.  Because row floor(last_x) stays, wc_morph_stream_set_speeds takes any finite speed > 0 at any time
+ * (the phase-dependent refusal of wc_synth_stream_set_speed does not arise).  The handle is created with max_backlog (>= 2) rows
+ * per stream and voice and allocates at create: per stream and voice max_backlog + min(max_backlog, max_frames_per_push) slots of
+ * F0 and both rows -- the rows a push adds go to slots that the state before the push does not hold, so a push that fails on the
+ * device with a HIP error leaves the host state and the kept rows of the last good push, and kept rows are never copied twice --
+ * together with the device array and the two page-locked staging buffers of the per-frame records.  wc_morph_stream_destroy
+ * releases them.
+ *
+ * Refused with WC_ERR_INVALID on the host before anything is enqueued, every stream, setting and kept row as it was: a negative
+ * count; n_a[u] or n_b[u] above max_frames_per_push; a push that would form more than max_frames_per_push frames for one stream
+ * (the count stops at the bound: a speed of 1e-300 costs nothing); a push after which a backlog would exceed max_backlog; NULL
+ * arrays with frames to read or to write; and in the setters a speed that is not finite and > 0, a weight or F0 weight that is not
+ * finite, a ratio that is neither 0 nor finite and >= 2.0 / fft_size, a bad stream index.
+ *
+ * Layout: n_a / n_b are host arrays; each voice's frames are packed stream by stream in its three arrays, as for
+ * wc_synth_stream_push_device; the formed frames are packed by frames_out[u] (host array), the outputs hold n_streams x
+ * max_frames_per_push rows.  fft_size is 512, 1024, 2048 or 4096.  A push is stream-ordered on the caller's stream (wc_set_stream)
+ * and only enqueues: the positions, weights, ratios and row references of the formed frames go up through the handle's staging
+ * with one asynchronous copy, one launch forms the frames and keeps the rows (the variant without shared memory while no stream
+ * that forms frames has a ratio).  A handle is driven on one stream at a time. */
+typedef struct wc_morph_stream wc_morph_stream;
+wc_morph_stream *wc_morph_stream_create(int fs, int fft_size, int n_streams, int max_frames_per_push, int max_backlog);
+void wc_morph_stream_destroy(wc_morph_stream *m);
+/* the stream as after create: no frames, speeds 1, weights 0, ratios 0 */
+int wc_morph_stream_reset(wc_morph_stream *m, int stream);
+int wc_morph_stream_set_speeds(wc_morph_stream *m, int stream, double speed_a, double speed_b);
+int wc_morph_stream_set_weight(wc_morph_stream *m, int stream, double weight, double f0_weight);
+int wc_morph_stream_set_ratios(wc_morph_stream *m, int stream, double ratio_a, double ratio_b);
+/* frames a push of n_a and n_b source frames would form for the stream at its current speeds: host arithmetic only, capped at
+ * max_frames_per_push + 1 (a push that would be refused for its count); WC_ERR_INVALID (negative) for a bad argument */
+int wc_morph_stream_frames_for_push(const wc_morph_stream *m, int stream, int n_a, int n_b);
+int wc_morph_stream_push_device(wc_morph_stream *m, const int *n_a, const double *d_f0_a, const double *d_sp_a, const double *d_ap_a,
+                                const int *n_b, const double *d_f0_b, const double *d_sp_b, const double *d_ap_b,
+                                double *d_f0_out, double *d_sp_out, double *d_ap_out, int *frames_out);
+/* The same with coded rows (world_class_codec.h): number_of_dimensions / GetNumberOfAperiodicities(fs) doubles per frame.  The pushed
+ * rows of both voices are decoded by the unmodified decoder (wc_decode_features_device; its refusals) into buffers of the handle
+ * (n_streams x max_frames_per_push rows per voice and matrix, reserved on the first coded push, released by
+ * wc_morph_stream_destroy), then the push is the full-row push: its frames equal wc_decode_features_device followed by
+ * wc_morph_stream_push_device bit for bit.  The backlog always holds full rows, so coded and full-row pushes may alternate. */
+int wc_morph_stream_push_coded_device(wc_morph_stream *m, const int *n_a, const double *d_f0_a, const double *d_coded_sp_a,
+                                      const double *d_coded_ap_a, const int *n_b, const double *d_f0_b, const double *d_coded_sp_b,
+                                      const double *d_coded_ap_b, int number_of_dimensions,
+                                      double *d_f0_out, double *d_sp_out, double *d_ap_out, int *frames_out);
+/* source: 0 = voice A, 1 = voice B.  last_a / last_b: NaN before the first frame or for a bad index */
+double wc_morph_stream_source_position(const wc_morph_stream *m, int stream, int source);
+/* source frames received / rows kept (backlog_x) / frames formed so far; -1 for a bad index */
+long long wc_morph_stream_frames_received(const wc_morph_stream *m, int stream, int source);
+int wc_morph_stream_backlog(const wc_morph_stream *m, int stream, int source);
+long long wc_morph_stream_frames_formed(const wc_morph_stream *m, int stream);
+
 #ifdef __cplusplus
 }
 #endif

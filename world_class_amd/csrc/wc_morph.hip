@@ -7,7 +7,8 @@
 //     sums).  ap = (1 - w) * apA + w * apB; sp = exp((1 - w) * la + w * lb) on the two log envelopes; F0 = exp of the same blend of
 //     the two log F0 where both frames are voiced, the nearer source's F0 (or 0) where one is, 0 where neither is.  w == 0 and
 //     w == 1 write the one source's retimed frame bit for bit (the paths of retime_kernel).  A gather bound by memory traffic or by
-//     its two log and one exp per bin: up to eight rows in, two out, two bins per lane and access.
+//     its two log and one exp per bin: up to eight rows in, two out, two bins per lane and access.  The blend's own expressions
+//     (mp_f0, mp_log) are stated in wc_morph_rows.hpp, shared with morph_stream_kernel (wc_morph_stream.hip).
 //     STRETCH = false: no LDS, the blend straight from registers.
 //     STRETCH: each source's interpolated row goes to LDS as its logarithm (two rows of kMaxBins doubles, 32 KB at fft 4096: four
 //     workgroups per CU of 160 KB); la(b) / lb(b) are wc::stretched_log_bin (wc_stretch.hpp: the value whose exp stretch_kernel and
@@ -22,6 +23,7 @@
 
 #include "../../include/world_class_c.h"
 #include "../../include/world_class_io.h"
+#include "wc_morph_rows.hpp"
 #include "wc_retime_rows.hpp"
 #include "wc_stages.hpp"
 
@@ -41,45 +43,6 @@ struct MpArgs {
 	const double *f0_a, *sp_a, *ap_a, *f0_b, *sp_b, *ap_b;
 	double *f0_out, *sp_out, *ap_out;
 };
-
-__device__ __forceinline__ bool mp_finite(double v) { return v >= -1.7976931348623157e308 && v <= 1.7976931348623157e308; }
-
-// the frame's F0 from the two retimed values: the nearer-source rule of rt_f0 across the two voices
-__device__ __forceinline__ double mp_f0(double fa, double fb, double wf) {
-	if (!mp_finite(wf)) return __builtin_nan("");
-	if (wf == 0.0) return fa;
-	if (wf == 1.0) return fb;
-	const bool va = fa != 0.0, vb = fb != 0.0;
-	if (va && vb) return exp((1.0 - wf) * log(fa) + wf * log(fb));
-	if (va) return wf < 0.5 ? fa : 0.0;
-	if (vb) return wf > 0.5 ? fb : 0.0;
-	return 0.0;
-}
-
-// la(b) of a source whose interpolated row's logarithm sits in lg: the row stretched by `ratio` in the log domain (0: as it is).
-// fill: the value of bin cut - 1, used from bin `top` upward (ratio < 1)
-struct MpLog {
-	const double *lg;
-	double ratio, fill;
-	int top, fs, fft_size;
-	__device__ __forceinline__ double at(int b) const {
-		if (ratio == 0.0) return lg[b];
-		if (b >= top) return fill;
-		return stretched_log_bin(b, ratio, fs, fft_size, [&](int k) { return lg[k]; });
-	}
-};
-__device__ __forceinline__ MpLog mp_log(const double *lg, double ratio, int fs, int fft_size) {
-	MpLog m;
-	m.lg = lg; m.ratio = ratio; m.fs = fs; m.fft_size = fft_size;
-	const int bins = fft_size / 2 + 1;
-	m.top = bins;
-	m.fill = 0.0;
-	if (ratio != 0.0 && ratio < 1.0) {
-		m.top = static_cast<int>(fft_size / 2.0 * ratio);  // >= 1 for a valid ratio
-		m.fill = stretched_log_bin(m.top - 1, ratio, fs, fft_size, [&](int k) { return lg[k]; });
-	}
-	return m;
-}
 
 template <bool STRETCH>
 __global__ __launch_bounds__(RT_T) void morph_kernel(MpArgs A) {

@@ -43,8 +43,26 @@ STREAM_SIGNATURES = {
     "wc_synth_stream_source_position": (C.c_double, [_vp, C.c_int]),
     "wc_synth_stream_frames_synthesised": (C.c_longlong, [_vp, C.c_int]),
     "wc_synth_stream_frames_for_push": (C.c_int, [_vp, C.c_int, C.c_int]),
+    "wc_morph_stream_create": (_vp, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "wc_morph_stream_destroy": (None, [_vp]),
+    "wc_morph_stream_reset": (C.c_int, [_vp, C.c_int]),
+    "wc_morph_stream_set_speeds": (C.c_int, [_vp, C.c_int, C.c_double, C.c_double]),
+    "wc_morph_stream_set_weight": (C.c_int, [_vp, C.c_int, C.c_double, C.c_double]),
+    "wc_morph_stream_set_ratios": (C.c_int, [_vp, C.c_int, C.c_double, C.c_double]),
+    "wc_morph_stream_frames_for_push": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int]),
+    "wc_morph_stream_push_device": (C.c_int, [_vp, _ip, _vp, _vp, _vp, _ip, _vp, _vp, _vp, _vp, _vp, _vp, _ip]),
+    "wc_morph_stream_push_coded_device": (C.c_int, [_vp, _ip, _vp, _vp, _vp, _ip, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _ip]),
+    "wc_morph_stream_source_position": (C.c_double, [_vp, C.c_int, C.c_int]),
+    "wc_morph_stream_frames_received": (C.c_longlong, [_vp, C.c_int, C.c_int]),
+    "wc_morph_stream_backlog": (C.c_int, [_vp, C.c_int, C.c_int]),
+    "wc_morph_stream_frames_formed": (C.c_longlong, [_vp, C.c_int]),
 }
 _bound = False
+
+
+def _opt(obj):
+    """_ptr, or NULL for None"""
+    return None if obj is None else _ptr(obj)
 
 
 def _lib():
@@ -357,6 +375,126 @@ class StreamSynthesizer:
         try:
             if getattr(self, "_h", None):
                 _lib().wc_synth_stream_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+
+class MorphStream:
+    """n_streams concurrent morph streams in front of a StreamSynthesizer: every push appends up to `max_frames` source frames of
+    voice A and of voice B per stream and returns the morphed frames (f0, spectrogram and aperiodicity rows) that both voices' rows
+    now allow -- those of one whole-utterance io.morph_parameters_device pair at the stream's positions (the rule of the header)."""
+
+    def __init__(self, fs, fft_size, n_streams=1, max_frames=200, max_backlog=16):
+        L = _lib()
+        self.fs, self.fft_size, self.n_streams, self.max_frames, self.max_backlog = fs, fft_size, n_streams, max_frames, max_backlog
+        self.bins = fft_size // 2 + 1
+        self._h = _handle(L.wc_morph_stream_create(fs, fft_size, n_streams, max_frames, max_backlog))
+        self._out = None  # the outputs of the numpy front-ends: allocated on their first call
+
+    def push_device(self, n_a, d_f0_a, d_sp_a, d_ap_a, n_b, d_f0_b, d_sp_b, d_ap_b, d_f0_out, d_sp_out, d_ap_out):
+        """device pointers in and out (packed layouts of the header); returns the frames formed per stream"""
+        out = (C.c_int * self.n_streams)()
+        _check(_lib().wc_morph_stream_push_device(self._h, self._counts(n_a), _opt(d_f0_a), _opt(d_sp_a), _opt(d_ap_a), self._counts(n_b), _opt(d_f0_b),
+                                                  _opt(d_sp_b), _opt(d_ap_b), _opt(d_f0_out), _opt(d_sp_out), _opt(d_ap_out), out))
+        return list(out)
+
+    def push_coded_device(self, n_a, d_f0_a, d_coded_sp_a, d_coded_ap_a, n_b, d_f0_b, d_coded_sp_b, d_coded_ap_b, number_of_dimensions, d_f0_out,
+                          d_sp_out, d_ap_out):
+        """as push_device with coded rows (number_of_dimensions mel-cepstral coefficients and the band aperiodicities per frame);
+        the frames come out as full rows"""
+        out = (C.c_int * self.n_streams)()
+        _check(_lib().wc_morph_stream_push_coded_device(self._h, self._counts(n_a), _opt(d_f0_a), _opt(d_coded_sp_a), _opt(d_coded_ap_a),
+                                                        self._counts(n_b), _opt(d_f0_b), _opt(d_coded_sp_b), _opt(d_coded_ap_b), int(number_of_dimensions),
+                                                        _opt(d_f0_out), _opt(d_sp_out), _opt(d_ap_out), out))
+        return list(out)
+
+    def _counts(self, n):
+        if len(n) != self.n_streams:
+            raise ValueError("one frame count per stream")
+        return _ints(n)
+
+    def push(self, a, b):
+        """a[u] / b[u]: (f0, sp rows, ap rows) with the new frames of voice A / B of stream u (empty = none).  Returns per stream
+        (f0, sp, ap) of the frames formed."""
+        return self._push(a, b, self.bins, self.bins, self.push_device)
+
+    def push_coded(self, a, b):
+        """push with coded rows: a[u] / b[u] = (f0, frames x number_of_dimensions, frames x number_of_aperiodicities(fs))"""
+        from .codec import number_of_aperiodicities
+        nd = next((np.shape(v[1])[1] for v in list(a) + list(b) if len(v[0])), 1)
+        return self._push(a, b, nd, number_of_aperiodicities(self.fs),
+                          lambda na, fa, xa, ya, nb, fb, xb, yb, *outs: self.push_coded_device(na, fa, xa, ya, nb, fb, xb, yb, nd, *outs))
+
+    def _push(self, a, b, w_sp, w_ap, run):
+        if self._out is None:
+            cap = self.n_streams * self.max_frames
+            self._out = (DeviceArray(cap), DeviceArray(cap * self.bins), DeviceArray(cap * self.bins))
+        args, held = [], []
+        for voice in (a, b):
+            counts = [len(v[0]) for v in voice]
+            tot = sum(counts)
+            f0 = np.concatenate([np.asarray(v[0], dtype=np.float64) for v in voice]) if tot else np.zeros(1)
+            sp = np.concatenate([np.asarray(v[1], dtype=np.float64).reshape(-1, w_sp) for v in voice]) if tot else np.zeros((1, w_sp))
+            ap = np.concatenate([np.asarray(v[2], dtype=np.float64).reshape(-1, w_ap) for v in voice]) if tot else np.zeros((1, w_ap))
+            d = [DeviceArray.from_host(np.ascontiguousarray(x)) for x in (f0, sp, ap)]
+            held += d
+            args += [counts] + d
+        try:
+            formed = run(*args, *self._out)
+        finally:
+            for x in held:
+                x.free()
+        tot = sum(formed)
+        f0 = self._out[0].to_host()[:tot]
+        sp = self._out[1].to_host()[:tot * self.bins].reshape(tot, self.bins)
+        ap = self._out[2].to_host()[:tot * self.bins].reshape(tot, self.bins)
+        res, o = [], 0
+        for c in formed:
+            res.append((f0[o:o + c].copy(), sp[o:o + c].copy(), ap[o:o + c].copy()))
+            o += c
+        return res
+
+    def set_speeds(self, stream, speed_a, speed_b):
+        """source frames of voice A / B per formed frame (1.0 after create and reset): any finite speed > 0 at any time"""
+        _check(_lib().wc_morph_stream_set_speeds(self._h, int(stream), float(speed_a), float(speed_b)))
+
+    def set_weight(self, stream, weight, f0_weight=None):
+        """the blend of the frames formed from the next push on: 0 = voice A, 1 = voice B; f0_weight None: the weight"""
+        _check(_lib().wc_morph_stream_set_weight(self._h, int(stream), float(weight), float(weight if f0_weight is None else f0_weight)))
+
+    def set_ratios(self, stream, ratio_a, ratio_b):
+        """spectral ratio per voice (0 = none), applied to that voice's log envelope in front of the blend"""
+        _check(_lib().wc_morph_stream_set_ratios(self._h, int(stream), float(ratio_a), float(ratio_b)))
+
+    def reset(self, stream):
+        _check(_lib().wc_morph_stream_reset(self._h, int(stream)))
+
+    def frames_for_push(self, stream, n_a, n_b):
+        """frames a push of n_a and n_b source frames would form at the current speeds (at most max_frames + 1)"""
+        c = _lib().wc_morph_stream_frames_for_push(self._h, int(stream), int(n_a), int(n_b))
+        if c < 0:
+            _check(c)
+        return c
+
+    def source_position(self, stream, source):
+        """position in voice `source` (0 = A, 1 = B) of the newest frame formed (NaN before the first)"""
+        return float(_lib().wc_morph_stream_source_position(self._h, int(stream), int(source)))
+
+    def frames_received(self, stream, source):
+        return int(_lib().wc_morph_stream_frames_received(self._h, int(stream), int(source)))
+
+    def backlog(self, stream, source):
+        """rows of voice `source` the stream keeps for later frames"""
+        return int(_lib().wc_morph_stream_backlog(self._h, int(stream), int(source)))
+
+    def frames_formed(self, stream):
+        return int(_lib().wc_morph_stream_frames_formed(self._h, int(stream)))
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                _lib().wc_morph_stream_destroy(self._h)
                 self._h = None
         except Exception:
             pass
