@@ -70,7 +70,8 @@ uint64_t wc_rng_get_position(void);
 void wc_rng_set_position(uint64_t position);
 /* The host-pointer batch calls (wc_*_compute_batch) keep their page-locked staging and its device twin on the device between
  * calls (grown on demand; ~1 GB each per row matrix of a 64 x 10 s batch at 48 kHz).  They are released when the last stage
- * handle on the device is destroyed, and by this call (on the calling thread's device); the next batch call allocates again. */
+ * handle on the device is destroyed, and by this call (on the calling thread's device); the next batch call allocates again.
+ * The scratch of wc_align_features_device (world_class_io.h) goes with them. */
 int wc_release_scratch(void);
 
 /* ---- size helpers (pure host arithmetic) ------------------------------------------------------- */

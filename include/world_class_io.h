@@ -130,6 +130,39 @@ int wc_morph_parameters_device(int fs, int fft_size, int n_pairs, const int *a_l
 							   const double *d_weight, const double *d_f0_weight, const double *d_ratio_a, const double *d_ratio_b,
 							   double *d_f0_out, double *d_sp_out, double *d_ap_out);
 
+/* ---- feature alignment ------------------------------------------------------------------------------------------------ */
+/* Dynamic time warping of a packed batch of pairs of feature sequences: where the time maps of the two calls above come from.  Pair
+ * u has n = a_length[u] rows of A and m = b_length[u] rows of B (host arrays); a row holds dims doubles, the rows are packed pair
+ * after pair (the layout of d_coded_sp everywhere).  Only the coefficients dim_begin <= c < dim_end are compared (dim_begin = 1
+ * leaves out the energy coefficient).
+ *   Local cost: d(i, j) = sqrt(sum_c (a[i][c] - b[j][c])^2), the sum over ascending c from 0.0, every difference, product and sum
+ *   rounded on its own, the square root correctly rounded.
+ *   Band: band == 0 allows every cell; band >= 1, with L = max(n, m) - 1, allows cell (i, j) iff |i * (m - 1) - j * (n - 1)| <=
+ *   band * L in 64-bit integers (a Sakoe-Chiba band around the straight line between the corners; both corners and a connected path
+ *   are always inside).
+ *   Accumulation: D(0, 0) = d(0, 0); D(i, j) = d(i, j) + best of Dd = D(i - 1, j - 1), Du = D(i - 1, j), Dl = D(i, j - 1), a
+ *   predecessor outside the matrix or the band counting as +inf, chosen by exactly these comparisons: the diagonal if Dd <= Du &&
+ *   Dd <= Dl, else up if Du <= Dl, else left (they fix the tie-break and what NaN and inf do).
+ *   Path: the recorded choices followed back from (n - 1, m - 1) to (0, 0); K cells, max(n, m) <= K <= n + m - 1.
+ * Outputs (device arrays; each of d_path, d_b_on_a, d_a_on_b may be NULL): d_cost[u] = D(n - 1, m - 1); d_path_length[u] = K;
+ * d_path: pair u's cells as (i, j) int32 pairs in forward order from entry sum_{v<u} (a_length[v] + b_length[v] - 1) on, only the
+ * first K entries written; d_b_on_a, packed like A's frames: for frame i (jmin(i) + jmax(i)) * 0.5 over the path's cells in row i;
+ * d_a_on_b the mirror image, packed like B's frames.  Both maps are exact half-integers and non-decreasing, and they are the
+ * d_position arguments above: B at A's timing is wc_retime_parameters_device with out_length = a_length and d_position = d_b_on_a;
+ * a morph on A's timeline takes d_position_a = 0, 1, ... and d_position_b = d_b_on_a.
+ * A total cost that is not finite: d_cost[u] is written as it is, d_path_length[u] = 0, that pair's maps are NaN and its path
+ * region is not written; no other pair is affected.
+ * Refused (WC_ERR_INVALID, nothing written, nothing enqueued): n_pairs < 0, a length below 1, dims < 1, dim_begin < 0, dim_end >
+ * dims, dim_begin >= dim_end, band < 0, NULL lengths, inputs, d_cost or d_path_length with pairs to do, and more than 2^28 stored
+ * cells in all.  A pair stores n * W cells, W the widest row its band can have: W = m at band 0 (all n * m cells), W = min(m,
+ * 2 * band * L / (n - 1) + 1) under a band -- the allowed cells, rounded up to whole rows.  The call's scratch is 9 bytes per
+ * stored cell plus 8 bytes per possible path entry, 2.3 GB at the cap; it is one buffer per device that grows on demand, is shared
+ * by the calls on that device (a call on another stream waits on the device for the one before it) and goes with
+ * wc_release_scratch().  n_pairs == 0 writes nothing.  Stream-ordered, enqueue-only. */
+int wc_align_features_device(int n_pairs, const int *a_length, const double *d_feat_a, const int *b_length, const double *d_feat_b,
+							 int dims, int dim_begin, int dim_end, int band, double *d_cost, int *d_path_length, int *d_path,
+							 double *d_b_on_a, double *d_a_on_b);
+
 #ifdef __cplusplus
 }
 #endif

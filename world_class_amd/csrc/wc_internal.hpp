@@ -78,6 +78,12 @@ struct Device {
 	// (a 64 x 10 s batch at 48 kHz holds ~1 GB of device and ~1 GB of page-locked memory per row matrix).  Released when the
 	// last stage handle on the device is destroyed and by wc_release_scratch() -- never tied to a host thread's lifetime.
 	Staging batch[6];
+	// Scratch of wc_align_features_device (wc_align.hip): local costs / accumulated costs, choices and the backward path of one
+	// call.  One buffer per device, used under the call lock; a call on another stream than the last one waits (on the device) for
+	// align_done, recorded behind the last call's kernels.  Grown on demand, released with the batch staging.
+	DevBuf align_scratch;
+	hipEvent_t align_done = nullptr;
+	hipStream_t align_last = nullptr;
 	int live_handles = 0;  // stage handles alive on this device (under mu)
 	void handle_born();
 	void handle_gone();  // the last one takes the batch staging with it

@@ -31,6 +31,8 @@ IO_SIGNATURES = {
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "wc_morph_parameters_device": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int),
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)] + [C.c_void_p] * 9),
+    "wc_align_features_device": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                           C.c_int] + [C.c_void_p] * 5),
 }
 
 _bound = False
@@ -247,6 +249,45 @@ def morph_parameters(a, b, position_a, position_b, weight, fs, fft_size, f0_weig
         for v in held + outs:
             if v is not None:
                 v.free()
+
+
+def align_features_device(a_lengths, d_feat_a, b_lengths, d_feat_b, dims, dim_begin, dim_end, band, d_cost, d_path_length, d_path=None,
+                          d_b_on_a=None, d_a_on_b=None):
+    """wc_align_features_device: dynamic time warping of a packed batch of pairs of feature rows (dims doubles each, coefficients
+    dim_begin <= c < dim_end compared, band 0 = every cell, else a Sakoe-Chiba band).  a_lengths / b_lengths: rows per pair (host
+    lists).  d_cost: one double per pair, d_path_length: one int32 per pair (0 where the total cost is not finite), d_path: (i, j)
+    int32 pairs, a_length + b_length - 1 entries per pair; d_b_on_a / d_a_on_b: B's position per frame of A and the reverse -- the
+    d_position of retime_parameters_device / morph_parameters_device.  The last three may be None."""
+    from . import _ints
+    if len(a_lengths) != len(b_lengths):
+        raise ValueError("align_features_device: a_lengths and b_lengths must have one entry per pair each")
+    _check(_io().wc_align_features_device(len(a_lengths), _ints(a_lengths), _opt(d_feat_a), _ints(b_lengths), _opt(d_feat_b), int(dims),
+                                          int(dim_begin), int(dim_end), int(band), _opt(d_cost), _opt(d_path_length), _opt(d_path),
+                                          _opt(d_b_on_a), _opt(d_a_on_b)))
+
+
+def align_features(feat_a, feat_b, dim_begin=1, dim_end=None, band=0):
+    """one pair, numpy in, numpy out: feat_a (n, dims) and feat_b (m, dims) aligned through the device call (see
+    align_features_device).  A dict of cost, path (K x 2 int array of (i, j); K = 0 where the cost is not finite), b_on_a (n) and
+    a_on_b (m)."""
+    from . import DeviceArray
+    feat_a, feat_b = _c(feat_a), _c(feat_b)
+    if feat_a.ndim != 2 or feat_b.ndim != 2 or feat_a.shape[1] != feat_b.shape[1]:
+        raise ValueError("align_features: feat_a and feat_b must be (frames, dims) with the same dims")
+    (n, dims), m = feat_a.shape, feat_b.shape[0]
+    if dim_end is None:
+        dim_end = dims
+    held = [DeviceArray.from_host(feat_a), DeviceArray.from_host(feat_b)]
+    outs = [DeviceArray(1), DeviceArray(1, np.int32), DeviceArray(2 * max(n + m - 1, 1), np.int32), DeviceArray(n), DeviceArray(m)]
+    try:
+        align_features_device([n], held[0], [m], held[1], dims, dim_begin, dim_end, band, *outs)
+        _check(lib().wc_synchronize())
+        k = int(outs[1].to_host()[0])
+        return {"cost": float(outs[0].to_host()[0]), "path": outs[2].to_host()[:2 * k].reshape(k, 2).copy(), "b_on_a": outs[3].to_host()[:n],
+                "a_on_b": outs[4].to_host()[:m]}
+    finally:
+        for a in held + outs:
+            a.free()
 
 
 def time_map(n_frames, speed):
