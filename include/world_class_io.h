@@ -163,6 +163,43 @@ int wc_align_features_device(int n_pairs, const int *a_length, const double *d_f
 							 int dims, int dim_begin, int dim_end, int band, double *d_cost, int *d_path_length, int *d_path,
 							 double *d_b_on_a, double *d_a_on_b);
 
+/* The same alignment under a wider rule: ends that need not be the corners, a step pattern that limits the slope, and the path's
+ * own timeline.  Packing, the local cost d(i, j) and its rounding, the band predicate, the three comparisons, what a total that is
+ * not finite does, the scratch and the stream order are those of wc_align_features_device; with step_pattern == 0, flags == 0 and
+ * d_span, d_timeline_a, d_timeline_b NULL every output equals that call's byte for byte.  ok(i, j) below means inside the matrix
+ * and inside the band; a term whose cells are not all ok is +inf.
+ *   Steps: step_pattern == 0 has Dd = D(i - 1, j - 1), Du = D(i - 1, j), Dl = D(i, j - 1).  step_pattern == 1 keeps the slope between
+ *   1/2 and 2: Dd = D(i - 1, j - 1), Du = D(i - 2, j - 1) + d(i - 1, j) (needs ok(i - 2, j - 1) and ok(i - 1, j)), Dl = D(i - 1, j - 2) +
+ *   d(i, j - 1) (needs ok(i - 1, j - 2) and ok(i, j - 1)), each one rounded sum with the D operand first.  D(i, j) = d(i, j) + best, the
+ *   diagonal if Dd <= Du && Dd <= Dl, else up if Du <= Dl, else left.  The path holds the intermediate cell: the choice up at (i, j)
+ *   puts (i - 1, j) and then (i - 2, j - 1) behind it, the choice left (i, j - 1) and then (i - 1, j - 2), so a path still steps by one
+ *   in each index and K <= n + m - 1.  With both ends closed the total is finite only if max(n, m) - 1 <= 2 * (min(n, m) - 1).
+ *   Start: D(0, 0) = d(0, 0).  With WC_ALIGN_OPEN_BEGIN D(0, j) = d(0, j) for every ok (0, j) (row 0 takes no step) and the backtrack
+ *   stops at the first cell it meets in row 0; without it, at (0, 0).
+ *   End: with WC_ALIGN_OPEN_END the ok cells of row n - 1 are scanned by ascending j from best = +inf and j is taken when D(n - 1, j)
+ *   < best: the lowest column of the minimum wins, NaN and +inf never do.  d_cost[u] is that D and the backtrack starts there.  If
+ *   no cell wins the pair ends at (n - 1, m - 1) like a closed one, and its total is then not finite.  A is always matched whole; a
+ *   caller who wants B whole inside A swaps the arguments.
+ *   Maps: d_b_on_a as above (every row is on the path).  With j_first and j_last the columns of the path's first and last cell,
+ *   d_a_on_b[j] is as above for j_first <= j <= j_last, 0.0 for j < j_first and (double)(n - 1) for j > j_last: the end frames are
+ *   held, as wc_retime_parameters_device holds them for positions outside.
+ * Further outputs (device arrays, each may be NULL on its own): d_span, two int32 per pair, (j_first, j_last), or (-1, -1) where the
+ * total is not finite.  d_timeline_a, d_timeline_b: doubles packed like d_path (pair u from entry sum_{v<u} (a_length[v] +
+ * b_length[v] - 1) on); entry k < K is (double)i_k and (double)j_k of the path's cell k; nothing is written behind K and nothing at
+ * all where the total is not finite.  They are d_position_a and d_position_b of wc_morph_parameters_device with out_length = K:
+ * the caller reads d_path_length back for that.
+ * Refused (WC_ERR_INVALID, nothing written, nothing enqueued): what wc_align_features_device refuses; step_pattern outside {0, 1};
+ * flags outside 0..3; flags != 0 with band != 0 (the band lies around the line between the corners and has no meaning for an open
+ * end); under step_pattern == 1 more than 2^27 stored cells in all (it keeps d and D side by side: 17 bytes per stored cell, which
+ * keeps the scratch within the 2.3 GB above; step_pattern 0 keeps 2^28).  The count is made on the host before the device is
+ * touched.  Stream-ordered, enqueue-only. */
+#define WC_ALIGN_OPEN_BEGIN 1 /* the path may start at any cell (0, j) */
+#define WC_ALIGN_OPEN_END 2   /* the path may end at any cell (n - 1, j) */
+int wc_align_features_ex_device(int n_pairs, const int *a_length, const double *d_feat_a, const int *b_length, const double *d_feat_b,
+								int dims, int dim_begin, int dim_end, int band, int step_pattern, int flags, double *d_cost,
+								int *d_path_length, int *d_path, double *d_b_on_a, double *d_a_on_b, int *d_span, double *d_timeline_a,
+								double *d_timeline_b);
+
 #ifdef __cplusplus
 }
 #endif

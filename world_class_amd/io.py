@@ -33,7 +33,11 @@ IO_SIGNATURES = {
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)] + [C.c_void_p] * 9),
     "wc_align_features_device": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.c_int, C.c_int, C.c_int,
                                            C.c_int] + [C.c_void_p] * 5),
+    "wc_align_features_ex_device": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                              C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 8),
 }
+
+ALIGN_OPEN_BEGIN, ALIGN_OPEN_END = 1, 2  # WC_ALIGN_OPEN_BEGIN, WC_ALIGN_OPEN_END
 
 _bound = False
 
@@ -285,6 +289,50 @@ def align_features(feat_a, feat_b, dim_begin=1, dim_end=None, band=0):
         k = int(outs[1].to_host()[0])
         return {"cost": float(outs[0].to_host()[0]), "path": outs[2].to_host()[:2 * k].reshape(k, 2).copy(), "b_on_a": outs[3].to_host()[:n],
                 "a_on_b": outs[4].to_host()[:m]}
+    finally:
+        for a in held + outs:
+            a.free()
+
+
+def align_features_ex_device(a_lengths, d_feat_a, b_lengths, d_feat_b, dims, dim_begin, dim_end, band, step_pattern, flags, d_cost, d_path_length,
+                             d_path=None, d_b_on_a=None, d_a_on_b=None, d_span=None, d_timeline_a=None, d_timeline_b=None):
+    """wc_align_features_ex_device: align_features_device under the wider rule.  step_pattern 0: the steps of align_features_device; 1:
+    the slope stays between 1/2 and 2.  flags: ALIGN_OPEN_BEGIN | ALIGN_OPEN_END, the path may start at any (0, j) / end at any
+    (n - 1, j) (band must be 0 then).  d_a_on_b holds 0 before and n - 1 behind the path's columns.  d_span: two int32 per pair, the
+    columns of the path's first and last cell ((-1, -1) where the total cost is not finite); d_timeline_a / d_timeline_b: doubles
+    packed like d_path, i_k and j_k of the path's K cells -- d_position_a / d_position_b of morph_parameters_device with out_length
+    = K, which the caller reads back from d_path_length.  The last six may be None."""
+    from . import _ints
+    if len(a_lengths) != len(b_lengths):
+        raise ValueError("align_features_ex_device: a_lengths and b_lengths must have one entry per pair each")
+    _check(_io().wc_align_features_ex_device(len(a_lengths), _ints(a_lengths), _opt(d_feat_a), _ints(b_lengths), _opt(d_feat_b), int(dims),
+                                             int(dim_begin), int(dim_end), int(band), int(step_pattern), int(flags), _opt(d_cost),
+                                             _opt(d_path_length), _opt(d_path), _opt(d_b_on_a), _opt(d_a_on_b), _opt(d_span),
+                                             _opt(d_timeline_a), _opt(d_timeline_b)))
+
+
+def align_features_ex(feat_a, feat_b, dim_begin=1, dim_end=None, band=0, step_pattern=0, open_begin=False, open_end=False):
+    """one pair, numpy in, numpy out, through align_features_ex_device: the dict of align_features plus span (two ints, (-1, -1)
+    where the cost is not finite), timeline_a and timeline_b (K doubles each)."""
+    from . import DeviceArray
+    feat_a, feat_b = _c(feat_a), _c(feat_b)
+    if feat_a.ndim != 2 or feat_b.ndim != 2 or feat_a.shape[1] != feat_b.shape[1]:
+        raise ValueError("align_features_ex: feat_a and feat_b must be (frames, dims) with the same dims")
+    (n, dims), m = feat_a.shape, feat_b.shape[0]
+    if dim_end is None:
+        dim_end = dims
+    flags = (ALIGN_OPEN_BEGIN if open_begin else 0) | (ALIGN_OPEN_END if open_end else 0)
+    entries = max(n + m - 1, 1)
+    held = [DeviceArray.from_host(feat_a), DeviceArray.from_host(feat_b)]
+    outs = [DeviceArray(1), DeviceArray(1, np.int32), DeviceArray(2 * entries, np.int32), DeviceArray(n), DeviceArray(m), DeviceArray(2, np.int32),
+            DeviceArray(entries), DeviceArray(entries)]
+    try:
+        align_features_ex_device([n], held[0], [m], held[1], dims, dim_begin, dim_end, band, step_pattern, flags, *outs)
+        _check(lib().wc_synchronize())
+        k = int(outs[1].to_host()[0])
+        return {"cost": float(outs[0].to_host()[0]), "path": outs[2].to_host()[:2 * k].reshape(k, 2).copy(), "b_on_a": outs[3].to_host()[:n],
+                "a_on_b": outs[4].to_host()[:m], "span": outs[5].to_host()[:2].copy(), "timeline_a": outs[6].to_host()[:k].copy(),
+                "timeline_b": outs[7].to_host()[:k].copy()}
     finally:
         for a in held + outs:
             a.free()
