@@ -116,6 +116,40 @@ def test_open_ends_find_a_phrase_inside_a_track():
         assert ax.align(q, track, 0, 4, 0, step_pattern, 0)["cost"] > 0.0
 
 
+@pytest.mark.parametrize("step_pattern,band,flags", [(0, 0, 0), (0, 2, 0), (0, 0, 3), (1, 0, 0), (1, 3, 0), (1, 0, 1), (1, 0, 2), (1, 0, 3)])
+def test_the_invariants_helper_accepts_the_rule_and_refuses_what_is_wrong(step_pattern, band, flags):
+    """tests/align_checks.py judges the device's outputs against each other; here it judges the rule's, which are right, and a few
+    results that are wrong in one respect each"""
+    import align_checks as ac
+    refused = 0
+    for n, m in [(1, 1), (2, 2), (2, 3), (3, 2), (1, 6), (6, 1), (9, 14), (14, 9), (21, 40), (33, 65)]:
+        a, b = _feats(n, 7, 100 * n + m), _feats(m, 7, 100 * m + n)
+        r = ac.rule_outputs(ax.align(a, b, 1, 6, band, step_pattern, flags))
+        ac.check_alignment_outputs(a, b, (1, 6), band, step_pattern, flags, r)
+        if r["K"] < 4:
+            continue
+        wrong = [dict(r, cost=np.nextafter(r["cost"], INF)), dict(r, path=r["path"][1:], K=r["K"] - 1),
+                 dict(r, span=r["span"] + np.array([0, 1], dtype=np.int32)), dict(r, b_on_a=r["b_on_a"] + 0.5),
+                 dict(r, timeline_b=r["timeline_b"] + 1.0)]
+        k = r["K"] // 2  # a cell of the path moved off it: an illegal step, or a sum and maps that are another path's
+        moved = r["path"].copy()
+        moved[k, 1] += 1 if moved[k, 1] + 1 < m else -1
+        wrong.append(dict(r, path=moved))
+        for w in wrong:
+            with pytest.raises(AssertionError):
+                ac.check_alignment_outputs(a, b, (1, 6), band, step_pattern, flags, w)
+            refused += 1
+    assert refused >= 12
+    if step_pattern == 1 and flags == 0 and band == 0:  # a path of pattern 0 with two straight steps in a row is no path of pattern 1
+        a, b = _feats(9, 7, 1), _feats(14, 7, 2)
+        r0 = ac.rule_outputs(ax.align(a, b, 1, 6, 0, 0, 0))
+        steps = np.diff(r0["path"], axis=0)
+        assert ((steps.sum(axis=1) == 1)[1:] & (steps.sum(axis=1) == 1)[:-1]).any()
+        ac.check_alignment_outputs(a, b, (1, 6), 0, 0, 0, r0)
+        with pytest.raises(AssertionError):
+            ac.check_alignment_outputs(a, b, (1, 6), 0, 1, 0, r0)
+
+
 def test_the_batch_form_walks_the_packed_arrays():
     a, b = _feats(10 + 4, 3, 1), _feats(6 + 9, 3, 2)
     both = ax.align_batch([10, 4], a, [6, 9], b, 0, 3, 0, 1, 3)
