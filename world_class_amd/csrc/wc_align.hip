@@ -2,7 +2,7 @@
 // feature sequences to the time maps that retime and morph take.  Three launches for the whole batch, all bounded by lengths the
 // host wrote into the descriptors:
 //
-//   align_cost_kernel   fully parallel: a workgroup of 256 fills a tile of 32 rows of A x 32 rows of B with the local costs
+//   align_cost_kernel   (wc_align_cost.hpp, shared with the alignment streams)  fully parallel: a workgroup of 256 fills a tile of 32 rows of A x 32 rows of B with the local costs
 //     d(i, j).  The coefficients go through LDS 32 at a time (any dims), a lane holds four cells and adds to each in ascending c, one
 //     dependent chain per cell (difference, product, sum: rounded apart, -ffp-contract=off), then the correctly rounded root.  Under a
 //     band a pair stores W cells per row, W the widest row the band can have, row i from its first allowed column lo(i) on; the
@@ -37,41 +37,15 @@
 
 #include "../../include/world_class_c.h"
 #include "../../include/world_class_io.h"
+#include "wc_align_cost.hpp"
 #include "wc_stages.hpp"
 
 using namespace wc;
 
 namespace {
 
-constexpr int AL_TILE = 32;                   // rows of A and rows of B per workgroup of the cost pass
-constexpr int AL_KC = 32;                     // coefficients per trip through LDS
-constexpr int AL_CHUNK = 8;                   // cells a lane of the accumulation loads ahead of its chain
 constexpr long long kAlignMaxCells = 1ll << 28;  // stored cells per call (world_class_io.h)
 constexpr long long kAlignMaxCellsSlope = 1ll << 27;  // the same under step pattern 1, which keeps d and D side by side
-
-struct AlPair {
-	long long a_off, b_off;  // first row of A / of B in the packed arrays (also first frame of the maps)
-	long long cell_off;      // first stored cell
-	long long path_off;      // first path entry
-	long long tile_off;      // first workgroup of the cost pass
-	long long B;             // band * L, or -1: every cell is allowed
-	int n, m;                // rows of A / of B
-	int W;                   // stored cells per row
-	int tiles_j;             // cost tiles per block of 32 rows
-};
-
-struct AlArgs {
-	const AlPair *pairs;
-	int n_pairs, dims, dim_begin, dim_end;
-	const double *fa, *fb;
-	double *cells;           // d(i, j), then D(i, j) in place
-	unsigned char *choice;   // 0 diagonal, 1 up, 2 left
-	int2 *back;              // the path backwards
-	double *cost;
-	int *path_length;
-	int2 *path;
-	double *b_on_a, *a_on_b;
-};
 
 // what the extended call adds (the kernels of the plain call see it as pattern 0, no flags, no further outputs)
 struct AlEx {
@@ -81,72 +55,6 @@ struct AlEx {
 	int *span;
 	double *timeline_a, *timeline_b;
 };
-
-// the allowed columns [lo, hi] of row i: |i * (m - 1) - j * (n - 1)| <= B in 64-bit integers, solved for j
-__device__ __forceinline__ void al_row(const AlPair &u, int i, int &lo, int &hi) {
-	if (u.B < 0 || u.n == 1) {
-		lo = 0; hi = u.m - 1;
-		return;
-	}
-	const long long q = u.n - 1, x = (long long)i * (u.m - 1);
-	const long long l = x - u.B, h = (x + u.B) / q;
-	lo = l <= 0 ? 0 : (int)((l + q - 1) / q);
-	hi = h > u.m - 1 ? u.m - 1 : (int)h;
-}
-
-__global__ __launch_bounds__(256) void align_cost_kernel(AlArgs A) {
-	__shared__ double sa[AL_TILE][AL_KC + 1], sb[AL_TILE][AL_KC + 1];
-	const int tid = threadIdx.x;
-	const long long g = blockIdx.x;
-	int plo = 0, phi = A.n_pairs;
-	while (phi - plo > 1) {
-		const int mid = (plo + phi) >> 1;
-		if (A.pairs[mid].tile_off <= g) plo = mid;
-		else phi = mid;
-	}
-	const AlPair u = A.pairs[plo];
-	const long long t = g - u.tile_off;
-	const int i0 = (int)(t / u.tiles_j) * AL_TILE;
-	if (i0 >= u.n) return;
-	const int i_last = min(i0 + AL_TILE - 1, u.n - 1);
-	int lo0, hi0, lo1, hi1;
-	al_row(u, i0, lo0, hi0);
-	al_row(u, i_last, lo1, hi1);
-	const long long j0l = (long long)lo0 + (t % u.tiles_j) * AL_TILE;
-	if (j0l > hi1) return;  // (the whole workgroup: lo and hi do not fall with i)
-	const int j0 = (int)j0l;
-	const int tx = tid & (AL_TILE - 1), ty = tid >> 5;
-	double acc[4] = {0.0, 0.0, 0.0, 0.0};
-	for (int c0 = A.dim_begin; c0 < A.dim_end; c0 += AL_KC) {
-		const int kc = min(AL_KC, A.dim_end - c0);
-		for (int e = tid; e < AL_TILE * AL_KC; e += 256) {
-			const int r = e >> 5, c = e & (AL_KC - 1);
-			const bool in = c < kc;
-			sa[r][c] = in && i0 + r < u.n ? A.fa[(u.a_off + i0 + r) * A.dims + c0 + c] : 0.0;
-			sb[r][c] = in && j0 + r < u.m ? A.fb[(u.b_off + j0 + r) * A.dims + c0 + c] : 0.0;
-		}
-		__syncthreads();
-		for (int c = 0; c < kc; ++c) {
-			const double b = sb[tx][c];
-#pragma unroll
-			for (int k = 0; k < 4; ++k) {
-				const double d = sa[ty + 8 * k][c] - b;
-				acc[k] = acc[k] + d * d;
-			}
-		}
-		__syncthreads();
-	}
-	const int j = j0 + tx;
-#pragma unroll
-	for (int k = 0; k < 4; ++k) {
-		const int i = i0 + ty + 8 * k;
-		if (i >= u.n || j >= u.m) continue;
-		int lo, hi;
-		al_row(u, i, lo, hi);
-		if (j < lo || j > hi) continue;
-		A.cells[u.cell_off + (long long)i * u.W + (j - lo)] = __dsqrt_rn(acc[k]);
-	}
-}
 
 // OPEN_BEGIN: every allowed cell of row 0 starts a path, D(0, j) = d(0, j)
 template <bool OPEN_BEGIN>

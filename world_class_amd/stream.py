@@ -57,6 +57,17 @@ STREAM_SIGNATURES = {
     "wc_morph_stream_backlog": (C.c_int, [_vp, C.c_int, C.c_int]),
     "wc_morph_stream_frames_formed": (C.c_longlong, [_vp, C.c_int]),
 }
+# the alignment streams (include/world_class_align_stream.h, which world_class_stream.h includes): a table of their own, bound with
+# the one above
+ALIGN_STREAM_SIGNATURES = {
+    "wc_align_stream_create": (_vp, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "wc_align_stream_destroy": (None, [_vp]),
+    "wc_align_stream_set_track_device": (C.c_int, [_vp, C.c_int, C.c_int, _vp]),
+    "wc_align_stream_reset": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int]),
+    "wc_align_stream_push_device": (C.c_int, [_vp, _ip, _vp, _vp, _vp]),
+    "wc_align_stream_rows_received": (C.c_longlong, [_vp, C.c_int]),
+    "wc_align_stream_track_length": (C.c_int, [_vp, C.c_int]),
+}
 _bound = False
 
 
@@ -69,7 +80,7 @@ def _lib():
     global _bound
     L = lib()
     if not _bound:
-        for name, (res, args) in STREAM_SIGNATURES.items():
+        for name, (res, args) in list(STREAM_SIGNATURES.items()) + list(ALIGN_STREAM_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
@@ -496,5 +507,87 @@ class MorphStream:
             if getattr(self, "_h", None):
                 _lib().wc_morph_stream_destroy(self._h)
                 self._h = None
+        except Exception:
+            pass
+
+
+class AlignStream:
+    """n_streams concurrent alignment streams over n_tracks resident tracks of coded rows (dims doubles, compared over
+    dim_begin <= c < dim_end): every push appends up to `max_rows_per_push` rows of a live voice per stream and returns, per pushed
+    row, its position in the stream's track and the cost so far -- d_cost and span[1] of one whole-utterance
+    io.align_features_ex_device pair (the rows so far, the track) at step pattern 0 with an open end (the rule of the header)."""
+
+    def __init__(self, dims, n_streams, n_tracks, max_track_frames, max_rows_per_push, dim_begin=1, dim_end=None):
+        L = _lib()
+        self.dims, self.n_streams, self.n_tracks = int(dims), int(n_streams), int(n_tracks)
+        self.max_track_frames, self.max_rows_per_push = int(max_track_frames), int(max_rows_per_push)
+        self.dim_begin, self.dim_end = int(dim_begin), int(dims if dim_end is None else dim_end)
+        self._h = _handle(L.wc_align_stream_create(self.dims, self.dim_begin, self.dim_end, self.n_streams, self.n_tracks, self.max_track_frames,
+                                                   self.max_rows_per_push))
+        self._out = None  # the outputs of push: allocated on its first call
+
+    def set_track_device(self, track, m, d_feat):
+        """m rows of a device array into the slot (stream-ordered; refused while a stream that has received rows follows it)"""
+        _check(_lib().wc_align_stream_set_track_device(self._h, int(track), int(m), _opt(d_feat)))
+
+    def set_track(self, track, feat):
+        feat = np.ascontiguousarray(feat, dtype=np.float64)
+        if feat.ndim != 2 or feat.shape[1] != self.dims:
+            raise ValueError("a track is an (m, dims) array")
+        d = DeviceArray.from_host(feat)
+        try:
+            self.set_track_device(track, feat.shape[0], d)
+            _check(lib().wc_synchronize())
+        finally:
+            d.free()
+
+    def reset(self, stream, track, open_begin=False):
+        """attach the stream to a track that has been set; its row count returns to zero"""
+        _check(_lib().wc_align_stream_reset(self._h, int(stream), int(track), 1 if open_begin else 0))
+
+    def push_device(self, n_rows, d_feat, d_position, d_cost):
+        """device pointers in and out (packed layouts of the header): one position and one cost per pushed row"""
+        if len(n_rows) != self.n_streams:
+            raise ValueError("one row count per stream")
+        _check(_lib().wc_align_stream_push_device(self._h, _ints(n_rows), _opt(d_feat), _opt(d_position), _opt(d_cost)))
+
+    def push(self, rows):
+        """rows[u]: a (k_u, dims) array with the new rows of stream u, or None.  Returns per stream (position, cost), k_u doubles
+        each."""
+        if len(rows) != self.n_streams:
+            raise ValueError("one entry per stream")
+        mats = [np.zeros((0, self.dims)) if r is None else np.asarray(r, dtype=np.float64).reshape(-1, self.dims) for r in rows]
+        counts = [len(v) for v in mats]
+        tot = sum(counts)
+        if self._out is None:
+            cap = self.n_streams * self.max_rows_per_push
+            self._out = (DeviceArray(cap), DeviceArray(cap))
+        d = DeviceArray.from_host(np.concatenate(mats)) if tot else None
+        try:
+            self.push_device(counts, d, self._out[0], self._out[1])
+            pos, cost = (o.to_host()[:tot] for o in self._out) if tot else (np.zeros(0), np.zeros(0))
+        finally:
+            if d is not None:
+                d.free()
+        res, o = [], 0
+        for c in counts:
+            res.append((pos[o:o + c].copy(), cost[o:o + c].copy()))
+            o += c
+        return res
+
+    def rows_received(self, stream):
+        return int(_lib().wc_align_stream_rows_received(self._h, int(stream)))
+
+    def track_length(self, track):
+        return int(_lib().wc_align_stream_track_length(self._h, int(track)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib().wc_align_stream_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
         except Exception:
             pass
