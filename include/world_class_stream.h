@@ -313,5 +313,7 @@ long long wc_morph_stream_frames_formed(const wc_morph_stream *m, int stream);
  * The streaming form of wc_align_features_ex_device at step pattern 0 with an open end: every pushed row gets its position in the
  * track and the cost so far, from one row of state per stream.  The rule and the wc_align_stream_* calls are in the header below. */
 #include "world_class_align_stream.h"
+/* A search window around the last position and a position that never falls (wc_align_stream_set_window): the header below. */
+#include "world_class_align_window.h"
 
 #endif /* WORLD_CLASS_STREAM_H */

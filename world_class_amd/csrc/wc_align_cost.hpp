@@ -2,6 +2,7 @@
 // (wc_align_stream.hip): the pair descriptors, the band's row ranges and align_cost_kernel.  One kernel for both, so that the
 // rounding of d(i, j) -- ascending c from 0.0; difference, product and sum rounded apart (-ffp-contract=off); the correctly rounded
 // root -- cannot drift apart between a stream's rows and the call they are held against.
+// al_cell_costs is the same arithmetic per cell for the one caller whose columns are decided on the device (the windowed streams).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -45,6 +46,26 @@ __device__ __forceinline__ void al_row(const AlPair &u, int i, int &lo, int &hi)
 	const long long l = x - u.B, h = (x + u.B) / q;
 	lo = l <= 0 ? 0 : (int)((l + q - 1) / q);
 	hi = h > u.m - 1 ? u.m - 1 : (int)h;
+}
+
+// d(i, j) of N cells by one lane, for a caller that cannot go through the kernel below (the windowed alignment streams, whose columns
+// are decided on the device): a[k] and b[k] point at the two rows of cell k.  Per cell it is the kernel's arithmetic: ascending c from
+// 0.0, the difference, the product and the sum rounded apart, the correctly rounded root; the N chains only hide each other's loads.
+template <int N>
+__device__ __forceinline__ void al_cell_costs(const double *const (&a)[N], const double *const (&b)[N], int dim_begin, int dim_end,
+                                              double (&out)[N]) {
+	double acc[N];
+#pragma unroll
+	for (int k = 0; k < N; ++k) acc[k] = 0.0;
+	for (int c = dim_begin; c < dim_end; ++c) {
+#pragma unroll
+		for (int k = 0; k < N; ++k) {
+			const double d = a[k][c] - b[k][c];
+			acc[k] = acc[k] + d * d;
+		}
+	}
+#pragma unroll
+	for (int k = 0; k < N; ++k) out[k] = __dsqrt_rn(acc[k]);
 }
 
 static __global__ __launch_bounds__(256) void align_cost_kernel(AlArgs A) {

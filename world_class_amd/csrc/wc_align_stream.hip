@@ -1,8 +1,8 @@
 // Alignment streams (include/world_class_align_stream.h: wc_align_stream): a live voice is followed row by row through a known
 // track.  The streaming form of wc_align_features_ex_device (wc_align.hip) at step pattern 0, band 0 and an open end: row i of D
 // needs row i - 1 of D and row i of d only, so a stream carries one row of D from push to push and every pushed row gets the
-// open-end scan of its own row of D -- the position in the track and the cost so far.  Two launches per push, both bounded by
-// counts the host wrote into the descriptors:
+// open-end scan of its own row of D -- the position in the track and the cost so far.  Two launches per push for the streams
+// without a search window and one for those with, all bounded by counts the host wrote into the descriptors:
 //
 //   align_cost_kernel   (wc_align_cost.hpp, the whole call's kernel and so its rounding)  one AlPair per stream that has rows: the
 //     pushed rows against the stream's track, W = m, no band, into the stream's part of the handle's d buffer.
@@ -18,10 +18,25 @@
 //     together, then the chain of three comparisons and one sum per cell runs on registers.  Each lane keeps its row's running
 //     (best, j*) under the strict < of the open-end scan and writes d_position / d_cost when its row has ended.
 //
-//   A push is host arithmetic (every refusal), one asynchronous copy of the descriptors out of page-locked staging and the two
-//   launches; set_track is one asynchronous device-to-device copy.
+//   align_window_rows_kernel   (include/world_class_align_window.h) the streams with a search window are left out of the two launches
+//     above and take this one: one 64-lane wavefront per windowed stream that has rows, no barrier, no LDS.  The window's start is
+//     decided on the device from a position that an earlier row of the same push produced, so the host cannot hand
+//     align_cost_kernel the columns.  The host's part is the arithmetic of the passes: a pass never crosses an epoch boundary (hop rows
+//     on the absolute row index, at most 64), so all its rows share one window [lo, lo + w).  Per pass: (a) lo and w from the window of
+//     the row before, its position and the floor q -- read from the stream's record (AwRec) in front of the first pass, carried in
+//     uniform registers between the passes, written back behind the last; (b) all 64 lanes compute the R x w local costs with
+//     al_cell_costs (wc_align_cost.hpp: the cost kernel's arithmetic per cell) into the stream's part of d; a fence; (c) the
+//     lane-skewed chain of the kernel above over the w columns from lo, where lane 0 takes a state cell only inside the window of the
+//     row before (+inf outside: never stale memory) and starts its diagonal from D(i - 1, lo - 1) where the window has moved on.
+//     Under WC_ALIGN_WINDOW_MONOTONE row i's floor is row i - 1's result: a pass of one row scans under the floor in the chain; a
+//     longer pass stores D over d, and behind a fence the wavefront scans the rows one after the other, 64 columns at a time.
+//
+//   A push is host arithmetic (every refusal), one asynchronous copy of the descriptors out of page-locked staging and the
+//   launches (two for the plain streams, one for the windowed; a kind without rows is not launched); set_track is one asynchronous
+//   device-to-device copy.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <vector>
 
 #include "../../include/world_class_io.h"
@@ -111,6 +126,166 @@ __global__ __launch_bounds__(64) void align_stream_rows_kernel(AsArgs A) {
 	}
 }
 
+constexpr int AW_CELLS = 4;  // local costs a lane computes side by side
+
+struct AwWork {
+	long long out_off;  // first pushed row of the stream in the packed rows and outputs
+	long long b_off;    // first row of the stream's track
+	long long d_off;    // the stream's local costs: row r of the push at r * m, column j of its window at j - lo
+	long long st_off;   // the stream's two state rows (indexed by the absolute column)
+	long long first;    // rows the stream had received before this push
+	int u;              // the stream: its window record
+	int n, m;           // rows pushed / rows of the track
+	int parity;
+	int flags;          // of the reset
+	int W, back, hop;   // min(width, m), back, hop
+	int monotone;
+};
+
+// what the next row needs of the last: its window, its written position (-1: NaN) and the last position that was not NaN (0: none)
+struct AwRec {
+	int lo, w, pos, q;
+};
+
+struct AwArgs {
+	const AwWork *work;
+	const double *fa, *fb;
+	double *d, *state;
+	AwRec *rec;
+	long long max_m;
+	int dims, dim_begin, dim_end;
+	double *position, *cost;
+};
+
+__global__ __launch_bounds__(64) void align_window_rows_kernel(AwArgs A) {
+	const AwWork w = A.work[blockIdx.x];
+	const int lane = threadIdx.x;
+	const double inf = __builtin_inf();
+	const int m = w.m;
+	const bool open_begin = (w.flags & WC_ALIGN_OPEN_BEGIN) != 0, monotone = w.monotone != 0;
+	int par = w.parity;
+	int plo = 0, pw = 0, ppos = -1, q = 0;  // the record of the row before the pass (uniform)
+	if (w.first > 0) {
+		const AwRec r = A.rec[w.u];
+		plo = r.lo; pw = r.w; ppos = r.pos; q = r.q;
+	}
+	for (int i0 = 0; i0 < w.n;) {  // (every trip count below is the wavefront's, but for the loops that say otherwise)
+		const long long abs0 = w.first + i0;
+		const int in_epoch = (int)(abs0 % w.hop);
+		const int R = min(w.n - i0, w.hop - in_epoch);  // rows of this pass: to the end of the push or of the epoch
+		// (a) the window of the pass
+		int lo = plo, wd = pw;
+		if (abs0 == 0) {
+			lo = 0; wd = open_begin ? m : w.W;
+		} else if (in_epoch == 0) {
+			lo = ppos < 0 ? plo : min(max(plo, ppos - w.back), m - w.W);
+			wd = w.W;
+		}
+		// (b) the R x wd local costs
+		double *dpass = A.d + w.d_off + (long long)i0 * m;
+		const int cells = R * wd;  // (at most max_rows_per_push x max_track_frames <= 2^28)
+		for (int base = 0; base < cells; base += 64 * AW_CELLS) {
+			const double *pa[AW_CELLS], *pb[AW_CELLS];
+			double v[AW_CELLS];
+			long long at[AW_CELLS];
+#pragma unroll
+			for (int k = 0; k < AW_CELLS; ++k) {
+				const int cell = base + 64 * k + lane;
+				const int c = cell < cells ? cell : 0;  // (a lane without a cell computes cell 0 again and stores nothing)
+				const int r = c / wd, jr = c - r * wd;
+				pa[k] = A.fa + (w.out_off + i0 + r) * A.dims;
+				pb[k] = A.fb + (w.b_off + lo + jr) * A.dims;
+				at[k] = cell < cells ? (long long)r * m + jr : -1;
+			}
+			al_cell_costs<AW_CELLS>(pa, pb, A.dim_begin, A.dim_end, v);
+#pragma unroll
+			for (int k = 0; k < AW_CELLS; ++k)
+				if (at[k] >= 0) dpass[at[k]] = v[k];
+		}
+		__threadfence();  // the local costs, before the lane of their row loads them
+		// (c) the chain over the window
+		const bool mine = lane < R, last = lane == R - 1;
+		const bool has_prev = abs0 > 0;
+		const bool row0 = abs0 + lane == 0;
+		const bool post = monotone && R > 1;  // rows 1.. of the pass do not know their floor while the chain runs
+		const int floor_j = monotone ? q : 0;
+		const double *src = A.state + w.st_off + (long long)par * A.max_m;
+		double *dst = A.state + w.st_off + (long long)(par ^ 1) * A.max_m;
+		double *drow = dpass + (long long)(mine ? lane : 0) * m;
+		double cur = inf;
+		// D(i - 1, lo - 1): a cell of the window of the row before where the window has moved on, +inf otherwise
+		double diag = lane == 0 && has_prev && lo - 1 >= plo && lo - 1 < plo + pw ? src[lo - 1] : inf;
+		double best = inf;
+		int bj = -1;
+		const int steps = wd + R - 1;
+		for (int s0 = 0; s0 < steps; s0 += AL_CHUNK) {
+			double dv[AL_CHUNK], sv[AL_CHUNK];
+#pragma unroll
+			for (int k = 0; k < AL_CHUNK; ++k) {
+				const int jr = s0 + k - lane, j = lo + jr;
+				const bool in = mine && jr >= 0 && jr < wd;
+				dv[k] = in ? drow[jr] : 0.0;
+				sv[k] = in && lane == 0 && has_prev && j >= plo && j < plo + pw ? src[j] : inf;
+			}
+#pragma unroll
+			for (int k = 0; k < AL_CHUNK; ++k) {
+				double up = __shfl_up(cur, 1);
+				if (lane == 0) up = sv[k];
+				const int jr = s0 + k - lane, j = lo + jr;
+				if (mine && jr >= 0 && jr < wd) {
+					const double Dd = diag, Du = up, Dl = cur;
+					double b;
+					if (Dd <= Du && Dd <= Dl) b = Dd;
+					else if (Du <= Dl) b = Du;
+					else b = Dl;
+					const double D = (row0 && (open_begin || j == 0)) ? dv[k] : dv[k] + b;
+					if (j >= floor_j && D < best) { best = D; bj = j; }
+					if (last) dst[j] = D;
+					if (post) drow[jr] = D;
+					cur = D;
+				}
+				diag = up;
+			}
+		}
+		if (post) {  // the scans again, row after row under the floor the row before left: 64 columns at a time, the lowest column of the least D
+			__threadfence();
+			for (int r = 0; r < R; ++r) {
+				const double *row = dpass + (long long)r * m;
+				double b = inf;
+				int at = -1;
+				for (int jr = lane; jr < wd; jr += 64) {  // (the lane's own trip count: nothing crosses the lanes in here)
+					const double D = row[jr];
+					if (lo + jr >= q && D < b) { b = D; at = lo + jr; }
+				}
+#pragma unroll
+				for (int off = 32; off > 0; off >>= 1) {
+					const double ob = __shfl_xor(b, off);
+					const int oa = __shfl_xor(at, off);
+					if (ob < b || (ob == b && oa < at)) { b = ob; at = oa; }
+				}
+				if (lane == r) { best = b; bj = at; }
+				if (at >= 0) q = at;
+			}
+		}
+		if (mine) {
+			const long long o = w.out_off + i0 + lane;
+			A.cost[o] = bj >= 0 ? best : cur;  // (cur: D(i, lo + wd - 1))
+			A.position[o] = bj >= 0 ? (double)bj : __builtin_nan("");
+		}
+		ppos = __builtin_amdgcn_readfirstlane(__shfl(bj, R - 1));
+		if (monotone && !post && ppos >= 0) q = ppos;  // (a pass of one row)
+		plo = lo; pw = wd;
+		par ^= 1;
+		i0 += R;
+		if (i0 < w.n) __threadfence();  // the new state row, before lane 0 of the next pass reads it
+	}
+	if (lane == 0) {
+		AwRec r;
+		r.lo = plo; r.w = pw; r.pos = ppos; r.q = q;
+		A.rec[w.u] = r;
+	}
+}
+
 }  // namespace
 
 struct wc_align_stream {
@@ -121,13 +296,15 @@ struct wc_align_stream {
 		int flags = 0;
 		int parity = 0;      // the state row that holds D of the newest row
 		long long rows = 0;  // rows received since the reset
+		int width = 0, back = 0, hop = 1, wflags = 0;  // the search window (world_class_align_window.h); width 0: none
 	};
 	std::vector<Stream> st;
 	std::vector<int> track_m;  // rows per slot, 0: empty
 	DevBuf tracks;             // n_tracks x max_m rows of dims
 	DevBuf d;                  // n_streams x max_rows x max_m local costs
 	DevBuf state;              // n_streams x 2 x max_m
-	DevBuf drec;               // the descriptors of a push: AlPair per stream with rows | AsWork per stream with rows
+	DevBuf wrec;               // n_streams window records (AwRec)
+	DevBuf drec;               // the descriptors of a push: AlPair, then AsWork per plain stream with rows | AwWork per windowed stream with rows
 	HostBuf h_rec[2];          // their page-locked staging: a pair, so that a push waits for the copy of the push before the last only
 	int parity = 0;
 };
@@ -169,8 +346,8 @@ wc_align_stream *wc_align_stream_create(int dims, int dim_begin, int dim_end, in
 	h->dev = dev;
 	h->st.assign(n_streams, wc_align_stream::Stream());
 	h->track_m.assign(n_tracks, 0);
-	const size_t rec = (sizeof(AlPair) + sizeof(AsWork)) * (size_t)n_streams;
-	if (h->tracks.reserve(sizeof(double) * (size_t)track_rows * dims) || h->d.reserve(sizeof(double) * (size_t)sr * max_track_frames) ||
+	const size_t rec = std::max(sizeof(AlPair) + sizeof(AsWork), sizeof(AwWork)) * (size_t)n_streams;
+	if (h->wrec.reserve(sizeof(AwRec) * (size_t)n_streams) || h->tracks.reserve(sizeof(double) * (size_t)track_rows * dims) || h->d.reserve(sizeof(double) * (size_t)sr * max_track_frames) ||
 		h->state.reserve(sizeof(double) * (size_t)2 * n_streams * max_track_frames) || h->drec.reserve(rec) || h->h_rec[0].reserve(rec) ||
 		h->h_rec[1].reserve(rec)) {
 		wc_align_stream_destroy(h);
@@ -182,7 +359,7 @@ wc_align_stream *wc_align_stream_create(int dims, int dim_begin, int dim_end, in
 void wc_align_stream_destroy(wc_align_stream *h) {
 	if (!h) return;
 	h->dev->quiesce();
-	h->tracks.release(); h->d.release(); h->state.release(); h->drec.release(); h->h_rec[0].release(); h->h_rec[1].release();
+	h->tracks.release(); h->d.release(); h->state.release(); h->wrec.release(); h->drec.release(); h->h_rec[0].release(); h->h_rec[1].release();
 	delete h;
 }
 
@@ -209,6 +386,7 @@ int wc_align_stream_reset(wc_align_stream *h, int stream, int track, int flags) 
 	if (h->track_m[track] == 0) return fail(WC_ERR_INVALID, "align stream reset: the track has not been set");
 	wc_align_stream::Stream &s = h->st[stream];
 	s.track = track; s.flags = flags; s.rows = 0;  // (the parity stays: row 0 reads no state row)
+	s.width = 0; s.back = 0; s.hop = 1; s.wflags = 0;
 	return WC_OK;
 }
 
@@ -217,36 +395,47 @@ int wc_align_stream_push_device(wc_align_stream *h, const int *n_rows, const dou
 	DeviceLock lock(h->dev);
 	const int n = h->n_streams;
 	long long total = 0;
-	int active = 0;
+	int plain = 0, windowed = 0;  // streams with rows: without / with a search window
 	for (int u = 0; u < n; ++u) {
 		if (n_rows[u] < 0) return fail(WC_ERR_INVALID, "align stream push: negative row count");
 		if (n_rows[u] > h->max_rows) return fail(WC_ERR_INVALID, "align stream push: more than max_rows_per_push rows for one stream");
 		if (n_rows[u] > 0 && h->st[u].track < 0) return fail(WC_ERR_INVALID, "align stream push: rows for a stream that was never reset onto a track");
 		total += n_rows[u];
-		active += n_rows[u] > 0;
+		if (n_rows[u] > 0) ++(h->st[u].width > 0 ? windowed : plain);
 	}
 	if (total == 0) return WC_OK;
 	if (!d_feat_a || !d_position || !d_cost) return fail(WC_ERR_INVALID, "align stream push: null array");
 	// ---- the descriptors (no refusal is left) ----
 	if (h->h_rec[h->parity].reserve(0)) return WC_ERR_DEVICE;  // (the copy of the push before the last has read this staging)
 	AlPair *pairs = h->h_rec[h->parity].as<AlPair>();
-	AsWork *work = reinterpret_cast<AsWork *>(pairs + active);
+	AsWork *work = reinterpret_cast<AsWork *>(pairs + plain);
+	AwWork *wwork = reinterpret_cast<AwWork *>(work + plain);
 	long long off = 0, tiles = 0;
-	int k = 0;
+	int k = 0, kw = 0;
 	for (int u = 0; u < n; ++u) {
 		const int c = n_rows[u];
 		if (c == 0) continue;
 		const wc_align_stream::Stream &s = h->st[u];
 		const int m = h->track_m[s.track];
+		const long long b_off = (long long)s.track * h->max_m, d_off = (long long)u * h->max_rows * h->max_m;
+		const long long st_off = (long long)u * 2 * h->max_m;
+		if (s.width > 0) {
+			AwWork &w = wwork[kw++];
+			w.out_off = off; w.b_off = b_off; w.d_off = d_off; w.st_off = st_off; w.first = s.rows;
+			w.u = u; w.n = c; w.m = m; w.parity = s.parity; w.flags = s.flags;
+			w.W = std::min(s.width, m); w.back = s.back; w.hop = s.hop; w.monotone = (s.wflags & WC_ALIGN_WINDOW_MONOTONE) != 0;
+			off += c;
+			continue;
+		}
 		AlPair &q = pairs[k];
-		q.a_off = off; q.b_off = (long long)s.track * h->max_m;
-		q.cell_off = (long long)u * h->max_rows * h->max_m;
+		q.a_off = off; q.b_off = b_off;
+		q.cell_off = d_off;
 		q.path_off = 0; q.tile_off = tiles; q.B = -1;
 		q.n = c; q.m = m; q.W = m;
 		q.tiles_j = (m + AL_TILE - 1) / AL_TILE;
 		tiles += (long long)((c + AL_TILE - 1) / AL_TILE) * q.tiles_j;
 		AsWork &w = work[k];
-		w.out_off = off; w.d_off = q.cell_off; w.st_off = (long long)u * 2 * h->max_m; w.first = s.rows;
+		w.out_off = off; w.d_off = d_off; w.st_off = st_off; w.first = s.rows;
 		w.n = c; w.m = m; w.parity = s.parity; w.flags = s.flags;
 		off += c;
 		++k;
@@ -255,32 +444,74 @@ int wc_align_stream_push_device(wc_align_stream *h, const int *n_rows, const dou
 	WC_HIP(hipSetDevice(h->dev->id));
 	hipStream_t hs = h->dev->active();
 	int rc;
-	const size_t bytes = (sizeof(AlPair) + sizeof(AsWork)) * (size_t)active;
+	const size_t bytes = (sizeof(AlPair) + sizeof(AsWork)) * (size_t)plain + sizeof(AwWork) * (size_t)windowed;
 	WC_HIP(hipMemcpyAsync(h->drec.p, pairs, bytes, hipMemcpyHostToDevice, hs));
 	if ((rc = h->h_rec[h->parity].mark(hs))) return rc;
-	AlArgs a = {};
-	a.pairs = h->drec.as<AlPair>();
-	a.n_pairs = active; a.dims = h->dims; a.dim_begin = h->dim_begin; a.dim_end = h->dim_end;
-	a.fa = d_feat_a; a.fb = h->tracks.as<double>();
-	a.cells = h->d.as<double>();
-	AsArgs x;
-	x.work = reinterpret_cast<const AsWork *>(a.pairs + active);
-	x.d = h->d.as<double>(); x.state = h->state.as<double>(); x.max_m = h->max_m;
-	x.position = d_position; x.cost = d_cost;
-	if ((rc = h->dev->time_begin("align_stream_cost_kernel", hs))) return rc;
-	hipLaunchKernelGGL(align_cost_kernel, dim3((unsigned)tiles), dim3(256), 0, hs, a);
-	WC_HIP(hipGetLastError());
-	if ((rc = h->dev->time_end("align_stream_cost_kernel", hs))) return rc;
-	if ((rc = h->dev->time_begin("align_stream_rows_kernel", hs))) return rc;
-	hipLaunchKernelGGL(align_stream_rows_kernel, dim3((unsigned)active), dim3(64), 0, hs, x);
-	WC_HIP(hipGetLastError());
-	if ((rc = h->dev->time_end("align_stream_rows_kernel", hs))) return rc;
+	const AlPair *d_pairs = h->drec.as<AlPair>();
+	const AsWork *d_work = reinterpret_cast<const AsWork *>(d_pairs + plain);
+	if (plain > 0) {
+		AlArgs a = {};
+		a.pairs = d_pairs;
+		a.n_pairs = plain; a.dims = h->dims; a.dim_begin = h->dim_begin; a.dim_end = h->dim_end;
+		a.fa = d_feat_a; a.fb = h->tracks.as<double>();
+		a.cells = h->d.as<double>();
+		AsArgs x;
+		x.work = d_work;
+		x.d = h->d.as<double>(); x.state = h->state.as<double>(); x.max_m = h->max_m;
+		x.position = d_position; x.cost = d_cost;
+		if ((rc = h->dev->time_begin("align_stream_cost_kernel", hs))) return rc;
+		hipLaunchKernelGGL(align_cost_kernel, dim3((unsigned)tiles), dim3(256), 0, hs, a);
+		WC_HIP(hipGetLastError());
+		if ((rc = h->dev->time_end("align_stream_cost_kernel", hs))) return rc;
+		if ((rc = h->dev->time_begin("align_stream_rows_kernel", hs))) return rc;
+		hipLaunchKernelGGL(align_stream_rows_kernel, dim3((unsigned)plain), dim3(64), 0, hs, x);
+		WC_HIP(hipGetLastError());
+		if ((rc = h->dev->time_end("align_stream_rows_kernel", hs))) return rc;
+	}
+	if (windowed > 0) {
+		AwArgs x;
+		x.work = reinterpret_cast<const AwWork *>(d_work + plain);
+		x.fa = d_feat_a; x.fb = h->tracks.as<double>();
+		x.d = h->d.as<double>(); x.state = h->state.as<double>(); x.rec = h->wrec.as<AwRec>(); x.max_m = h->max_m;
+		x.dims = h->dims; x.dim_begin = h->dim_begin; x.dim_end = h->dim_end;
+		x.position = d_position; x.cost = d_cost;
+		if ((rc = h->dev->time_begin("align_window_rows_kernel", hs))) return rc;
+		hipLaunchKernelGGL(align_window_rows_kernel, dim3((unsigned)windowed), dim3(64), 0, hs, x);
+		WC_HIP(hipGetLastError());
+		if ((rc = h->dev->time_end("align_window_rows_kernel", hs))) return rc;
+	}
 	for (int u = 0; u < n; ++u) {
 		wc_align_stream::Stream &s = h->st[u];
+		if (n_rows[u] == 0) continue;
+		// one flip per pass: of up to 64 rows, or under a window of the rows of one epoch
+		const long long passes = s.width > 0 ? (s.rows + n_rows[u] - 1) / s.hop - s.rows / s.hop + 1 : (n_rows[u] + 63) / 64;
 		s.rows += n_rows[u];
-		s.parity ^= ((n_rows[u] + 63) / 64) & 1;  // one flip per pass
+		s.parity ^= (int)(passes & 1);
 	}
 	h->parity = 1 - h->parity;
+	return WC_OK;
+}
+
+int wc_align_stream_set_window(wc_align_stream *h, int stream, int width, int back, int hop, int flags) {
+	if (!as_stream_ok(h, stream)) return fail(WC_ERR_INVALID, "align stream: bad stream index");
+	if (width < 0 || back < 0 || (width > 0 ? back >= width : back != 0))
+		return fail(WC_ERR_INVALID, "align stream set_window: need 0 <= back < width, or width = 0 and back = 0");
+	if (hop < 1 || hop > 64 || (width == 0 && hop != 1)) return fail(WC_ERR_INVALID, "align stream set_window: need 1 <= hop <= 64, and hop = 1 with width = 0");
+	if ((flags != 0 && flags != WC_ALIGN_WINDOW_MONOTONE) || (width == 0 && flags != 0))
+		return fail(WC_ERR_INVALID, "align stream set_window: flags must be 0 or WC_ALIGN_WINDOW_MONOTONE, and 0 with width = 0");
+	DeviceLock lock(h->dev);
+	wc_align_stream::Stream &s = h->st[stream];
+	if (s.track < 0) return fail(WC_ERR_INVALID, "align stream set_window: the stream was never reset onto a track");
+	if (s.rows > 0) return fail(WC_ERR_INVALID, "align stream set_window: the stream has received rows (reset it first)");
+	s.width = width; s.back = back; s.hop = hop; s.wflags = flags;
+	return WC_OK;
+}
+
+int wc_align_stream_get_window(const wc_align_stream *h, int stream, int *width, int *back, int *hop, int *flags) {
+	if (!as_stream_ok(h, stream)) return fail(WC_ERR_INVALID, "align stream: bad stream index");
+	if (!width || !back || !hop || !flags) return fail(WC_ERR_INVALID, "align stream get_window: null pointer");
+	const wc_align_stream::Stream &s = h->st[stream];
+	*width = s.width; *back = s.back; *hop = s.hop; *flags = s.wflags;
 	return WC_OK;
 }
 

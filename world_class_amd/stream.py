@@ -68,6 +68,13 @@ ALIGN_STREAM_SIGNATURES = {
     "wc_align_stream_rows_received": (C.c_longlong, [_vp, C.c_int]),
     "wc_align_stream_track_length": (C.c_int, [_vp, C.c_int]),
 }
+# the search window of an alignment stream (include/world_class_align_window.h, included just below the header above): again a
+# table of its own
+ALIGN_WINDOW_SIGNATURES = {
+    "wc_align_stream_set_window": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "wc_align_stream_get_window": (C.c_int, [_vp, C.c_int, _ip, _ip, _ip, _ip]),
+}
+ALIGN_WINDOW_MONOTONE = 1
 _bound = False
 
 
@@ -80,7 +87,7 @@ def _lib():
     global _bound
     L = lib()
     if not _bound:
-        for name, (res, args) in list(STREAM_SIGNATURES.items()) + list(ALIGN_STREAM_SIGNATURES.items()):
+        for name, (res, args) in list(STREAM_SIGNATURES.items()) + list(ALIGN_STREAM_SIGNATURES.items()) + list(ALIGN_WINDOW_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
@@ -544,6 +551,18 @@ class AlignStream:
     def reset(self, stream, track, open_begin=False):
         """attach the stream to a track that has been set; its row count returns to zero"""
         _check(_lib().wc_align_stream_reset(self._h, int(stream), int(track), 1 if open_begin else 0))
+
+    def set_window(self, stream, width, back, hop=1, monotone=False):
+        """a search window of `width` columns that starts `back` columns behind the position and moves every `hop` rows, on a stream
+        that has been reset and has no rows yet (the rule of world_class_align_window.h); monotone: the position never falls.
+        width 0 (back 0, hop 1) removes it; so does every reset"""
+        _check(_lib().wc_align_stream_set_window(self._h, int(stream), int(width), int(back), int(hop), ALIGN_WINDOW_MONOTONE if monotone else 0))
+
+    def get_window(self, stream):
+        """(width, back, hop, monotone); (0, 0, 1, False) where no window is set"""
+        v = [C.c_int() for _ in range(4)]
+        _check(_lib().wc_align_stream_get_window(self._h, int(stream), *[C.byref(x) for x in v]))
+        return v[0].value, v[1].value, v[2].value, bool(v[3].value & ALIGN_WINDOW_MONOTONE)
 
     def push_device(self, n_rows, d_feat, d_position, d_cost):
         """device pointers in and out (packed layouts of the header): one position and one cost per pushed row"""
