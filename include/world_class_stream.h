@@ -315,5 +315,8 @@ long long wc_morph_stream_frames_formed(const wc_morph_stream *m, int stream);
 #include "world_class_align_stream.h"
 /* A search window around the last position and a position that never falls (wc_align_stream_set_window): the header below. */
 #include "world_class_align_window.h"
+/* Settled positions from a lagged backtrack: where the row L frames ago lies on the path behind the newest row, and the flush
+ * (wc_align_stream_reserve_lag, _set_lag, _push_settled_device, _tail_device): the header below. */
+#include "world_class_align_lag.h"
 
 #endif /* WORLD_CLASS_STREAM_H */

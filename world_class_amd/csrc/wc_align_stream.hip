@@ -31,9 +31,14 @@
 //     Under WC_ALIGN_WINDOW_MONOTONE row i's floor is row i - 1's result: a pass of one row scans under the floor in the chain; a
 //     longer pass stores D over d, and behind a fence the wavefront scans the rows one after the other, 64 columns at a time.
 //
+//   align_stream_settle_kernel, align_stream_tail_kernel   (include/world_class_align_lag.h) a stream with a lag has the two row
+//     kernels store every cell's choice in a ring of bytes; behind them the settle kernel walks back from each pushed row's
+//     position to the row `lag` frames ago, and the tail kernel does the same walk from the newest row on request.  Their comment
+//     stands with them below.
+//
 //   A push is host arithmetic (every refusal), one asynchronous copy of the descriptors out of page-locked staging and the
-//   launches (two for the plain streams, one for the windowed; a kind without rows is not launched); set_track is one asynchronous
-//   device-to-device copy.
+//   launches (two for the plain streams, one for the windowed, one more for a settled push; a kind without rows is not launched);
+//   set_track is one asynchronous device-to-device copy.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -58,16 +63,26 @@ struct AsWork {
 	int n, m;           // rows pushed / rows of the track
 	int parity;         // the state row that holds D of the last row before this push
 	int flags;
+	int u;                // the stream: its entry of lastpos
+	unsigned char *ring;  // the stream's ring of choices (world_class_align_lag.h), or null: the stream has no lag
 };
 
 struct AsArgs {
 	const AsWork *work;
 	const double *d;
 	double *state;
-	long long max_m;  // doubles per state row
+	long long max_m;  // doubles per state row, bytes per ring row
 	double *position, *cost;
+	int ring_cap;     // rows of a stream's ring
+	int *lastpos;     // per stream with a lag: the column written for its newest row, -1 for NaN
 };
 
+// the choices of a cell, one byte each in a stream's ring: the whole call's three (wc_align_cost.hpp: AlArgs::choice) and the start
+constexpr int AS_DIAG = 0, AS_UP = 1, AS_LEFT = 2, AS_START = 3;
+
+// LAG: some stream of the launch has a ring.  A push whose streams have none runs the instantiation without the stores: the code
+// of the kernel as it was before the ring.
+template <bool LAG>
 __global__ __launch_bounds__(64) void align_stream_rows_kernel(AsArgs A) {
 	const AsWork w = A.work[blockIdx.x];
 	const int lane = threadIdx.x;
@@ -83,6 +98,8 @@ __global__ __launch_bounds__(64) void align_stream_rows_kernel(AsArgs A) {
 		const double *__restrict__ src = A.state + w.st_off + (long long)par * A.max_m;
 		double *__restrict__ dst = A.state + w.st_off + (long long)(par ^ 1) * A.max_m;
 		const double *__restrict__ drow = A.d + w.d_off + (long long)(mine ? i0 + lane : i0) * m;
+		// the ring row of this lane's row: absolute row % cap, indexed by the absolute column
+		unsigned char *__restrict__ crow = LAG && w.ring ? w.ring + ((w.first + i0 + (mine ? lane : 0)) % A.ring_cap) * A.max_m : nullptr;
 		double cur = inf;   // this lane's last result: D(i, j - 1), and what lane + 1 takes as D(i, j) one step later
 		double diag = inf;  // what came from above one step ago: D(i - 1, j - 1)
 		double best = inf;
@@ -105,10 +122,13 @@ __global__ __launch_bounds__(64) void align_stream_rows_kernel(AsArgs A) {
 				if (mine && j >= 0 && j < m) {
 					const double Dd = diag, Du = up, Dl = cur;
 					double b;
-					if (Dd <= Du && Dd <= Dl) b = Dd;
-					else if (Du <= Dl) b = Du;
-					else b = Dl;
-					const double D = (row0 && (open_begin || j == 0)) ? dv[k] : dv[k] + b;
+					int c;
+					if (Dd <= Du && Dd <= Dl) { b = Dd; c = AS_DIAG; }
+					else if (Du <= Dl) { b = Du; c = AS_UP; }
+					else { b = Dl; c = AS_LEFT; }
+					const bool start = row0 && (open_begin || j == 0);
+					const double D = start ? dv[k] : dv[k] + b;
+					if (LAG && crow) crow[j] = (unsigned char)(start ? AS_START : c);
 					if (D < best) { best = D; bj = j; }
 					if (last) dst[j] = D;
 					cur = D;
@@ -120,6 +140,7 @@ __global__ __launch_bounds__(64) void align_stream_rows_kernel(AsArgs A) {
 			const long long o = w.out_off + i0 + lane;
 			A.cost[o] = bj >= 0 ? best : cur;  // (cur: D(i, m - 1))
 			A.position[o] = bj >= 0 ? (double)bj : __builtin_nan("");
+			if (LAG && w.ring && i0 + lane == w.n - 1) A.lastpos[w.u] = bj;  // (where wc_align_stream_tail_device starts)
 		}
 		par ^= 1;
 		if (i0 + 64 < w.n) __threadfence();  // the new state row, before lane 0 of the next pass reads it
@@ -140,6 +161,7 @@ struct AwWork {
 	int flags;          // of the reset
 	int W, back, hop;   // min(width, m), back, hop
 	int monotone;
+	unsigned char *ring;  // the stream's ring of choices, or null: the stream has no lag
 };
 
 // what the next row needs of the last: its window, its written position (-1: NaN) and the last position that was not NaN (0: none)
@@ -155,8 +177,11 @@ struct AwArgs {
 	long long max_m;
 	int dims, dim_begin, dim_end;
 	double *position, *cost;
+	int ring_cap;
+	int *lastpos;
 };
 
+template <bool LAG>
 __global__ __launch_bounds__(64) void align_window_rows_kernel(AwArgs A) {
 	const AwWork w = A.work[blockIdx.x];
 	const int lane = threadIdx.x;
@@ -212,6 +237,7 @@ __global__ __launch_bounds__(64) void align_window_rows_kernel(AwArgs A) {
 		const double *src = A.state + w.st_off + (long long)par * A.max_m;
 		double *dst = A.state + w.st_off + (long long)(par ^ 1) * A.max_m;
 		double *drow = dpass + (long long)(mine ? lane : 0) * m;
+		unsigned char *crow = LAG && w.ring ? w.ring + ((abs0 + (mine ? lane : 0)) % A.ring_cap) * A.max_m : nullptr;
 		double cur = inf;
 		// D(i - 1, lo - 1): a cell of the window of the row before where the window has moved on, +inf otherwise
 		double diag = lane == 0 && has_prev && lo - 1 >= plo && lo - 1 < plo + pw ? src[lo - 1] : inf;
@@ -235,10 +261,13 @@ __global__ __launch_bounds__(64) void align_window_rows_kernel(AwArgs A) {
 				if (mine && jr >= 0 && jr < wd) {
 					const double Dd = diag, Du = up, Dl = cur;
 					double b;
-					if (Dd <= Du && Dd <= Dl) b = Dd;
-					else if (Du <= Dl) b = Du;
-					else b = Dl;
-					const double D = (row0 && (open_begin || j == 0)) ? dv[k] : dv[k] + b;
+					int c;
+					if (Dd <= Du && Dd <= Dl) { b = Dd; c = AS_DIAG; }
+					else if (Du <= Dl) { b = Du; c = AS_UP; }
+					else { b = Dl; c = AS_LEFT; }
+					const bool start = row0 && (open_begin || j == 0);
+					const double D = start ? dv[k] : dv[k] + b;
+					if (LAG && crow) crow[j] = (unsigned char)(start ? AS_START : c);
 					if (j >= floor_j && D < best) { best = D; bj = j; }
 					if (last) dst[j] = D;
 					if (post) drow[jr] = D;
@@ -283,6 +312,105 @@ __global__ __launch_bounds__(64) void align_window_rows_kernel(AwArgs A) {
 		AwRec r;
 		r.lo = plo; r.w = pw; r.pos = ppos; r.q = q;
 		A.rec[w.u] = r;
+		if (LAG && w.ring) A.lastpos[w.u] = ppos;
+	}
+}
+
+// ---- settled positions from a lagged backtrack (include/world_class_align_lag.h) ----
+//
+// A stream with a lag keeps the choices of its last cap = max_lag + max_rows_per_push rows in a ring of bytes: the two kernels above
+// store, for every cell they compute, which predecessor the three comparisons took (or AS_START), at ring row (absolute row) % cap and
+// the absolute column.  A push of rows [f, f + n) walks back to rows >= f - L; the ring then holds rows f + n - cap .. f + n - 1,
+// which covers them because n <= max_rows_per_push and L <= max_lag.
+//
+// Why stale ring bytes cannot show.  A walk starts at the winner of a row's scan, whose D is finite.  A cell's D is its cost plus the
+// chosen predecessor, and where that sum is finite the predecessor is: the comparisons take a finite term over +inf and never a
+// NaN.  So a path from a finite cell visits finite cells only -- cells that the stream computed since its reset, inside their rows'
+// windows -- and never reads a byte from outside a row's window or from before the reset.  (The walks below still stop at a
+// column below 0 or at a byte that is no choice, and give NaN: what a broken ring would cost is a wrong number, not a wild load.)
+struct SeWork {
+	long long out_off;  // settle: first pushed row of the stream in the packed outputs; tail: the stream's first entry of d_tail
+	long long first;    // settle: rows received before this push; tail: rows received
+	const unsigned char *ring;  // null (settle only): no lag, d_settled = d_position
+	int u, n, lag;      // the stream; settle: rows pushed, tail: K entries to write; the lag
+};
+
+struct SeArgs {
+	const SeWork *work;
+	int n_work;       // (the tail's bound)
+	long long max_m;  // bytes per ring row
+	int ring_cap;
+	const double *position;
+	const int *lastpos;
+	double *out;      // d_settled / d_tail
+};
+
+// the path's cells in one row: from (the row at ring slot `slot`, j) through the row's left steps to its lowest column, which
+// replaces j.  The half-integer centre of the cells, or NaN where the walk breaks
+__device__ inline double se_row(const SeArgs &A, const unsigned char *ring, int slot, int &j) {
+	const unsigned char *row = ring + (long long)slot * A.max_m;
+	const int jmax = j;
+	while (row[j] == AS_LEFT) {  // (the lane's own trip count: nothing crosses the lanes in here)
+		if (j == 0) return __builtin_nan("");
+		--j;
+	}
+	return (j + jmax) * 0.5;
+}
+
+// one step up from the lowest cell (slot, j) of the path in a row: false where the byte is neither diagonal nor up
+__device__ inline bool se_up(const SeArgs &A, const unsigned char *ring, int &slot, int &j) {
+	const int c = ring[(long long)slot * A.max_m + j];
+	if (c == AS_DIAG) {
+		if (j == 0) return false;
+		--j;
+	} else if (c != AS_UP) {
+		return false;
+	}
+	slot = slot == 0 ? A.ring_cap - 1 : slot - 1;
+	return true;
+}
+
+// launched behind the row kernels of the same push, so that the order on the stream has made their choices and d_position
+// visible: one 64-lane wavefront per stream that has rows, no barrier.  Lane l takes pushed rows l, l + 64, ..: from (i, j*_i) it
+// walks its own path back to row t = max(i - L, 0) and through that row's left steps, and writes d_settled.  Every loop has the
+// lane's own trip count (each step lowers the row or the column: at most L + m steps); nothing crosses the lanes.
+__global__ __launch_bounds__(64) void align_stream_settle_kernel(SeArgs A) {
+	const SeWork w = A.work[blockIdx.x];
+	for (int r = threadIdx.x; r < w.n; r += 64) {
+		const long long o = w.out_off + r;
+		const double p = A.position[o];
+		double s = p;
+		if (w.ring && p == p) {
+			const long long i = w.first + r;
+			int up = (int)min(i, (long long)w.lag);  // rows to climb
+			int slot = (int)(i % A.ring_cap), j = (int)p;
+			s = se_row(A, w.ring, slot, j);
+			while (up > 0 && s == s) {
+				s = se_up(A, w.ring, slot, j) ? se_row(A, w.ring, slot, j) : __builtin_nan("");
+				--up;
+			}
+		}
+		A.out[o] = s;
+	}
+}
+
+// wc_align_stream_tail_device: the same walk from the stream's newest row, one lane per wanted stream, writing every row it passes
+__global__ __launch_bounds__(64) void align_stream_tail_kernel(SeArgs A) {
+	const int k = blockIdx.x * 64 + threadIdx.x;
+	if (k >= A.n_work) return;
+	const SeWork w = A.work[k];
+	double *out = A.out + w.out_off;
+	int j = A.lastpos[w.u];
+	int slot = (int)((w.first - 1) % A.ring_cap);
+	bool ok = j >= 0;
+	for (int e = w.n - 1; e >= 0; --e) {  // (entry e: row n - K + e)
+		double s = __builtin_nan("");
+		if (ok) {
+			s = se_row(A, w.ring, slot, j);
+			ok = s == s;
+		}
+		out[e] = s;
+		if (ok && e > 0) ok = se_up(A, w.ring, slot, j);
 	}
 }
 
@@ -297,6 +425,7 @@ struct wc_align_stream {
 		int parity = 0;      // the state row that holds D of the newest row
 		long long rows = 0;  // rows received since the reset
 		int width = 0, back = 0, hop = 1, wflags = 0;  // the search window (world_class_align_window.h); width 0: none
+		int lag = 0;         // the lag of the settled position (world_class_align_lag.h); 0: none
 	};
 	std::vector<Stream> st;
 	std::vector<int> track_m;  // rows per slot, 0: empty
@@ -304,7 +433,12 @@ struct wc_align_stream {
 	DevBuf d;                  // n_streams x max_rows x max_m local costs
 	DevBuf state;              // n_streams x 2 x max_m
 	DevBuf wrec;               // n_streams window records (AwRec)
-	DevBuf drec;               // the descriptors of a push: AlPair, then AsWork per plain stream with rows | AwWork per windowed stream with rows
+	DevBuf ring;               // wc_align_stream_reserve_lag: n_streams x ring_cap x max_m choices, one byte each
+	DevBuf lastpos;            // and n_streams ints: the column written for a stream's newest row
+	int max_lag = 0, ring_cap = 0;  // 0: no reservation
+	// the descriptors of a push: AlPair, then AsWork per plain stream with rows | AwWork per windowed stream with rows | SeWork per
+	// stream with rows of a settled push; of a tail: SeWork per wanted stream
+	DevBuf drec;
 	HostBuf h_rec[2];          // their page-locked staging: a pair, so that a push waits for the copy of the push before the last only
 	int parity = 0;
 };
@@ -346,7 +480,7 @@ wc_align_stream *wc_align_stream_create(int dims, int dim_begin, int dim_end, in
 	h->dev = dev;
 	h->st.assign(n_streams, wc_align_stream::Stream());
 	h->track_m.assign(n_tracks, 0);
-	const size_t rec = std::max(sizeof(AlPair) + sizeof(AsWork), sizeof(AwWork)) * (size_t)n_streams;
+	const size_t rec = (std::max(sizeof(AlPair) + sizeof(AsWork), sizeof(AwWork)) + sizeof(SeWork)) * (size_t)n_streams;
 	if (h->wrec.reserve(sizeof(AwRec) * (size_t)n_streams) || h->tracks.reserve(sizeof(double) * (size_t)track_rows * dims) || h->d.reserve(sizeof(double) * (size_t)sr * max_track_frames) ||
 		h->state.reserve(sizeof(double) * (size_t)2 * n_streams * max_track_frames) || h->drec.reserve(rec) || h->h_rec[0].reserve(rec) ||
 		h->h_rec[1].reserve(rec)) {
@@ -359,7 +493,7 @@ wc_align_stream *wc_align_stream_create(int dims, int dim_begin, int dim_end, in
 void wc_align_stream_destroy(wc_align_stream *h) {
 	if (!h) return;
 	h->dev->quiesce();
-	h->tracks.release(); h->d.release(); h->state.release(); h->wrec.release(); h->drec.release(); h->h_rec[0].release(); h->h_rec[1].release();
+	h->tracks.release(); h->d.release(); h->state.release(); h->wrec.release(); h->ring.release(); h->lastpos.release(); h->drec.release(); h->h_rec[0].release(); h->h_rec[1].release();
 	delete h;
 }
 
@@ -387,10 +521,16 @@ int wc_align_stream_reset(wc_align_stream *h, int stream, int track, int flags) 
 	wc_align_stream::Stream &s = h->st[stream];
 	s.track = track; s.flags = flags; s.rows = 0;  // (the parity stays: row 0 reads no state row)
 	s.width = 0; s.back = 0; s.hop = 1; s.wflags = 0;
+	s.lag = 0;
 	return WC_OK;
 }
 
-int wc_align_stream_push_device(wc_align_stream *h, const int *n_rows, const double *d_feat_a, double *d_position, double *d_cost) {
+}  // extern "C"
+
+namespace {
+
+// wc_align_stream_push_device (settle = false: d_settled is not looked at) and wc_align_stream_push_settled_device
+int as_push(wc_align_stream *h, const int *n_rows, const double *d_feat_a, double *d_position, double *d_cost, double *d_settled, bool settle) {
 	if (!h || !n_rows) return fail(WC_ERR_INVALID, "align stream push: null argument");
 	DeviceLock lock(h->dev);
 	const int n = h->n_streams;
@@ -404,14 +544,17 @@ int wc_align_stream_push_device(wc_align_stream *h, const int *n_rows, const dou
 		if (n_rows[u] > 0) ++(h->st[u].width > 0 ? windowed : plain);
 	}
 	if (total == 0) return WC_OK;
-	if (!d_feat_a || !d_position || !d_cost) return fail(WC_ERR_INVALID, "align stream push: null array");
+	if (!d_feat_a || !d_position || !d_cost || (settle && !d_settled)) return fail(WC_ERR_INVALID, "align stream push: null array");
 	// ---- the descriptors (no refusal is left) ----
 	if (h->h_rec[h->parity].reserve(0)) return WC_ERR_DEVICE;  // (the copy of the push before the last has read this staging)
 	AlPair *pairs = h->h_rec[h->parity].as<AlPair>();
 	AsWork *work = reinterpret_cast<AsWork *>(pairs + plain);
 	AwWork *wwork = reinterpret_cast<AwWork *>(work + plain);
+	SeWork *swork = reinterpret_cast<SeWork *>(wwork + windowed);
+	const int settled = settle ? plain + windowed : 0;  // a settled push: one item per stream with rows
 	long long off = 0, tiles = 0;
-	int k = 0, kw = 0;
+	int k = 0, kw = 0, ks = 0;
+	bool plain_lag = false, windowed_lag = false;  // a stream of the kind has rows and a ring
 	for (int u = 0; u < n; ++u) {
 		const int c = n_rows[u];
 		if (c == 0) continue;
@@ -419,11 +562,19 @@ int wc_align_stream_push_device(wc_align_stream *h, const int *n_rows, const dou
 		const int m = h->track_m[s.track];
 		const long long b_off = (long long)s.track * h->max_m, d_off = (long long)u * h->max_rows * h->max_m;
 		const long long st_off = (long long)u * 2 * h->max_m;
+		unsigned char *ring = s.lag > 0 ? h->ring.as<unsigned char>() + (size_t)u * h->ring_cap * h->max_m : nullptr;
+		if (settle) {
+			SeWork &e = swork[ks++];
+			e.out_off = off; e.first = s.rows; e.ring = ring;
+			e.u = u; e.n = c; e.lag = s.lag;
+		}
 		if (s.width > 0) {
 			AwWork &w = wwork[kw++];
 			w.out_off = off; w.b_off = b_off; w.d_off = d_off; w.st_off = st_off; w.first = s.rows;
 			w.u = u; w.n = c; w.m = m; w.parity = s.parity; w.flags = s.flags;
 			w.W = std::min(s.width, m); w.back = s.back; w.hop = s.hop; w.monotone = (s.wflags & WC_ALIGN_WINDOW_MONOTONE) != 0;
+			w.ring = ring;
+			windowed_lag |= ring != nullptr;
 			off += c;
 			continue;
 		}
@@ -437,6 +588,8 @@ int wc_align_stream_push_device(wc_align_stream *h, const int *n_rows, const dou
 		AsWork &w = work[k];
 		w.out_off = off; w.d_off = d_off; w.st_off = st_off; w.first = s.rows;
 		w.n = c; w.m = m; w.parity = s.parity; w.flags = s.flags;
+		w.u = u; w.ring = ring;
+		plain_lag |= ring != nullptr;
 		off += c;
 		++k;
 	}
@@ -444,7 +597,7 @@ int wc_align_stream_push_device(wc_align_stream *h, const int *n_rows, const dou
 	WC_HIP(hipSetDevice(h->dev->id));
 	hipStream_t hs = h->dev->active();
 	int rc;
-	const size_t bytes = (sizeof(AlPair) + sizeof(AsWork)) * (size_t)plain + sizeof(AwWork) * (size_t)windowed;
+	const size_t bytes = (sizeof(AlPair) + sizeof(AsWork)) * (size_t)plain + sizeof(AwWork) * (size_t)windowed + sizeof(SeWork) * (size_t)settled;
 	WC_HIP(hipMemcpyAsync(h->drec.p, pairs, bytes, hipMemcpyHostToDevice, hs));
 	if ((rc = h->h_rec[h->parity].mark(hs))) return rc;
 	const AlPair *d_pairs = h->drec.as<AlPair>();
@@ -459,12 +612,14 @@ int wc_align_stream_push_device(wc_align_stream *h, const int *n_rows, const dou
 		x.work = d_work;
 		x.d = h->d.as<double>(); x.state = h->state.as<double>(); x.max_m = h->max_m;
 		x.position = d_position; x.cost = d_cost;
+		x.ring_cap = h->ring_cap; x.lastpos = h->lastpos.as<int>();
 		if ((rc = h->dev->time_begin("align_stream_cost_kernel", hs))) return rc;
 		hipLaunchKernelGGL(align_cost_kernel, dim3((unsigned)tiles), dim3(256), 0, hs, a);
 		WC_HIP(hipGetLastError());
 		if ((rc = h->dev->time_end("align_stream_cost_kernel", hs))) return rc;
 		if ((rc = h->dev->time_begin("align_stream_rows_kernel", hs))) return rc;
-		hipLaunchKernelGGL(align_stream_rows_kernel, dim3((unsigned)plain), dim3(64), 0, hs, x);
+		if (plain_lag) hipLaunchKernelGGL(align_stream_rows_kernel<true>, dim3((unsigned)plain), dim3(64), 0, hs, x);
+		else hipLaunchKernelGGL(align_stream_rows_kernel<false>, dim3((unsigned)plain), dim3(64), 0, hs, x);
 		WC_HIP(hipGetLastError());
 		if ((rc = h->dev->time_end("align_stream_rows_kernel", hs))) return rc;
 	}
@@ -475,10 +630,22 @@ int wc_align_stream_push_device(wc_align_stream *h, const int *n_rows, const dou
 		x.d = h->d.as<double>(); x.state = h->state.as<double>(); x.rec = h->wrec.as<AwRec>(); x.max_m = h->max_m;
 		x.dims = h->dims; x.dim_begin = h->dim_begin; x.dim_end = h->dim_end;
 		x.position = d_position; x.cost = d_cost;
+		x.ring_cap = h->ring_cap; x.lastpos = h->lastpos.as<int>();
 		if ((rc = h->dev->time_begin("align_window_rows_kernel", hs))) return rc;
-		hipLaunchKernelGGL(align_window_rows_kernel, dim3((unsigned)windowed), dim3(64), 0, hs, x);
+		if (windowed_lag) hipLaunchKernelGGL(align_window_rows_kernel<true>, dim3((unsigned)windowed), dim3(64), 0, hs, x);
+		else hipLaunchKernelGGL(align_window_rows_kernel<false>, dim3((unsigned)windowed), dim3(64), 0, hs, x);
 		WC_HIP(hipGetLastError());
 		if ((rc = h->dev->time_end("align_window_rows_kernel", hs))) return rc;
+	}
+	if (settled > 0) {  // behind the row kernels: their choices and d_position are visible by the order on the stream
+		SeArgs x = {};
+		x.work = reinterpret_cast<const SeWork *>(reinterpret_cast<const AwWork *>(d_work + plain) + windowed);
+		x.n_work = settled; x.max_m = h->max_m; x.ring_cap = h->ring_cap;
+		x.position = d_position; x.lastpos = h->lastpos.as<int>(); x.out = d_settled;
+		if ((rc = h->dev->time_begin("align_stream_settle_kernel", hs))) return rc;
+		hipLaunchKernelGGL(align_stream_settle_kernel, dim3((unsigned)settled), dim3(64), 0, hs, x);
+		WC_HIP(hipGetLastError());
+		if ((rc = h->dev->time_end("align_stream_settle_kernel", hs))) return rc;
 	}
 	for (int u = 0; u < n; ++u) {
 		wc_align_stream::Stream &s = h->st[u];
@@ -488,6 +655,94 @@ int wc_align_stream_push_device(wc_align_stream *h, const int *n_rows, const dou
 		s.rows += n_rows[u];
 		s.parity ^= (int)(passes & 1);
 	}
+	h->parity = 1 - h->parity;
+	return WC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int wc_align_stream_push_device(wc_align_stream *h, const int *n_rows, const double *d_feat_a, double *d_position, double *d_cost) {
+	return as_push(h, n_rows, d_feat_a, d_position, d_cost, nullptr, false);
+}
+
+int wc_align_stream_push_settled_device(wc_align_stream *h, const int *n_rows, const double *d_feat_a, double *d_position, double *d_cost,
+										double *d_settled) {
+	return as_push(h, n_rows, d_feat_a, d_position, d_cost, d_settled, true);
+}
+
+int wc_align_stream_reserve_lag(wc_align_stream *h, int max_lag) {
+	if (!h) return fail(WC_ERR_INVALID, "align stream reserve_lag: null handle");
+	if (max_lag < 1) return fail(WC_ERR_INVALID, "align stream reserve_lag: max_lag must be at least 1");
+	DeviceLock lock(h->dev);
+	if (h->max_lag > 0) return fail(WC_ERR_INVALID, "align stream reserve_lag: the handle has a reservation");
+	// (64-bit, a factor at a time: cap <= 2^32, n_streams x cap <= 2^60, and only a product within 2^30 meets the next factor)
+	const long long cap = (long long)max_lag + h->max_rows, limit = 1ll << 30;
+	if (cap > limit || cap * h->n_streams > limit || cap * h->n_streams * h->max_m > limit)
+		return fail(WC_ERR_INVALID, "align stream reserve_lag: n_streams x (max_lag + max_rows_per_push) x max_track_frames above 2^30 bytes");
+	WC_HIP(hipSetDevice(h->dev->id));
+	if (h->ring.reserve((size_t)(cap * h->n_streams * h->max_m)) || h->lastpos.reserve(sizeof(int) * (size_t)h->n_streams)) {
+		h->ring.release(); h->lastpos.release();
+		return WC_ERR_DEVICE;
+	}
+	h->max_lag = max_lag; h->ring_cap = (int)cap;
+	return WC_OK;
+}
+
+int wc_align_stream_set_lag(wc_align_stream *h, int stream, int lag) {
+	if (!as_stream_ok(h, stream)) return fail(WC_ERR_INVALID, "align stream: bad stream index");
+	DeviceLock lock(h->dev);
+	if (lag < 0 || lag > h->max_lag) return fail(WC_ERR_INVALID, "align stream set_lag: need 0 <= lag <= max_lag of wc_align_stream_reserve_lag");
+	wc_align_stream::Stream &s = h->st[stream];
+	if (s.track < 0) return fail(WC_ERR_INVALID, "align stream set_lag: the stream was never reset onto a track");
+	if (s.rows > 0) return fail(WC_ERR_INVALID, "align stream set_lag: the stream has received rows (reset it first)");
+	s.lag = lag;
+	return WC_OK;
+}
+
+int wc_align_stream_get_lag(const wc_align_stream *h, int stream) {
+	if (!as_stream_ok(h, stream)) return -1;
+	return h->st[stream].lag;
+}
+
+int wc_align_stream_tail_device(wc_align_stream *h, const int *want, double *d_tail) {
+	if (!h || !want || !d_tail) return fail(WC_ERR_INVALID, "align stream tail: null argument");
+	DeviceLock lock(h->dev);
+	int count = 0;
+	for (int u = 0; u < h->n_streams; ++u) {
+		if (!want[u]) continue;
+		if (h->st[u].lag == 0) return fail(WC_ERR_INVALID, "align stream tail: a wanted stream has no lag");
+		if (h->st[u].rows == 0) return fail(WC_ERR_INVALID, "align stream tail: a wanted stream has no rows");
+		++count;
+	}
+	if (count == 0) return WC_OK;
+	if (h->h_rec[h->parity].reserve(0)) return WC_ERR_DEVICE;
+	SeWork *work = h->h_rec[h->parity].as<SeWork>();
+	long long off = 0;
+	int k = 0;
+	for (int u = 0; u < h->n_streams; ++u) {
+		if (!want[u]) continue;
+		const wc_align_stream::Stream &s = h->st[u];
+		SeWork &e = work[k++];
+		e.out_off = off; e.first = s.rows;
+		e.ring = h->ring.as<unsigned char>() + (size_t)u * h->ring_cap * h->max_m;
+		e.u = u; e.n = (int)std::min<long long>(s.lag + 1, s.rows); e.lag = s.lag;
+		off += e.n;
+	}
+	WC_HIP(hipSetDevice(h->dev->id));
+	hipStream_t hs = h->dev->active();
+	int rc;
+	WC_HIP(hipMemcpyAsync(h->drec.p, work, sizeof(SeWork) * (size_t)count, hipMemcpyHostToDevice, hs));
+	if ((rc = h->h_rec[h->parity].mark(hs))) return rc;
+	SeArgs x = {};
+	x.work = h->drec.as<SeWork>();
+	x.n_work = count; x.max_m = h->max_m; x.ring_cap = h->ring_cap;
+	x.lastpos = h->lastpos.as<int>(); x.out = d_tail;
+	if ((rc = h->dev->time_begin("align_stream_tail_kernel", hs))) return rc;
+	hipLaunchKernelGGL(align_stream_tail_kernel, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, hs, x);
+	WC_HIP(hipGetLastError());
+	if ((rc = h->dev->time_end("align_stream_tail_kernel", hs))) return rc;
 	h->parity = 1 - h->parity;
 	return WC_OK;
 }

@@ -75,6 +75,14 @@ ALIGN_WINDOW_SIGNATURES = {
     "wc_align_stream_get_window": (C.c_int, [_vp, C.c_int, _ip, _ip, _ip, _ip]),
 }
 ALIGN_WINDOW_MONOTONE = 1
+# settled positions from a lagged backtrack (include/world_class_align_lag.h, included below the window's header): a fourth table
+ALIGN_LAG_SIGNATURES = {
+    "wc_align_stream_reserve_lag": (C.c_int, [_vp, C.c_int]),
+    "wc_align_stream_set_lag": (C.c_int, [_vp, C.c_int, C.c_int]),
+    "wc_align_stream_get_lag": (C.c_int, [_vp, C.c_int]),
+    "wc_align_stream_push_settled_device": (C.c_int, [_vp, _ip, _vp, _vp, _vp, _vp]),
+    "wc_align_stream_tail_device": (C.c_int, [_vp, _ip, _vp]),
+}
 _bound = False
 
 
@@ -87,7 +95,7 @@ def _lib():
     global _bound
     L = lib()
     if not _bound:
-        for name, (res, args) in list(STREAM_SIGNATURES.items()) + list(ALIGN_STREAM_SIGNATURES.items()) + list(ALIGN_WINDOW_SIGNATURES.items()):
+        for name, (res, args) in list(STREAM_SIGNATURES.items()) + list(ALIGN_STREAM_SIGNATURES.items()) + list(ALIGN_WINDOW_SIGNATURES.items()) + list(ALIGN_LAG_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
@@ -532,6 +540,7 @@ class AlignStream:
         self._h = _handle(L.wc_align_stream_create(self.dims, self.dim_begin, self.dim_end, self.n_streams, self.n_tracks, self.max_track_frames,
                                                    self.max_rows_per_push))
         self._out = None  # the outputs of push: allocated on its first call
+        self._settled = None  # the third output of push_settled: allocated on its first call
 
     def set_track_device(self, track, m, d_feat):
         """m rows of a device array into the slot (stream-ordered; refused while a stream that has received rows follows it)"""
@@ -564,34 +573,90 @@ class AlignStream:
         _check(_lib().wc_align_stream_get_window(self._h, int(stream), *[C.byref(x) for x in v]))
         return v[0].value, v[1].value, v[2].value, bool(v[3].value & ALIGN_WINDOW_MONOTONE)
 
+    def reserve_lag(self, max_lag):
+        """the ring of choices behind set_lag: one byte per cell, max_lag + max_rows_per_push rows of max_track_frames per stream
+        (the rule of world_class_align_lag.h); once per handle"""
+        _check(_lib().wc_align_stream_reserve_lag(self._h, int(max_lag)))
+
+    def set_lag(self, stream, lag):
+        """push_settled reports where the row `lag` frames ago lies on the path behind the newest row; on a stream that has been
+        reset and has no rows yet, 0 <= lag <= max_lag of reserve_lag.  0 removes the lag; so does every reset"""
+        _check(_lib().wc_align_stream_set_lag(self._h, int(stream), int(lag)))
+
+    def get_lag(self, stream):
+        """the stream's lag (0: none); -1 for a bad index"""
+        return int(_lib().wc_align_stream_get_lag(self._h, int(stream)))
+
     def push_device(self, n_rows, d_feat, d_position, d_cost):
         """device pointers in and out (packed layouts of the header): one position and one cost per pushed row"""
         if len(n_rows) != self.n_streams:
             raise ValueError("one row count per stream")
         _check(_lib().wc_align_stream_push_device(self._h, _ints(n_rows), _opt(d_feat), _opt(d_position), _opt(d_cost)))
 
-    def push(self, rows):
-        """rows[u]: a (k_u, dims) array with the new rows of stream u, or None.  Returns per stream (position, cost), k_u doubles
-        each."""
+    def push_settled_device(self, n_rows, d_feat, d_position, d_cost, d_settled):
+        """push_device with one more output packed the same way: per pushed row, where the row `lag` frames ago lies on the path
+        behind it (the position itself for a stream without a lag)"""
+        if len(n_rows) != self.n_streams:
+            raise ValueError("one row count per stream")
+        _check(_lib().wc_align_stream_push_settled_device(self._h, _ints(n_rows), _opt(d_feat), _opt(d_position), _opt(d_cost), _opt(d_settled)))
+
+    def _push(self, rows, n_out):
         if len(rows) != self.n_streams:
             raise ValueError("one entry per stream")
         mats = [np.zeros((0, self.dims)) if r is None else np.asarray(r, dtype=np.float64).reshape(-1, self.dims) for r in rows]
         counts = [len(v) for v in mats]
         tot = sum(counts)
+        cap = self.n_streams * self.max_rows_per_push
         if self._out is None:
-            cap = self.n_streams * self.max_rows_per_push
             self._out = (DeviceArray(cap), DeviceArray(cap))
+        if n_out == 3 and self._settled is None:
+            self._settled = DeviceArray(cap)
+        outs = self._out + ((self._settled,) if n_out == 3 else ())
         d = DeviceArray.from_host(np.concatenate(mats)) if tot else None
         try:
-            self.push_device(counts, d, self._out[0], self._out[1])
-            pos, cost = (o.to_host()[:tot] for o in self._out) if tot else (np.zeros(0), np.zeros(0))
+            if n_out == 3:
+                self.push_settled_device(counts, d, *outs)
+            else:
+                self.push_device(counts, d, *outs)
+            got = [o.to_host()[:tot] for o in outs] if tot else [np.zeros(0)] * n_out
         finally:
             if d is not None:
                 d.free()
         res, o = [], 0
         for c in counts:
-            res.append((pos[o:o + c].copy(), cost[o:o + c].copy()))
+            res.append(tuple(g[o:o + c].copy() for g in got))
             o += c
+        return res
+
+    def push(self, rows):
+        """rows[u]: a (k_u, dims) array with the new rows of stream u, or None.  Returns per stream (position, cost), k_u doubles
+        each."""
+        return self._push(rows, 2)
+
+    def push_settled(self, rows):
+        """push with the settled positions: per stream (position, cost, settled), k_u doubles each"""
+        return self._push(rows, 3)
+
+    def tail(self, streams=None):
+        """the flush: per stream in `streams` (None: every stream that has a lag and rows) the K = min(lag + 1, rows received)
+        half-integers of the newest row's path in the stream's last K rows, ascending.  Returns one array per stream of the
+        handle, None for a stream that was not asked for.  Changes no state"""
+        if streams is None:
+            streams = [u for u in range(self.n_streams) if self.get_lag(u) > 0 and self.rows_received(u) > 0]
+        want = [0] * self.n_streams
+        for u in streams:
+            want[int(u)] = 1
+        ks = [min(self.get_lag(u) + 1, self.rows_received(u)) if want[u] else 0 for u in range(self.n_streams)]
+        d = DeviceArray(max(sum(ks), 1))
+        try:
+            _check(_lib().wc_align_stream_tail_device(self._h, _ints(want), _ptr(d)))
+            got = d.to_host()
+        finally:
+            d.free()
+        res, o = [], 0
+        for u, k in enumerate(ks):
+            res.append(got[o:o + k].copy() if want[u] else None)
+            o += k
         return res
 
     def rows_received(self, stream):
