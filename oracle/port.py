@@ -74,6 +74,8 @@ class Port:
                                         _dp, _dp, _dp, _dp, _dp, _dp, _dp]
         L.wco_synthesis_pulses.restype = C.c_int
         L.wco_synthesis_pulses.argtypes = [_dp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, _ip]
+        L.wco_synthesis_pulse_list.restype = C.c_int
+        L.wco_synthesis_pulse_list.argtypes = [_dp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, _ip, _ip]
         L.wco_set_threads(threads)
 
     def set_harvest_options(self, target_fs=8000.0, channels_in_octave=40.0, use_cos_table=False):
@@ -171,6 +173,18 @@ class Port:
         cap = C.c_int(0)
         n = self.lib.wco_synthesis_pulses(_p(f0), len(f0), fft_size, fs, frame_period, out_length, C.byref(cap))
         return n, cap.value
+
+    def synthesis_pulse_list(self, f0, fft_size, fs, frame_period=5.0, out_length=None):
+        """(sample index, voiced flag) of every pulse of the time base; pulse i draws index[i + 1] - index[i] noise samples"""
+        f0 = _c(f0)
+        if out_length is None:
+            out_length = int((len(f0) - 1) * frame_period / 1000.0 * fs) + 1
+        cap = out_length + 1
+        index = np.zeros(cap, dtype=np.int32)
+        voiced = np.zeros(cap, dtype=np.int32)
+        n = self.lib.wco_synthesis_pulse_list(_p(f0), len(f0), fft_size, fs, frame_period, out_length, cap,
+                                              index.ctypes.data_as(_ip), voiced.ctypes.data_as(_ip))
+        return index[:n].copy(), voiced[:n].astype(bool)
 
     def pipeline(self, x, fs, harvest_floor=71.0, frame_period=5.0, given_f0=None):
         """Demo order of reference test/test.cpp:288-384, RNG at its seed state."""

@@ -1307,6 +1307,19 @@ int wco_synthesis_pulses(const double *f0, int f0_length, int fft_size, int fs, 
 	if (reference_capacity) *reference_capacity = max_f0 > 0 ? out_length / static_cast<int>(fs / max_f0) : 0;
 	return static_cast<int>(P.index.size());
 }
+// the pulses themselves: sample index and voiced flag (vuv at that sample) of the first `capacity` pulses; returns the count.
+// Pulse i draws index[i + 1] - index[i] noise samples, the last one none (synthesis() above).
+int wco_synthesis_pulse_list(const double *f0, int f0_length, int fft_size, int fs, double frame_period_ms,
+							 int out_length, int capacity, int *index, int *voiced) {
+	Pulses P;
+	synth_time_base(f0, f0_length, fs, frame_period_ms / 1000., out_length, fs / fft_size + 1.0, P);
+	const int np = static_cast<int>(P.index.size());
+	for (int i = 0; i < np && i < capacity; ++i) {
+		index[i] = P.index[i];
+		voiced[i] = P.vuv[P.index[i]] != 0.0 ? 1 : 0;
+	}
+	return np;
+}
 uint64_t wco_cheaptrick_draws(int fs, const double *f0, int f0_length, double f0_floor, int fft_size) {
 	int N = fft_size ? fft_size : ct_fft_size(fs, f0_floor);
 	double floor_ = ct_f0_floor(fs, N);

@@ -59,6 +59,11 @@ void wco_synthesis(const double *f0, int f0_length, const double *sp, const doub
 int wco_synthesis_pulses(const double *f0, int f0_length, int fft_size, int fs, double frame_period_ms,
                          int out_length, int *reference_capacity);
 
+/* the pulses themselves: sample index and voiced flag of the first `capacity` pulses; returns the count.
+ * Pulse i draws index[i + 1] - index[i] noise samples, the last one none. */
+int wco_synthesis_pulse_list(const double *f0, int f0_length, int fft_size, int fs, double frame_period_ms,
+                             int out_length, int capacity, int *index, int *voiced);
+
 /* draw-count contract ("RNG draw-count contract") */
 uint64_t wco_cheaptrick_draws(int fs, const double *f0, int f0_length, double f0_floor, int fft_size);
 

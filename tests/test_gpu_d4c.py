@@ -156,7 +156,10 @@ def test_d4c_threshold_golden(wca):
 
 def test_d4c_two_wavefront_kernels_against_the_block_kernels_and_frames_they_leave_out(wca, port, monkeypatch):
     """48 kHz default: two wavefronts per frame (d4c2_*).  Against the workgroup-per-frame kernels on the same input, and on a
-    contour with F0 above what their LDS holds (~1.4 kHz), which the block kernel picks up behind them."""
+    contour with F0 written over it at 1300 Hz and 1800 Hz.  Those fourteen frames exercise LoveTrain only: on this speech signal
+    LoveTrain gates every one of them out (the CPU restatement returns the 1 - 1e-12 row for all of them), so d4c2_frame leaves
+    before it reaches d4c2_can and neither the list of left-out frames nor the block kernel behind it runs here.  The hand-over at
+    48 kHz is held by tests/test_gpu_stage_edges.py, on signals whose frames are gated in on both sides of d4c2_can."""
     fs = 48000
     x = make_utterance(fs, 0.5, 99)
     tpos, f0 = port.harvest(x, fs)

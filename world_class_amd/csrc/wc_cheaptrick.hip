@@ -62,6 +62,13 @@ __host__ __device__ __forceinline__ bool ct_wave_can(double f0c, int fs) {
 	const int upper = 2 + (int)(f0c * N / fs);
 	return b <= 60 && upper <= 120;
 }
+// debug symbol (not in the public headers, like wc_debug_wave_fft): does the one-wavefront kernel of this FFT size take a frame of
+// this F0 (after the floor's substitution, reference :76)?  1 / 0; -1: the size has no one-wavefront kernel.  Host only.
+extern "C" int wc_debug_ct_wave_takes(int fft_size, double f0c, int fs) {
+	if (fft_size == 2048) return ct_wave_can<2048>(f0c, fs) ? 1 : 0;
+	if (fft_size == 1024) return ct_wave_can<1024>(f0c, fs) ? 1 : 0;
+	return -1;
+}
 
 template <int N, int T>
 __device__ __forceinline__ void ct_frame_block(const CtArgs &a, long long g, double2 *A, double *scr, double *red) {

@@ -1501,6 +1501,14 @@ __host__ __device__ __forceinline__ bool d4c1_can(double f0, int fs) {
 	const int v = (int)(f0 * 2048 / fs);
 	return v + 1 <= 120 && v + 2 <= 122;
 }
+// debug symbol (not in the public headers, like wc_debug_wave_fft): do the one-wavefront kernels of this transform size (D4C's own,
+// fft_size_d4c: 4096 at 48 kHz, 2048 at 16 - 24 kHz) take a gated frame of this F0 (after the floor at 47 Hz, reference :157)?
+// 1 / 0; -1: the size has no one-wavefront kernels.  Host only.
+extern "C" int wc_debug_d4c_wave_takes(int fft_size, double f0, int fs) {
+	if (fft_size == 4096) return d4c2_can(f0, fs) ? 1 : 0;
+	if (fft_size == 2048) return d4c1_can(f0, fs) ? 1 : 0;
+	return -1;
+}
 struct D4Bins1 {
 	double v[16];
 	double vM;
