@@ -318,5 +318,8 @@ long long wc_morph_stream_frames_formed(const wc_morph_stream *m, int stream);
 /* Settled positions from a lagged backtrack: where the row L frames ago lies on the path behind the newest row, and the flush
  * (wc_align_stream_reserve_lag, _set_lag, _push_settled_device, _tail_device): the header below. */
 #include "world_class_align_lag.h"
+/* Track-morph streams: a live voice morphed with a resident track at positions the kernel reads from device memory, such as the
+ * settled positions above, push by push and with a flush (wc_track_morph_*): the header below. */
+#include "world_class_track_morph.h"
 
 #endif /* WORLD_CLASS_STREAM_H */
