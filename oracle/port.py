@@ -131,6 +131,43 @@ class Port:
         return dict(y=y, raw=raw, cand=cand, score=score, f0_base=base, f0_fixed=fixed, f0_1ms=f1,
                     n_cand=nc)
 
+    def harvest_tail(self, cand, score, fs, x_length, frame_period=5.0, trace=True):
+        """Harvest's tail alone (removal of unreliable candidates, contour fixing, smoothing, resampling) on the refined candidate
+        rows cand / score [1 ms frames of x_length samples][n_cand].  Returns cand, score (after the removal), f0_base, s1, s2,
+        s3, f0_fixed, f0_1ms, tpos, f0 and -- with trace -- `trace`: what the contour logic decided (wc_oracle.h)."""
+        cand, score = _c(cand), _c(score)
+        L, nc = cand.shape
+        assert score.shape == cand.shape
+        n_out = self.get_samples(fs, x_length, frame_period)
+        r = dict(cand=np.zeros((L, nc)), score=np.zeros((L, nc)), tpos=np.zeros(n_out), f0=np.zeros(n_out))
+        for k in ("f0_base", "s1", "s2", "s3", "f0_fixed", "f0_1ms"):
+            r[k] = np.zeros(L)
+        cap = 16 + 6 * L
+        tr = np.zeros(cap, dtype=np.int32)
+        fn = self.lib.wco_harvest_tail
+        fn.restype = C.c_int
+        fn.argtypes = [_dp, _dp, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int] + [_dp] * 10 + [_ip, C.c_int]
+        got = fn(_p(cand), _p(score), L, nc, frame_period, fs, int(x_length), _p(r["cand"]), _p(r["score"]), _p(r["f0_base"]),
+                 _p(r["s1"]), _p(r["s2"]), _p(r["s3"]), _p(r["f0_fixed"]), _p(r["f0_1ms"]), _p(r["tpos"]), _p(r["f0"]),
+                 tr.ctypes.data_as(_ip) if trace else None, cap)
+        if got != n_out:
+            raise ValueError("harvest_tail: bad arguments (%d)" % got)
+        if trace:
+            h = [int(v) for v in tr[:16]]
+            n1, n2, n3 = h[0], h[1], h[2]
+            at = [16]
+
+            def take(n, w):
+                v = tr[at[0]:at[0] + n * w].astype(np.int64).reshape(n, w) if w > 1 else tr[at[0]:at[0] + n].astype(np.int64)
+                at[0] += n * w
+                return v
+            sec1, sec2, ext, sel, sec3 = take(n1, 2), take(n2, 2), take(n2, 4), take(n2, 1), take(n3, 2)
+            r["trace"] = dict(sec1=sec1, sec2=sec2, sec3=sec3, ext_before=ext[:, :2], ext_after=ext[:, 2:], selected=sel.astype(bool),
+                              count=h[3], disjoint=h[4], contained=h[5], s1_gt_s2=h[6], s1_lt_s2=h[7], s1_eq_s2=h[8],
+                              groups2=h[9], groups3=h[10], gaps_filled=h[11], gaps_left=h[12], window_sum=h[13],
+                              smooth_sections=h[14])
+        return r
+
     def cheaptrick_fft_size(self, fs, f0_floor=71.0):
         return self.lib.wco_cheaptrick_fft_size(fs, f0_floor)
 

@@ -789,6 +789,20 @@ struct Harvest {
 	std::vector<vd> raw;         // [band][L]
 	std::vector<vd> cand, score;  // [L][max_cand]
 };
+// what hv_fix_contour / hv_smooth decided, for tests that must prove which path a candidate table takes (wco_harvest_tail);
+// filled only while g_hv_trace points at one
+struct HvTrace {
+	std::vector<int> sec1, sec2, sec3;  // (first, last) of the voiced sections after fixStep1, fixStep2 and fixStep3
+	std::vector<int> ext;               // per section of fixStep2: first, last before and first, last after extendF0
+	std::vector<int> selected;          // per section of fixStep2: kept by extendSub (1) or not (0)
+	int count = 0;
+	int branch[5] = {0, 0, 0, 0, 0};    // mergeF0: disjoint, contained, s1 > s2, s1 < s2, s1 == s2
+	int groups2 = 0, groups3 = 0;       // start frames shared by >= 2 and by >= 3 selected sections
+	int gaps_filled = 0, gaps_left = 0; // fixStep4
+	long long window_sum = 0;           // sum over the sections of fixStep2 of min(L-1, ed+104) - max(0, st-104) + 1
+	int smooth_sections = 0;
+};
+static HvTrace *g_hv_trace = nullptr;
 static int get_samples(int fs, int x_length, double fp) {  // :173-181
 	return static_cast<int>(1000.0 * x_length / fs / fp) + 1;
 }
@@ -1049,19 +1063,25 @@ static double search_score(double f0, const double *c, const double *s, int n) {
 }
 // :475-497
 static int merge_f0_sub(const Harvest &H, double *merged, int st1, int ed1, const double *f2, int st2, int ed2) {
-	if (st1 <= st2 && ed1 >= ed2) return ed1;
+	if (st1 <= st2 && ed1 >= ed2) {
+		if (g_hv_trace) g_hv_trace->branch[1]++;
+		return ed1;
+	}
 	double s1 = 0.0, s2 = 0.0;
 	for (int i = st2; i <= ed1; ++i) {
 		s1 += search_score(merged[i], H.cand[i].data(), H.score[i].data(), H.n_cand);
 		s2 += search_score(f2[i], H.cand[i].data(), H.score[i].data(), H.n_cand);
 	}
+	if (g_hv_trace) g_hv_trace->branch[s1 > s2 ? 2 : s1 < s2 ? 3 : 4]++;
 	if (s1 > s2) std::copy(f2 + ed1, f2 + ed2 + 1, merged + ed1);
 	else std::copy(f2 + st2, f2 + ed2 + 1, merged + st2);
 	return ed2;
 }
 // fixStep1..4 (:277-291, :319-334, :560-585 incl. :427-458 and :502-536, :590-614)
-static void hv_fix_contour(Harvest &H, vd &base_out, vd &best) {
+static void hv_fix_contour(Harvest &H, vd &base_out, vd &best, vd *steps = nullptr) {  // steps: s1, s2, s3 on request
 	int L = H.L;
+	HvTrace *const tr = g_hv_trace;
+	auto pairs = [](const std::vector<int> &b, int n_pairs) { return std::vector<int>(b.begin(), b.begin() + 2 * n_pairs); };
 	vd base(L, 0.0), s1(L, 0.0), s2, s3, s4;
 	for (int i = 0; i < L; ++i) {  // searchF0Base :254-272
 		double bs = 0.0;
@@ -1081,6 +1101,7 @@ static void hv_fix_contour(Harvest &H, vd &base_out, vd &best) {
 	s2 = s1;
 	std::vector<int> bl;
 	int nb = boundary_list(s1.data(), L, bl);
+	if (tr) tr->sec1 = pairs(bl, nb / 2);
 	for (int i = 0; i < nb / 2; ++i) {
 		if (bl[i * 2 + 1] - bl[i * 2] >= 6) continue;
 		for (int j = bl[i * 2]; j <= bl[i * 2 + 1]; ++j) s2[j] = 0.0;
@@ -1095,10 +1116,17 @@ static void hv_fix_contour(Harvest &H, vd &base_out, vd &best) {
 		chan[i] = i;
 		for (int j = bl[i * 2]; j <= bl[i * 2 + 1]; ++j) mc[i][j] = s2[j];
 	}
+	if (tr) {
+		tr->sec2 = pairs(bl, ns);
+		tr->selected.assign(ns, 0);
+		for (int i = 0; i < ns; ++i) tr->window_sum += std::min(L - 1, bl[i * 2 + 1] + 104) - std::max(0, bl[i * 2] - 104) + 1;
+	}
 	// extend (:427-458)
 	for (int i = 0; i < ns; ++i) {
+		if (tr) { tr->ext.push_back(bl[i * 2]); tr->ext.push_back(bl[i * 2 + 1]); }
 		bl[i * 2 + 1] = extend_f0(H, mc[i].data(), bl[i * 2 + 1], std::min(L - 2, bl[i * 2 + 1] + 100), 1, 0.18);
 		bl[i * 2] = extend_f0(H, mc[i].data(), bl[i * 2], std::max(1, bl[i * 2] - 100), -1, 0.18);
+		if (tr) { tr->ext.push_back(bl[i * 2]); tr->ext.push_back(bl[i * 2 + 1]); }
 	}
 	int count = 0;
 	double mean_f0 = 0.0;  // not reset between sections (:446-452) -- kept
@@ -1107,6 +1135,7 @@ static void hv_fix_contour(Harvest &H, vd &base_out, vd &best) {
 		for (int j = st; j < ed; ++j) mean_f0 += mc[chan[i]][j];
 		mean_f0 /= ed - st;
 		if (2200.0 / mean_f0 < ed - st) {
+			if (tr) tr->selected[i] = 1;  // (section i is still at position i: the swaps touch positions <= i only)
 			std::swap(chan[count], chan[i]);
 			std::swap(bl[count * 2], bl[i * 2]);
 			std::swap(bl[count * 2 + 1], bl[i * 2 + 1]);
@@ -1115,6 +1144,17 @@ static void hv_fix_contour(Harvest &H, vd &base_out, vd &best) {
 	}
 	// merge (:502-536)
 	// (with zero selected channels the reference still copies the row at position 0)
+	if (tr) {
+		tr->count = count;
+		std::vector<int> starts;
+		for (int i = 0; i < count; ++i) starts.push_back(bl[i * 2]);
+		std::sort(starts.begin(), starts.end());
+		for (size_t i = 0, j; i < starts.size(); i = j) {
+			for (j = i; j < starts.size() && starts[j] == starts[i]; ++j) {}
+			if (j - i >= 2) tr->groups2++;
+			if (j - i >= 3) tr->groups3++;
+		}
+	}
 	if (ns > 0) {
 		std::vector<int> order(count);
 		for (int i = 0; i < count; ++i) order[i] = i;
@@ -1124,6 +1164,7 @@ static void hv_fix_contour(Harvest &H, vd &base_out, vd &best) {
 			int i1 = bl[order[i] * 2], i2 = bl[order[i] * 2 + 1];
 			const vd &src = mc[chan[order[i]]];
 			if (i1 - bl[1] > 0) {
+				if (tr) tr->branch[0]++;
 				std::copy(src.begin() + i1, src.begin() + i2 + 1, s3.begin() + i1);
 				bl[0] = i1;
 				bl[1] = i2;
@@ -1135,8 +1176,11 @@ static void hv_fix_contour(Harvest &H, vd &base_out, vd &best) {
 	// step 4
 	s4 = s3;
 	nb = boundary_list(s3.data(), L, bl);
+	if (tr) tr->sec3 = pairs(bl, nb / 2);
+	if (steps) { steps[0] = s1; steps[1] = s2; steps[2] = s3; }
 	for (int i = 0; i < nb / 2 - 1; ++i) {
 		int distance = bl[(i + 1) * 2] - bl[i * 2 + 1] - 1;
+		if (tr) (distance >= 9 ? tr->gaps_left : tr->gaps_filled)++;
 		if (distance >= 9) continue;
 		double t0 = s3[bl[i * 2 + 1]] + 1;
 		double t1 = s3[bl[(i + 1) * 2]] - 1;
@@ -1155,6 +1199,7 @@ static void hv_smooth(const Harvest &H, const vd &f0, double *smoothed) {
 	std::copy(f0.begin(), f0.end(), contour.begin() + lag);
 	std::vector<int> bl;
 	int nb = boundary_list(contour.data(), n, bl);
+	if (g_hv_trace) g_hv_trace->smooth_sections = nb / 2;
 	std::vector<vd> mc(nb / 2, vd(n, 0.0));
 	for (int i = 0; i < nb / 2; ++i)
 		for (int j = bl[i * 2]; j <= bl[i * 2 + 1]; ++j) mc[i][j] = contour[j];
@@ -1214,21 +1259,25 @@ static void hv_general_body(Harvest &H, const double *x, int x_length, int fs, d
 	f0_1ms.assign(H.L, 0.0);
 	hv_smooth(H, f0_fixed, f0_1ms.data());
 }
-// :183-208
-static void harvest(const double *x, int x_length, int fs, double floor_, double ceil_, double fp,
-					double *tpos, double *f0) {
-	Harvest H;
-	vd base, fixed, f1;
-	hv_general_body(H, x, x_length, fs, floor_, ceil_, base, fixed, f1);
+// :183-208, from the 1 ms contour to the caller's frame period
+static void hv_resample(const vd &tpos_1ms, const vd &f1, int fs, int x_length, double fp, double *tpos, double *f0) {
+	const int L1 = static_cast<int>(f1.size());
 	if (fp == 1.0) {
-		for (int i = 0; i < H.L; ++i) { tpos[i] = H.tpos[i]; f0[i] = f1[i]; }
+		for (int i = 0; i < L1; ++i) { tpos[i] = tpos_1ms[i]; f0[i] = f1[i]; }
 		return;
 	}
 	int L = get_samples(fs, x_length, fp);
 	for (int i = 0; i < L; ++i) {
 		tpos[i] = i * fp / 1000.0;
-		f0[i] = f1[std::min(H.L - 1, mround(tpos[i] * 1000.0))];
+		f0[i] = f1[std::min(L1 - 1, mround(tpos[i] * 1000.0))];
 	}
+}
+static void harvest(const double *x, int x_length, int fs, double floor_, double ceil_, double fp,
+					double *tpos, double *f0) {
+	Harvest H;
+	vd base, fixed, f1;
+	hv_general_body(H, x, x_length, fs, floor_, ceil_, base, fixed, f1);
+	hv_resample(H.tpos, f1, fs, x_length, fp, tpos, f0);
 }
 
 }  // namespace
@@ -1347,5 +1396,50 @@ int wco_harvest_debug(const double *x, int x_length, int fs, double f0_floor, do
 	if (f0_fixed) std::copy(fixed.begin(), fixed.end(), f0_fixed);
 	if (f0_1ms) std::copy(f1.begin(), f1.end(), f0_1ms);
 	return H.L;
+}
+int wco_harvest_tail(const double *cand, const double *score, int L, int n_cand, double frame_period, int fs, int x_length,
+					 double *cand_out, double *score_out, double *f0_base, double *s1, double *s2, double *s3, double *f0_fixed,
+					 double *f0_1ms, double *tpos, double *f0, int *trace, int trace_capacity) {
+	if (!cand || !score || L < 3 || n_cand < 1 || L != get_samples(fs, x_length, 1)) return -1;
+	Harvest H;
+	H.fs = fs;
+	H.L = L;
+	H.n_cand = H.max_cand = n_cand;
+	H.cand.assign(L, vd(n_cand));
+	H.score.assign(L, vd(n_cand));
+	for (int i = 0; i < L; ++i) {
+		std::copy(cand + static_cast<size_t>(i) * n_cand, cand + static_cast<size_t>(i + 1) * n_cand, H.cand[i].begin());
+		std::copy(score + static_cast<size_t>(i) * n_cand, score + static_cast<size_t>(i + 1) * n_cand, H.score[i].begin());
+	}
+	H.tpos.resize(L);
+	for (int i = 0; i < L; ++i) H.tpos[i] = i * 1 / 1000.0;
+	HvTrace T;
+	vd base, fixed, f1(L, 0.0), steps[3];
+	hv_remove_unreliable(H);
+	g_hv_trace = trace ? &T : nullptr;
+	hv_fix_contour(H, base, fixed, steps);
+	hv_smooth(H, fixed, f1.data());
+	g_hv_trace = nullptr;
+	if (cand_out) for (int i = 0; i < L; ++i) std::copy(H.cand[i].begin(), H.cand[i].end(), cand_out + static_cast<size_t>(i) * n_cand);
+	if (score_out) for (int i = 0; i < L; ++i) std::copy(H.score[i].begin(), H.score[i].end(), score_out + static_cast<size_t>(i) * n_cand);
+	if (f0_base) std::copy(base.begin(), base.end(), f0_base);
+	if (s1) std::copy(steps[0].begin(), steps[0].end(), s1);
+	if (s2) std::copy(steps[1].begin(), steps[1].end(), s2);
+	if (s3) std::copy(steps[2].begin(), steps[2].end(), s3);
+	if (f0_fixed) std::copy(fixed.begin(), fixed.end(), f0_fixed);
+	if (f0_1ms) std::copy(f1.begin(), f1.end(), f0_1ms);
+	if (tpos && f0) hv_resample(H.tpos, f1, fs, x_length, frame_period, tpos, f0);
+	if (trace) {
+		std::vector<int> t(WCO_HV_TRACE_HEADER, 0);
+		t[0] = static_cast<int>(T.sec1.size() / 2); t[1] = static_cast<int>(T.sec2.size() / 2); t[2] = static_cast<int>(T.sec3.size() / 2);
+		t[3] = T.count;
+		for (int k = 0; k < 5; ++k) t[4 + k] = T.branch[k];
+		t[9] = T.groups2; t[10] = T.groups3; t[11] = T.gaps_filled; t[12] = T.gaps_left;
+		t[13] = static_cast<int>(T.window_sum); t[14] = T.smooth_sections;
+		for (const std::vector<int> *v : {&T.sec1, &T.sec2, &T.ext, &T.selected, &T.sec3}) t.insert(t.end(), v->begin(), v->end());
+		if (static_cast<int>(t.size()) > trace_capacity) return -2;
+		std::copy(t.begin(), t.end(), trace);
+	}
+	return get_samples(fs, x_length, frame_period);
 }
 }  // extern "C"

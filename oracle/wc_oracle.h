@@ -74,6 +74,22 @@ uint64_t wco_cheaptrick_draws(int fs, const double *f0, int f0_length, double f0
 int wco_harvest_debug(const double *x, int x_length, int fs, double f0_floor, double f0_ceil,
                       int *dims, double *y, double *raw, double *cand, double *score,
                       double *f0_base, double *f0_fixed, double *f0_1ms);
+
+/* Harvest's tail alone on candidate rows given by the caller: removeUnreliableCandidates, fixF0Contour, smoothF0Contour
+ * and the resampling to frame_period, on cand / score [L][n_cand] refined candidates (0 = empty) with L = the 1 ms frame
+ * count of x_length samples at fs.  Out (any may be NULL): cand_out / score_out [L][n_cand] after the removal; f0_base,
+ * s1, s2, s3 (after fixStep1..3), f0_fixed, f0_1ms [L]; tpos / f0 at frame_period.  Returns their frame count, < 0 on
+ * bad arguments (-2: trace_capacity too small; 16 + 6 L always suffices).
+ * trace (optional) -- WCO_HV_TRACE_HEADER ints: [0..2] sections after fixStep1, fixStep2, fixStep3 (n1, n2, n3), [3] sections
+ * kept by extendSub (count), [4..8] mergeF0 branches taken: disjoint, contained, s1 > s2, s1 < s2, s1 == s2, [9] / [10] start
+ * frames shared by >= 2 / >= 3 kept sections, [11] / [12] gaps filled / left by fixStep4, [13] sum over the sections of
+ * fixStep2 of min(L-1, ed+104) - max(0, st-104) + 1, [14] sections seen by the smoothing, [15] 0; then the lists: n1 (first,
+ * last) pairs after fixStep1, n2 pairs after fixStep2, n2 x (first, last before extendF0, first, last after), n2 flags (kept by
+ * extendSub), n3 pairs after fixStep3. */
+#define WCO_HV_TRACE_HEADER 16
+int wco_harvest_tail(const double *cand, const double *score, int L, int n_cand, double frame_period, int fs, int x_length,
+                     double *cand_out, double *score_out, double *f0_base, double *s1, double *s2, double *s3,
+                     double *f0_fixed, double *f0_1ms, double *tpos, double *f0, int *trace, int trace_capacity);
 #ifdef __cplusplus
 }
 #endif

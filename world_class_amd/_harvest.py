@@ -13,6 +13,7 @@ class Harvest:
     def __init__(self, fs, f0_floor=71.0, f0_ceil=800.0, frame_period=5.0, target_fs=8000.0,
                  channels_in_octave=40.0, use_cos_table=False):
         self.fs, self.frame_period = fs, frame_period
+        self._last_lengths = []  # sample counts of the most recent call's utterances (debug_tail)
         self._h = _handle(lib().wc_harvest_create(fs, f0_floor, f0_ceil, frame_period, target_fs,
                                                   channels_in_octave, int(use_cos_table)))
 
@@ -24,11 +25,13 @@ class Harvest:
         n = self.get_samples(len(x))
         tpos, f0 = np.zeros(n), np.zeros(n)
         _check(lib().wc_harvest_compute(self._h, _p(x), len(x), _p(tpos), _p(f0)))
+        self._last_lengths = [len(x)]
         return tpos, f0
 
     def compute_device(self, d_x, x_lengths, d_tpos, d_f0):
         _check(lib().wc_harvest_compute_device(self._h, len(x_lengths), _ptr(d_x), _ints(x_lengths), _ptr(d_tpos),
                                                _ptr(d_f0)))
+        self._last_lengths = [int(n) for n in x_lengths]
 
     def compute_batch(self, xs):
         """host list in, list of (temporal positions, F0) out: wc_harvest_compute_batch (one trip over PCIe each way, one batch)"""
@@ -36,6 +39,7 @@ class Harvest:
         fl = [self.get_samples(len(x)) for x in xs]
         ts, fs_ = [np.zeros(n) for n in fl], [np.zeros(n) for n in fl]
         _check(lib().wc_harvest_compute_batch(self._h, len(xs), _ptr_array(xs), _ints([len(x) for x in xs]), _ptr_array(ts), _ptr_array(fs_)))
+        self._last_lengths = [len(x) for x in xs]
         return list(zip(ts, fs_))
 
     def debug_fetch(self, name, utt=0):
@@ -63,6 +67,26 @@ class Harvest:
         s1 = np.zeros((frames, 7 * S))
         _check(fn(self._h, cand0.ctypes.data, int(by_slots), c1.ctypes.data, s1.ctypes.data))  # 0 default (frames in groups), 1 slots, 2 packed
         return c1, s1
+
+    def debug_tail(self, cand, score):
+        """Development hook: Harvest's tail alone -- unreliable-candidate test, contour logic, smoothing, output -- on the refined
+        candidate rows cand / score ([1 ms frames of the most recent call, utterance after utterance][7 S], 0 = empty slot).
+        Returns [(temporal positions, F0)] per utterance of that call; debug_fetch then reads the tail's intermediates."""
+        fn = lib().wc_harvest_debug_tail
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p] * 5
+        cand = np.ascontiguousarray(cand, dtype=np.float64)
+        score = np.ascontiguousarray(score, dtype=np.float64)
+        frames = sum(get_samples(self.fs, n, 1.0) for n in self._last_lengths)
+        if not self._last_lengths or cand.ndim != 2 or cand.shape != score.shape or cand.shape[0] != frames:
+            raise ValueError("debug_tail: rows must be [%d frames of the most recent call][7 S]" % frames)
+        if len(self.debug_fetch("cand1", 0)) != get_samples(self.fs, self._last_lengths[0], 1.0) * cand.shape[1]:
+            raise ValueError("debug_tail: rows are not 7 S wide")
+        fl = [self.get_samples(n) for n in self._last_lengths]
+        tpos, f0 = np.zeros(sum(fl)), np.zeros(sum(fl))
+        _check(fn(self._h, cand.ctypes.data, score.ctypes.data, tpos.ctypes.data, f0.ctypes.data))
+        at = np.concatenate([[0], np.cumsum(fl)])
+        return [(tpos[a:b].copy(), f0[a:b].copy()) for a, b in zip(at[:-1], at[1:])]
 
     def __del__(self):
         try:

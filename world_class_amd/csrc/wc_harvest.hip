@@ -3951,6 +3951,10 @@ struct wc_harvest {
 	std::vector<HvUtt> last_utts;
 	RefArgs last_refine;       // arguments of the most recent refinement launch (wc_harvest_debug_refine)
 	bool last_refine_valid = false;
+	struct Tail {  // sizes and reservations of the most recent call's tail (hv_launch_tail; wc_harvest_debug_tail repeats it)
+		int n_utt = 0, max_L1 = 0, max_L = 0, max_sec = 0, nc = 0;
+		long long chan_stride = 0, smooth_stride = 0, total_l1 = 0, total_out = 0;
+	} last_tail;
 };
 
 static DecCoef dec_coef(int r) {
@@ -4035,6 +4039,39 @@ static void launch_refine(const RefArgs &fa, hipStream_t s, int mode, bool table
 			else hipLaunchKernelGGL((hv_refine_packed_kernel<false, 7 * MAX_SLOTS>), dim3(frames), dim3(64), 0, s, fa);
 		}
 	}
+}
+
+// The tail's launches: the unreliable-candidate test on cand1 / score1, the contour logic, the smoothing and the output, for
+// hv_enqueue and wc_harvest_debug_tail alike.  between(k) runs behind the k-th launch (k = 1, 2, 3: hv_enqueue records its
+// hand-over event there) and ends the sequence when it returns non-zero.
+template <class Between>
+static int hv_launch_tail(wc_harvest *h, hipStream_t s, const wc_harvest::Tail &t, double *d_tpos, double *d_f0, Between &&between) {
+	const HvUtt *du = h->utts.as<HvUtt>();
+	const int n_utt = t.n_utt, nc = t.nc, max_sec = t.max_sec;
+	int rc;
+	const size_t unr_lds = sizeof(double) * (size_t)(3 * UNR_F + 2) * nc + sizeof(int) * (2 * UNR_F + 2) + (size_t)UNR_F * nc;
+	hipLaunchKernelGGL(hv_unreliable_kernel, dim3((unsigned)((t.max_L1 + UNR_F - 1) / UNR_F), n_utt), dim3(256), unr_lds, s, du, h->cand1.as<double>(),
+					   h->score1.as<double>(), h->cand2.as<double>(), h->score2.as<double>(), h->base.as<double>(), nc);
+	if ((rc = between(1))) return rc;
+	CtrArgs ca;
+	ca.utts = du; ca.cand = h->cand2.as<double>(); ca.score = h->score2.as<double>(); ca.base = h->base.as<double>();
+	ca.s1 = h->s1.as<double>(); ca.s2 = h->s2.as<double>(); ca.s3 = h->s3.as<double>(); ca.fixed = h->fixed.as<double>();
+	ca.sec = h->sec.as<int>(); ca.chan = h->chan.as<double>(); ca.chan_stride = t.chan_stride; ca.max_sec = max_sec; ca.nc = nc;
+	ca.ibuf = h->ibuf.as<int>();
+	ca.nsec = h->ibuf.as<int>() + 4ll * max_sec * n_utt;
+	hipLaunchKernelGGL(hv_contour_kernel<0>, dim3(n_utt), dim3(64), 0, s, ca);
+	if ((rc = between(2))) return rc;
+	hipLaunchKernelGGL(hv_contour_kernel<1>, dim3(96, n_utt), dim3(64), 0, s, ca);  // a 10 s utterance has 20-40 sections
+	if ((rc = between(3))) return rc;
+	hipLaunchKernelGGL(hv_contour_kernel<2>, dim3(n_utt), dim3(64), 0, s, ca);
+	SmArgs sa;
+	sa.utts = du; sa.fixed = h->fixed.as<double>(); sa.f0_1ms = h->f0_1ms.as<double>(); sa.sec = h->sec.as<int>();
+	sa.scratch = h->smooth.as<double>(); sa.scratch_stride = t.smooth_stride; sa.max_sec = max_sec;
+	sa.full_walk = h->smooth_full_walk ? 1 : 0;
+	hipLaunchKernelGGL(hv_smooth_kernel, dim3(n_utt), dim3(64), 0, s, sa);
+	hipLaunchKernelGGL(hv_output_kernel, dim3((t.max_L + 255) / 256, n_utt), dim3(256), 0, s, du, h->f0_1ms.as<double>(), d_tpos, d_f0, h->frame_period);
+	WC_HIP(hipGetLastError());
+	return WC_OK;
 }
 
 // part: 3 = the whole chain; 1 = the front only (decimation .. refinement); 2 = the tail of a chain whose front an earlier call
@@ -4319,34 +4356,21 @@ int hv_enqueue(wc_harvest *h, hipStream_t s, int n_utt, const double *d_x, const
 	// kernels, one wavefront per utterance or section) exposes their latency: 27.9 / 28.1 ms.  WC_HARVEST_MID_LATE=0..3 (A/B).
 	static const int mid_late = getenv("WC_HARVEST_MID_LATE") ? atoi(getenv("WC_HARVEST_MID_LATE")) : 1;
 	if (mid_event && !resume_tail && !(mid_late && (phases & 2))) WC_HIP(hipEventRecord(mid_event, s));
+	{
+		wc_harvest::Tail &t = h->last_tail;
+		t.n_utt = n_utt; t.max_L1 = max_L1; t.max_L = max_L; t.max_sec = max_sec; t.nc = nc;
+		t.chan_stride = chan_stride; t.smooth_stride = smooth_stride; t.total_l1 = total_l1; t.total_out = oo;
+	}
 	if (!(phases & 2)) {
 		h->last_utts = utts;
 		return WC_OK;
 	}
 	if (tail_after) WC_HIP(hipStreamWaitEvent(s, tail_after, 0));
 	if ((rc = dev->time_begin("harvest_contour", s))) return rc;  // the per-utterance tail: unreliable-candidate test, contour logic, smoothing
-	const size_t unr_lds = sizeof(double) * (size_t)(3 * UNR_F + 2) * nc + sizeof(int) * (2 * UNR_F + 2) + (size_t)UNR_F * nc;
-	hipLaunchKernelGGL(hv_unreliable_kernel, dim3((unsigned)((max_L1 + UNR_F - 1) / UNR_F), n_utt), dim3(256), unr_lds, s, du, h->cand1.as<double>(),
-					   h->score1.as<double>(), h->cand2.as<double>(), h->score2.as<double>(), h->base.as<double>(), nc);
-	if (mid_event && !resume_tail && mid_late == 1) WC_HIP(hipEventRecord(mid_event, s));
-	CtrArgs ca;
-	ca.utts = du; ca.cand = h->cand2.as<double>(); ca.score = h->score2.as<double>(); ca.base = h->base.as<double>();
-	ca.s1 = h->s1.as<double>(); ca.s2 = h->s2.as<double>(); ca.s3 = h->s3.as<double>(); ca.fixed = h->fixed.as<double>();
-	ca.sec = h->sec.as<int>(); ca.chan = h->chan.as<double>(); ca.chan_stride = chan_stride; ca.max_sec = max_sec; ca.nc = nc;
-	ca.ibuf = h->ibuf.as<int>();
-	ca.nsec = h->ibuf.as<int>() + 4ll * max_sec * n_utt;
-	hipLaunchKernelGGL(hv_contour_kernel<0>, dim3(n_utt), dim3(64), 0, s, ca);
-	if (mid_event && !resume_tail && mid_late == 2) WC_HIP(hipEventRecord(mid_event, s));
-	hipLaunchKernelGGL(hv_contour_kernel<1>, dim3(96, n_utt), dim3(64), 0, s, ca);  // a 10 s utterance has 20-40 sections
-	if (mid_event && !resume_tail && mid_late == 3) WC_HIP(hipEventRecord(mid_event, s));
-	hipLaunchKernelGGL(hv_contour_kernel<2>, dim3(n_utt), dim3(64), 0, s, ca);
-	SmArgs sa;
-	sa.utts = du; sa.fixed = h->fixed.as<double>(); sa.f0_1ms = h->f0_1ms.as<double>(); sa.sec = h->sec.as<int>();
-	sa.scratch = h->smooth.as<double>(); sa.scratch_stride = smooth_stride; sa.max_sec = max_sec;
-	sa.full_walk = h->smooth_full_walk ? 1 : 0;
-	hipLaunchKernelGGL(hv_smooth_kernel, dim3(n_utt), dim3(64), 0, s, sa);
-	hipLaunchKernelGGL(hv_output_kernel, dim3((max_L + 255) / 256, n_utt), dim3(256), 0, s, du, h->f0_1ms.as<double>(), d_tpos, d_f0, h->frame_period);
-	WC_HIP(hipGetLastError());
+	if ((rc = hv_launch_tail(h, s, h->last_tail, d_tpos, d_f0, [&](int k) -> int {
+			if (mid_event && !resume_tail && mid_late == k) WC_HIP(hipEventRecord(mid_event, s));
+			return WC_OK;
+		}))) return rc;
 	if ((rc = dev->time_end("harvest_contour", s))) return rc;
 	h->last_utts = utts;
 	return WC_OK;
@@ -4737,6 +4761,32 @@ int wc_harvest_debug_refine(wc_harvest *h, const double *cand0, int by_slots, do
 	WC_HIP(hipGetLastError());
 	WC_HIP(hipMemcpyAsync(cand1, fa.cand1, sizeof(double) * n_out, hipMemcpyDeviceToHost, s));
 	WC_HIP(hipMemcpyAsync(score1, fa.score1, sizeof(double) * n_out, hipMemcpyDeviceToHost, s));
+	WC_HIP(hipStreamSynchronize(s));
+	return WC_OK;
+}
+
+
+// Development hook: the tail alone -- unreliable-candidate test, contour logic, smoothing, output -- on refined candidate rows
+// given by the caller, over the utterances of the most recent call (lengths and reservations are that call's).  cand1 / score1:
+// [1 ms frames of the batch][7 S]; tpos / f0: the contours at the handle's frame period, packed by utterance.  The intermediates
+// are then wc_harvest_debug_fetch's (cand, score, base, s1, s2, s3, fixed, f0_1ms).  Lets the tests write ties, thresholds met
+// exactly and more voiced sections than audio ever has.
+int wc_harvest_debug_tail(wc_harvest *h, const double *cand1, const double *score1, double *tpos, double *f0) {
+	if (!h || !cand1 || !score1 || !tpos || !f0 || h->last_utts.empty() || h->last_tail.n_utt != (int)h->last_utts.size())
+		return fail(WC_ERR_INVALID, "harvest debug: no call whose tail could be repeated");
+	WC_HIP(hipSetDevice(h->dev->id));
+	DeviceLock lock(h->dev);
+	hipStream_t s = h->dev->active();
+	const wc_harvest::Tail &t = h->last_tail;
+	const size_t n_rows = (size_t)t.total_l1 * t.nc, n_out = (size_t)t.total_out;
+	int rc;
+	if ((rc = h->d_tpos.reserve(sizeof(double) * n_out))) return rc;
+	if ((rc = h->d_f0.reserve(sizeof(double) * n_out))) return rc;
+	WC_HIP(hipMemcpyAsync(h->cand1.p, cand1, sizeof(double) * n_rows, hipMemcpyHostToDevice, s));
+	WC_HIP(hipMemcpyAsync(h->score1.p, score1, sizeof(double) * n_rows, hipMemcpyHostToDevice, s));
+	if ((rc = hv_launch_tail(h, s, t, h->d_tpos.as<double>(), h->d_f0.as<double>(), [](int) { return WC_OK; }))) return rc;
+	WC_HIP(hipMemcpyAsync(tpos, h->d_tpos.p, sizeof(double) * n_out, hipMemcpyDeviceToHost, s));
+	WC_HIP(hipMemcpyAsync(f0, h->d_f0.p, sizeof(double) * n_out, hipMemcpyDeviceToHost, s));
 	WC_HIP(hipStreamSynchronize(s));
 	return WC_OK;
 }
