@@ -7,13 +7,12 @@
 //     sums).  ap = (1 - w) * apA + w * apB; sp = exp((1 - w) * la + w * lb) on the two log envelopes; F0 = exp of the same blend of
 //     the two log F0 where both frames are voiced, the nearer source's F0 (or 0) where one is, 0 where neither is.  w == 0 and
 //     w == 1 write the one source's retimed frame bit for bit (the paths of retime_kernel).  A gather bound by memory traffic or by
-//     its two log and one exp per bin: up to eight rows in, two out, two bins per lane and access.  The blend's own expressions
-//     (mp_f0, mp_log) are stated in wc_morph_rows.hpp, shared with morph_stream_kernel (wc_morph_stream.hip).
-//     STRETCH = false: no LDS, the blend straight from registers.
-//     STRETCH: each source's interpolated row goes to LDS as its logarithm (two rows of kMaxBins doubles, 32 KB at fft 4096: four
-//     workgroups per CU of 160 KB); la(b) / lb(b) are wc::stretched_log_bin (wc_stretch.hpp: the value whose exp stretch_kernel and
-//     retime_kernel<true> write) of the row by that source's ratio for this frame, the bins from cut upward the value of bin
-//     cut - 1, a ratio of 0 the row's own logarithm; an invalid ratio of either source makes the sp row NaN.
+//     its two log and one exp per bin: up to eight rows in, two out, two bins per lane and access.  The blend itself (mp_f0,
+//     mp_ap_row, mp_sp_row<STRETCH>) is stated in wc_morph_rows.hpp, shared with the stream kernels (wc_morph_stream.hip,
+//     wc_track_morph.hip, wc_track_morph_coded.hip); this kernel's own are the bisection, the outputs that may be absent, and the
+//     frame that is NaN: a position or weight that is not finite, or (the sp row only) an invalid ratio of either source.
+//     STRETCH = false: no LDS.  STRETCH: two LDS rows of kMaxBins doubles hold the sources' log envelopes, stretched by that source's
+//     ratio for this frame (wc::stretched_log_bin, wc_stretch.hpp), a ratio of 0 the row's own logarithm.
 //   A workgroup finds its pair by bisection in the descriptors, which go up through page-locked staging kept per (device, stream):
 //   a call only enqueues.
 #include <hip/hip_runtime.h>
@@ -59,7 +58,6 @@ __global__ __launch_bounds__(RT_T) void morph_kernel(MpArgs A) {
 	const RtPlace qa = rt_place(A.pos_a[g], u.na), qb = rt_place(A.pos_b[g], u.nb);
 	const double w = A.w[g];
 	const bool finite = qa.finite && qb.finite && mp_finite(w);
-	const double w0 = 1.0 - w;
 	const long long ia = u.a_off + qa.i, ja = u.a_off + qa.j, ib = u.b_off + qb.i, jb = u.b_off + qb.j;
 
 	if (A.f0_out && tid == 0) {
@@ -70,60 +68,19 @@ __global__ __launch_bounds__(RT_T) void morph_kernel(MpArgs A) {
 	}
 	if (A.ap_out) {
 		double *__restrict__ out = A.ap_out + g * bins;
-		const double *__restrict__ ai = A.ap_a + ia * bins, *__restrict__ aj = A.ap_a + ja * bins;
-		const double *__restrict__ bi = A.ap_b + ib * bins, *__restrict__ bj = A.ap_b + jb * bins;
+		const MpRow pa{A.ap_a + ia * bins, A.ap_a + ja * bins, qa.w0, qa.a}, pb{A.ap_b + ib * bins, A.ap_b + jb * bins, qb.w0, qb.a};
 		if (!finite) rt_nan_row(out, bins, tid);
-		else if (w == 0.0) rt_row(ai, aj, qa.w0, qa.a, out, bins, tid);
-		else if (w == 1.0) rt_row(bi, bj, qb.w0, qb.a, out, bins, tid);
-		else {
-			for (int t = tid; t < bins / 2; t += RT_T) {
-				const d2u x = rt_pair(ai, aj, qa.w0, qa.a, 2 * t), y = rt_pair(bi, bj, qb.w0, qb.a, 2 * t);
-				*reinterpret_cast<d2u *>(out + 2 * t) = w0 * x + w * y;
-			}
-			if (tid == 0) out[bins - 1] = w0 * rt_one(ai, aj, qa.w0, qa.a, bins - 1) + w * rt_one(bi, bj, qb.w0, qb.a, bins - 1);
-		}
+		else mp_ap_row(pa, pb, w, out, bins, tid);
 	}
 	if (!A.sp_out) return;
 	double *__restrict__ out = A.sp_out + g * bins;
-	const double *__restrict__ ai = A.sp_a + ia * bins, *__restrict__ aj = A.sp_a + ja * bins;
-	const double *__restrict__ bi = A.sp_b + ib * bins, *__restrict__ bj = A.sp_b + jb * bins;
 	const double ra = STRETCH && A.ratio_a ? A.ratio_a[g] : 0.0, rb = STRETCH && A.ratio_b ? A.ratio_b[g] : 0.0;
 	if (!finite || (STRETCH && ((ra != 0.0 && !frame_ratio_valid(ra, A.fft_size)) || (rb != 0.0 && !frame_ratio_valid(rb, A.fft_size))))) {
 		rt_nan_row(out, bins, tid);
 		return;
 	}
-	if constexpr (STRETCH) {
-		__shared__ double lga[kMaxBins], lgb[kMaxBins];
-		__shared__ double fill;
-		if (w == 0.0 || w == 1.0) {  // the one source's row as retime_kernel<true> writes it
-			const bool first = w == 0.0;
-			const double r = first ? ra : rb;
-			const RtPlace &q = first ? qa : qb;
-			const double *__restrict__ ri = first ? ai : bi, *__restrict__ rj = first ? aj : bj;
-			if (r == 0.0) rt_row(ri, rj, q.w0, q.a, out, bins, tid);
-			else rt_stretched_row(ri, rj, q.w0, q.a, out, r, A.fs, A.fft_size, tid, lga, &fill);
-			return;
-		}
-		rt_log_row(ai, aj, qa.w0, qa.a, lga, bins, tid);
-		rt_log_row(bi, bj, qb.w0, qb.a, lgb, bins, tid);
-		__syncthreads();
-		const MpLog la = mp_log(lga, ra, A.fs, A.fft_size), lb = mp_log(lgb, rb, A.fs, A.fft_size);
-		for (int b = tid; b < bins; b += RT_T) out[b] = exp(w0 * la.at(b) + w * lb.at(b));
-	} else {
-		if (w == 0.0) rt_row(ai, aj, qa.w0, qa.a, out, bins, tid);
-		else if (w == 1.0) rt_row(bi, bj, qb.w0, qb.a, out, bins, tid);
-		else {
-			for (int t = tid; t < bins / 2; t += RT_T) {
-				const d2u x = rt_pair(ai, aj, qa.w0, qa.a, 2 * t), y = rt_pair(bi, bj, qb.w0, qb.a, 2 * t);
-				d2u v;
-				v.x = exp(w0 * log(x.x) + w * log(y.x));
-				v.y = exp(w0 * log(x.y) + w * log(y.y));
-				*reinterpret_cast<d2u *>(out + 2 * t) = v;
-			}
-			if (tid == 0)
-				out[bins - 1] = exp(w0 * log(rt_one(ai, aj, qa.w0, qa.a, bins - 1)) + w * log(rt_one(bi, bj, qb.w0, qb.a, bins - 1)));
-		}
-	}
+	const MpRow sa{A.sp_a + ia * bins, A.sp_a + ja * bins, qa.w0, qa.a}, sb{A.sp_b + ib * bins, A.sp_b + jb * bins, qb.w0, qb.a};
+	mp_sp_row<STRETCH>(sa, sb, w, ra, rb, out, A.fs, A.fft_size, tid);
 }
 
 // descriptor staging per (device, stream), as for retime: calls on one stream are ordered behind each other, calls on different

@@ -3,7 +3,7 @@
 // takes.  The streaming form of wc_morph_parameters_device (wc_morph.hip), as retime_stream_kernel is that of retime_kernel.
 //
 //   morph_stream_kernel<STRETCH>   one workgroup of RT_T lanes per formed frame; the frame is morph_kernel's at the same two
-//     positions, weights and ratios (the expressions of wc_retime_rows.hpp and wc_morph_rows.hpp), so it has that kernel's bits.  A
+//     positions, weights and ratios: the same mp_f0 / mp_ap_row / mp_sp_row of wc_morph_rows.hpp on the same retimed rows.  A
 //     source row of a voice is a row of this push's packed arrays or, where its index lies below the push's first frame, a row of the
 //     stream's backlog: retime_stream_kernel's ki < 0 addressing with a backlog in the place of one carried row.  The host, which
 //     forms the positions anyway, resolves both rows of both voices per frame (MsFrame: a row of the push, or a backlog slot), so a
@@ -85,60 +85,17 @@ __global__ __launch_bounds__(RT_T) void morph_stream_kernel(MsArgs A) {
 	// rt_place without its clamp: the host keeps 0 <= p <= F - 1
 	const double aa = f.pa - floor(f.pa), ab = f.pb - floor(f.pb);
 	const double wa0 = 1.0 - aa, wb0 = 1.0 - ab;
-	const double w = set.w, w0 = 1.0 - w;
 
 	if (tid == 0)
 		A.f0_out[g] = mp_f0(rt_f0(*ms_row(A.f0_a, A.bf0, f.ia, 1), *ms_row(A.f0_a, A.bf0, f.ja, 1), wa0, aa),
 							rt_f0(*ms_row(A.f0_b, A.bf0, f.ib, 1), *ms_row(A.f0_b, A.bf0, f.jb, 1), wb0, ab), set.wf);
-	{
-		double *__restrict__ out = A.ap_out + g * bins;
-		const double *__restrict__ ai = ms_row(A.ap_a, A.bap, f.ia, bins), *__restrict__ aj = ms_row(A.ap_a, A.bap, f.ja, bins);
-		const double *__restrict__ bi = ms_row(A.ap_b, A.bap, f.ib, bins), *__restrict__ bj = ms_row(A.ap_b, A.bap, f.jb, bins);
-		if (w == 0.0) rt_row(ai, aj, wa0, aa, out, bins, tid);
-		else if (w == 1.0) rt_row(bi, bj, wb0, ab, out, bins, tid);
-		else {
-			for (int t = tid; t < bins / 2; t += RT_T) {
-				const d2u x = rt_pair(ai, aj, wa0, aa, 2 * t), y = rt_pair(bi, bj, wb0, ab, 2 * t);
-				*reinterpret_cast<d2u *>(out + 2 * t) = w0 * x + w * y;
-			}
-			if (tid == 0) out[bins - 1] = w0 * rt_one(ai, aj, wa0, aa, bins - 1) + w * rt_one(bi, bj, wb0, ab, bins - 1);
-		}
-	}
-	double *__restrict__ out = A.sp_out + g * bins;
-	const double *__restrict__ ai = ms_row(A.sp_a, A.bsp, f.ia, bins), *__restrict__ aj = ms_row(A.sp_a, A.bsp, f.ja, bins);
-	const double *__restrict__ bi = ms_row(A.sp_b, A.bsp, f.ib, bins), *__restrict__ bj = ms_row(A.sp_b, A.bsp, f.jb, bins);
-	if constexpr (STRETCH) {
-		__shared__ double lga[kMaxBins], lgb[kMaxBins];
-		__shared__ double fill;
-		const double ra = set.ra, rb = set.rb;  // 0 or valid: the setter refuses the others
-		if (w == 0.0 || w == 1.0) {  // the one source's row as retime_kernel<true> writes it
-			const bool first = w == 0.0;
-			const double r = first ? ra : rb, a = first ? aa : ab, a0 = first ? wa0 : wb0;
-			const double *__restrict__ ri = first ? ai : bi, *__restrict__ rj = first ? aj : bj;
-			if (r == 0.0) rt_row(ri, rj, a0, a, out, bins, tid);
-			else rt_stretched_row(ri, rj, a0, a, out, r, A.fs, A.fft_size, tid, lga, &fill);
-			return;
-		}
-		rt_log_row(ai, aj, wa0, aa, lga, bins, tid);
-		rt_log_row(bi, bj, wb0, ab, lgb, bins, tid);
-		__syncthreads();
-		const MpLog la = mp_log(lga, ra, A.fs, A.fft_size), lb = mp_log(lgb, rb, A.fs, A.fft_size);
-		for (int b = tid; b < bins; b += RT_T) out[b] = exp(w0 * la.at(b) + w * lb.at(b));
-	} else {
-		if (w == 0.0) rt_row(ai, aj, wa0, aa, out, bins, tid);
-		else if (w == 1.0) rt_row(bi, bj, wb0, ab, out, bins, tid);
-		else {
-			for (int t = tid; t < bins / 2; t += RT_T) {
-				const d2u x = rt_pair(ai, aj, wa0, aa, 2 * t), y = rt_pair(bi, bj, wb0, ab, 2 * t);
-				d2u v;
-				v.x = exp(w0 * log(x.x) + w * log(y.x));
-				v.y = exp(w0 * log(x.y) + w * log(y.y));
-				*reinterpret_cast<d2u *>(out + 2 * t) = v;
-			}
-			if (tid == 0)
-				out[bins - 1] = exp(w0 * log(rt_one(ai, aj, wa0, aa, bins - 1)) + w * log(rt_one(bi, bj, wb0, ab, bins - 1)));
-		}
-	}
+	const MpRow pa{ms_row(A.ap_a, A.bap, f.ia, bins), ms_row(A.ap_a, A.bap, f.ja, bins), wa0, aa};
+	const MpRow pb{ms_row(A.ap_b, A.bap, f.ib, bins), ms_row(A.ap_b, A.bap, f.jb, bins), wb0, ab};
+	mp_ap_row(pa, pb, set.w, A.ap_out + g * bins, bins, tid);
+	const MpRow sa{ms_row(A.sp_a, A.bsp, f.ia, bins), ms_row(A.sp_a, A.bsp, f.ja, bins), wa0, aa};
+	const MpRow sb{ms_row(A.sp_b, A.bsp, f.ib, bins), ms_row(A.sp_b, A.bsp, f.jb, bins), wb0, ab};
+	// (the ratios are 0 or valid: the setter refuses the others)
+	mp_sp_row<STRETCH>(sa, sb, set.w, set.ra, set.rb, A.sp_out + g * bins, A.fs, A.fft_size, tid);
 }
 
 // ---- the host half: the rule of the header ----

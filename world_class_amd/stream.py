@@ -718,71 +718,44 @@ class AlignStream:
             pass
 
 
-class TrackMorph:
-    """n_streams concurrent track-morph streams in front of a StreamSynthesizer, over n_tracks resident tracks of full rows: every
-    push appends up to `max_frames` rows of a live voice per stream with one position in the stream's track per row -- device
-    memory, such as d_settled of AlignStream.push_settled_device -- and returns the morphed frames (f0, spectrogram and aperiodicity
-    rows) those positions allow, `delay` rows behind the newest: those of one whole-utterance io.morph_parameters_device pair (the
-    rows so far, the track) at position_a = the frame's index (the rule of include/world_class_track_morph.h)."""
+class _TrackMorphBase:
+    """What TrackMorph and CodedTrackMorph share: everything but the row widths.  `_prefix` names the handle's C symbols; a class
+    sets n_streams, max_frames, max_delay, bins, _h and _out (None) in its __init__ and keeps the methods that name its rows."""
 
-    def __init__(self, fs, fft_size, n_streams, n_tracks, max_track_frames, max_frames=200, max_delay=0):
-        L = _lib()
-        self.fs, self.fft_size, self.n_streams, self.n_tracks = int(fs), int(fft_size), int(n_streams), int(n_tracks)
-        self.max_track_frames, self.max_frames, self.max_delay = int(max_track_frames), int(max_frames), int(max_delay)
-        self.bins = self.fft_size // 2 + 1
-        self._h = _handle(L.wc_track_morph_create(self.fs, self.fft_size, self.n_streams, self.n_tracks, self.max_track_frames, self.max_frames,
-                                                  self.max_delay))
-        self._out = None  # the outputs of the numpy front-ends: allocated on their first call
+    _prefix = None
 
-    def set_track_device(self, track, m, d_f0_b, d_sp_b, d_ap_b):
-        """m full rows of device arrays into the slot (stream-ordered; refused while a stream that has received rows is attached)"""
-        _check(_lib().wc_track_morph_set_track_device(self._h, int(track), int(m), _opt(d_f0_b), _opt(d_sp_b), _opt(d_ap_b)))
-
-    def set_track(self, track, f0, sp, ap):
-        f0 = np.ascontiguousarray(f0, dtype=np.float64).ravel()
-        sp, ap = (np.ascontiguousarray(v, dtype=np.float64) for v in (sp, ap))
-        if sp.shape != (len(f0), self.bins) or ap.shape != sp.shape:
-            raise ValueError("a track is m F0 values and two (m, fft_size / 2 + 1) arrays")
-        d = [DeviceArray.from_host(v) for v in (f0, sp, ap)]
-        try:
-            self.set_track_device(track, len(f0), *d)
-            _check(lib().wc_synchronize())
-        finally:
-            for x in d:
-                x.free()
+    def _c(self, name):
+        return getattr(_lib(), self._prefix + name)
 
     def reset(self, stream, track, delay=0):
         """attach the stream to a track that has been set, `delay` rows behind the newest (the lag of the alignment stream whose
         settled positions it is given); counts, weights and ratios return to zero"""
-        _check(_lib().wc_track_morph_reset(self._h, int(stream), int(track), int(delay)))
+        _check(self._c("reset")(self._h, int(stream), int(track), int(delay)))
 
     def set_weight(self, stream, weight, f0_weight=None):
         """the blend of the frames formed from the next push on: 0 = the live voice, 1 = the track; f0_weight None: the weight"""
-        _check(_lib().wc_track_morph_set_weight(self._h, int(stream), float(weight), float(weight if f0_weight is None else f0_weight)))
+        _check(self._c("set_weight")(self._h, int(stream), float(weight), float(weight if f0_weight is None else f0_weight)))
 
     def set_ratios(self, stream, ratio_a, ratio_b):
         """spectral ratio of the live voice / of the track (0 = none), applied to that log envelope in front of the blend"""
-        _check(_lib().wc_track_morph_set_ratios(self._h, int(stream), float(ratio_a), float(ratio_b)))
+        _check(self._c("set_ratios")(self._h, int(stream), float(ratio_a), float(ratio_b)))
 
     def _counts(self, n):
         if len(n) != self.n_streams:
             raise ValueError("one entry per stream")
         return _ints(n)
 
-    def push_device(self, n_a, d_f0_a, d_sp_a, d_ap_a, d_position_b, d_f0_out, d_sp_out, d_ap_out):
-        """device pointers in and out (packed layouts of the header), one position per pushed row; returns the frames formed per
-        stream"""
+    def _push_device(self, n_a, *d):
         out = (C.c_int * self.n_streams)()
-        _check(_lib().wc_track_morph_push_device(self._h, self._counts(n_a), _opt(d_f0_a), _opt(d_sp_a), _opt(d_ap_a), _opt(d_position_b),
-                                                 _opt(d_f0_out), _opt(d_sp_out), _opt(d_ap_out), out))
+        _check(self._c("push_device")(self._h, self._counts(n_a), *(_opt(x) for x in d), out))
         return list(out)
 
     def flush_device(self, want, d_tail, d_f0_out, d_sp_out, d_ap_out):
         """the rows that still wait, at the positions of AlignStream's tail_device for the same `want` (one flag per stream); the
         wanted streams have ended afterwards.  Returns the frames formed per stream"""
         out = (C.c_int * self.n_streams)()
-        _check(_lib().wc_track_morph_flush_device(self._h, self._counts([1 if v else 0 for v in want]), _opt(d_tail), _opt(d_f0_out), _opt(d_sp_out),
-                                                  _opt(d_ap_out), out))
+        _check(self._c("flush_device")(self._h, self._counts([1 if v else 0 for v in want]), _opt(d_tail), _opt(d_f0_out), _opt(d_sp_out),
+                                       _opt(d_ap_out), out))
         return list(out)
 
     def _run(self, ins, run):
@@ -805,9 +778,8 @@ class TrackMorph:
             o += c
         return res
 
-    def push(self, rows, positions):
-        """rows[u]: (f0, sp rows, ap rows) with the new rows of the live voice of stream u (empty = none); positions[u]: one
-        position in the track per row.  Returns per stream (f0, sp, ap) of the frames formed."""
+    def _push(self, rows, positions, sp_width, ap_width):
+        """push for rows of the two widths"""
         if len(rows) != self.n_streams or len(positions) != self.n_streams:
             raise ValueError("one entry per stream")
         counts = [len(v[0]) for v in rows]
@@ -815,10 +787,20 @@ class TrackMorph:
             raise ValueError("one position per pushed row")
         tot = sum(counts)
         f0 = np.concatenate([np.asarray(v[0], dtype=np.float64).ravel() for v in rows]) if tot else np.zeros(1)
-        sp = np.concatenate([np.asarray(v[1], dtype=np.float64).reshape(-1, self.bins) for v in rows]) if tot else np.zeros((1, self.bins))
-        ap = np.concatenate([np.asarray(v[2], dtype=np.float64).reshape(-1, self.bins) for v in rows]) if tot else np.zeros((1, self.bins))
+        sp = np.concatenate([np.asarray(v[1], dtype=np.float64).reshape(-1, sp_width) for v in rows]) if tot else np.zeros((1, sp_width))
+        ap = np.concatenate([np.asarray(v[2], dtype=np.float64).reshape(-1, ap_width) for v in rows]) if tot else np.zeros((1, ap_width))
         pos = np.concatenate([np.asarray(p, dtype=np.float64).ravel() for p in positions]) if tot else np.zeros(1)
         return self._run((f0, sp, ap, pos), lambda *a: self.push_device(counts, *a))
+
+    def _set_track(self, track, f0, sp, ap):
+        """set_track for rows whose shapes the class has checked"""
+        d = [DeviceArray.from_host(v) for v in (f0, sp, ap)]
+        try:
+            self.set_track_device(track, len(f0), *d)
+            _check(lib().wc_synchronize())
+        finally:
+            for x in d:
+                x.free()
 
     def flush(self, tails, streams=None):
         """tails[u]: what AlignStream.tail returns for stream u (K = min(delay + 1, rows received) doubles; None: not wanted);
@@ -838,24 +820,24 @@ class TrackMorph:
         return self._run((tail,), lambda *a: self.flush_device(want, *a))
 
     def frames_received(self, stream):
-        return int(_lib().wc_track_morph_frames_received(self._h, int(stream)))
+        return int(self._c("frames_received")(self._h, int(stream)))
 
     def frames_formed(self, stream):
-        return int(_lib().wc_track_morph_frames_formed(self._h, int(stream)))
+        return int(self._c("frames_formed")(self._h, int(stream)))
 
     def pending(self, stream):
         """rows of the live voice the stream keeps for frames still to be formed"""
-        return int(_lib().wc_track_morph_pending(self._h, int(stream)))
+        return int(self._c("pending")(self._h, int(stream)))
 
     def get_delay(self, stream):
-        return int(_lib().wc_track_morph_get_delay(self._h, int(stream)))
+        return int(self._c("get_delay")(self._h, int(stream)))
 
     def track_length(self, track):
-        return int(_lib().wc_track_morph_track_length(self._h, int(track)))
+        return int(self._c("track_length")(self._h, int(track)))
 
     def close(self):
         if getattr(self, "_h", None):
-            _lib().wc_track_morph_destroy(self._h)
+            self._c("destroy")(self._h)
             self._h = None
 
     def __del__(self):
@@ -865,11 +847,53 @@ class TrackMorph:
             pass
 
 
-class CodedTrackMorph:
+class TrackMorph(_TrackMorphBase):
+    """n_streams concurrent track-morph streams in front of a StreamSynthesizer, over n_tracks resident tracks of full rows: every
+    push appends up to `max_frames` rows of a live voice per stream with one position in the stream's track per row -- device
+    memory, such as d_settled of AlignStream.push_settled_device -- and returns the morphed frames (f0, spectrogram and aperiodicity
+    rows) those positions allow, `delay` rows behind the newest: those of one whole-utterance io.morph_parameters_device pair (the
+    rows so far, the track) at position_a = the frame's index (the rule of include/world_class_track_morph.h)."""
+
+    _prefix = "wc_track_morph_"
+
+    def __init__(self, fs, fft_size, n_streams, n_tracks, max_track_frames, max_frames=200, max_delay=0):
+        L = _lib()
+        self.fs, self.fft_size, self.n_streams, self.n_tracks = int(fs), int(fft_size), int(n_streams), int(n_tracks)
+        self.max_track_frames, self.max_frames, self.max_delay = int(max_track_frames), int(max_frames), int(max_delay)
+        self.bins = self.fft_size // 2 + 1
+        self._h = _handle(L.wc_track_morph_create(self.fs, self.fft_size, self.n_streams, self.n_tracks, self.max_track_frames, self.max_frames,
+                                                  self.max_delay))
+        self._out = None  # the outputs of the numpy front-ends: allocated on their first call
+
+    def set_track_device(self, track, m, d_f0_b, d_sp_b, d_ap_b):
+        """m full rows of device arrays into the slot (stream-ordered; refused while a stream that has received rows is attached)"""
+        _check(_lib().wc_track_morph_set_track_device(self._h, int(track), int(m), _opt(d_f0_b), _opt(d_sp_b), _opt(d_ap_b)))
+
+    def set_track(self, track, f0, sp, ap):
+        f0 = np.ascontiguousarray(f0, dtype=np.float64).ravel()
+        sp, ap = (np.ascontiguousarray(v, dtype=np.float64) for v in (sp, ap))
+        if sp.shape != (len(f0), self.bins) or ap.shape != sp.shape:
+            raise ValueError("a track is m F0 values and two (m, fft_size / 2 + 1) arrays")
+        self._set_track(track, f0, sp, ap)
+
+    def push_device(self, n_a, d_f0_a, d_sp_a, d_ap_a, d_position_b, d_f0_out, d_sp_out, d_ap_out):
+        """device pointers in and out (packed layouts of the header), one position per pushed row; returns the frames formed per
+        stream"""
+        return self._push_device(n_a, d_f0_a, d_sp_a, d_ap_a, d_position_b, d_f0_out, d_sp_out, d_ap_out)
+
+    def push(self, rows, positions):
+        """rows[u]: (f0, sp rows, ap rows) with the new rows of the live voice of stream u (empty = none); positions[u]: one
+        position in the track per row.  Returns per stream (f0, sp, ap) of the frames formed."""
+        return self._push(rows, positions, self.bins, self.bins)
+
+
+class CodedTrackMorph(_TrackMorphBase):
     """TrackMorph with its tracks, its ring and its live rows held as coded features (include/world_class_track_morph_coded.h):
     `number_of_dimensions` doubles of the coded spectral envelope and GetNumberOfAperiodicities(fs) band aperiodicities per row, as
     codec.code_features_device writes them -- the arrays an AlignStream takes.  The frames it returns are full rows (f0, spectrogram
     and aperiodicity rows) and equal, bit for bit, those of a TrackMorph fed codec.decode_features_device of the same coded rows."""
+
+    _prefix = "wc_track_morph_coded_"
 
     def __init__(self, fs, fft_size, number_of_dimensions, n_streams, n_tracks, max_track_frames, max_frames=200, max_delay=0):
         L = _lib()
@@ -892,128 +916,18 @@ class CodedTrackMorph:
         csp, cap = (np.ascontiguousarray(v, dtype=np.float64) for v in (csp, cap))
         if csp.shape != (len(f0), self.number_of_dimensions) or cap.shape != (len(f0), self.n_ap):
             raise ValueError("a coded track is m F0 values, an (m, number_of_dimensions) and an (m, number of aperiodicities) array")
-        d = [DeviceArray.from_host(v) for v in (f0, csp, cap)]
-        try:
-            self.set_track_device(track, len(f0), *d)
-            _check(lib().wc_synchronize())
-        finally:
-            for x in d:
-                x.free()
-
-    def reset(self, stream, track, delay=0):
-        """attach the stream to a track that has been set, `delay` rows behind the newest (the lag of the alignment stream whose
-        settled positions it is given); counts, weights and ratios return to zero"""
-        _check(_lib().wc_track_morph_coded_reset(self._h, int(stream), int(track), int(delay)))
-
-    def set_weight(self, stream, weight, f0_weight=None):
-        """the blend of the frames formed from the next push on: 0 = the live voice, 1 = the track; f0_weight None: the weight"""
-        _check(_lib().wc_track_morph_coded_set_weight(self._h, int(stream), float(weight), float(weight if f0_weight is None else f0_weight)))
-
-    def set_ratios(self, stream, ratio_a, ratio_b):
-        """spectral ratio of the live voice / of the track (0 = none), applied to that log envelope in front of the blend"""
-        _check(_lib().wc_track_morph_coded_set_ratios(self._h, int(stream), float(ratio_a), float(ratio_b)))
-
-    def _counts(self, n):
-        if len(n) != self.n_streams:
-            raise ValueError("one entry per stream")
-        return _ints(n)
+        self._set_track(track, f0, csp, cap)
 
     def push_device(self, n_a, d_f0_a, d_coded_sp_a, d_coded_ap_a, d_position_b, d_f0_out, d_sp_out, d_ap_out):
         """device pointers in (coded rows) and out (full rows), packed as the header says, one position per pushed row; returns the
         frames formed per stream"""
-        out = (C.c_int * self.n_streams)()
-        _check(_lib().wc_track_morph_coded_push_device(self._h, self._counts(n_a), _opt(d_f0_a), _opt(d_coded_sp_a), _opt(d_coded_ap_a),
-                                                       _opt(d_position_b), _opt(d_f0_out), _opt(d_sp_out), _opt(d_ap_out), out))
-        return list(out)
-
-    def flush_device(self, want, d_tail, d_f0_out, d_sp_out, d_ap_out):
-        """the rows that still wait, at the positions of AlignStream's tail_device for the same `want` (one flag per stream); the
-        wanted streams have ended afterwards.  Returns the frames formed per stream"""
-        out = (C.c_int * self.n_streams)()
-        _check(_lib().wc_track_morph_coded_flush_device(self._h, self._counts([1 if v else 0 for v in want]), _opt(d_tail), _opt(d_f0_out),
-                                                        _opt(d_sp_out), _opt(d_ap_out), out))
-        return list(out)
-
-    def _run(self, ins, run):
-        if self._out is None:
-            cap = self.n_streams * max(self.max_frames, self.max_delay)
-            self._out = (DeviceArray(cap), DeviceArray(cap * self.bins), DeviceArray(cap * self.bins))
-        d = [DeviceArray.from_host(np.ascontiguousarray(x)) for x in ins]
-        try:
-            formed = run(*d, *self._out)
-            tot = sum(formed)
-            f0 = self._out[0].to_host()[:tot]
-            sp = self._out[1].to_host()[:tot * self.bins].reshape(tot, self.bins)
-            ap = self._out[2].to_host()[:tot * self.bins].reshape(tot, self.bins)
-        finally:
-            for x in d:
-                x.free()
-        res, o = [], 0
-        for c in formed:
-            res.append((f0[o:o + c].copy(), sp[o:o + c].copy(), ap[o:o + c].copy()))
-            o += c
-        return res
+        return self._push_device(n_a, d_f0_a, d_coded_sp_a, d_coded_ap_a, d_position_b, d_f0_out, d_sp_out, d_ap_out)
 
     def push(self, rows, positions):
         """rows[u]: (f0, coded sp rows, coded ap rows) with the new rows of the live voice of stream u (empty = none); positions[u]:
         one position in the track per row.  Returns per stream (f0, sp, ap) of the frames formed, full rows."""
-        if len(rows) != self.n_streams or len(positions) != self.n_streams:
-            raise ValueError("one entry per stream")
-        counts = [len(v[0]) for v in rows]
-        if [len(np.atleast_1d(p)) for p in positions] != counts:
-            raise ValueError("one position per pushed row")
-        tot = sum(counts)
-        nd, n_ap = self.number_of_dimensions, self.n_ap
-        f0 = np.concatenate([np.asarray(v[0], dtype=np.float64).ravel() for v in rows]) if tot else np.zeros(1)
-        csp = np.concatenate([np.asarray(v[1], dtype=np.float64).reshape(-1, nd) for v in rows]) if tot else np.zeros((1, nd))
-        cap = np.concatenate([np.asarray(v[2], dtype=np.float64).reshape(-1, n_ap) for v in rows]) if tot else np.zeros((1, n_ap))
-        pos = np.concatenate([np.asarray(p, dtype=np.float64).ravel() for p in positions]) if tot else np.zeros(1)
-        return self._run((f0, csp, cap, pos), lambda *a: self.push_device(counts, *a))
-
-    def flush(self, tails, streams=None):
-        """tails[u]: what AlignStream.tail returns for stream u (K = min(delay + 1, rows received) doubles; None: not wanted);
-        streams None: every stream with an entry.  Returns per stream (f0, sp, ap) of the frames formed, empty where not wanted"""
-        if len(tails) != self.n_streams:
-            raise ValueError("one entry per stream")
-        if streams is None:
-            streams = [u for u in range(self.n_streams) if tails[u] is not None]
-        want = [0] * self.n_streams
-        for u in streams:
-            want[int(u)] = 1
-        ks = [min(self.get_delay(u) + 1, self.frames_received(u)) if want[u] else 0 for u in range(self.n_streams)]
-        parts = [np.asarray(tails[u], dtype=np.float64).ravel() for u in range(self.n_streams) if want[u]]
-        if [len(p) for p in parts] != [k for u, k in enumerate(ks) if want[u]]:
-            raise ValueError("min(delay + 1, rows received) tail positions per wanted stream")
-        tail = np.concatenate(parts) if parts and sum(ks) else np.zeros(1)
-        return self._run((tail,), lambda *a: self.flush_device(want, *a))
-
-    def frames_received(self, stream):
-        return int(_lib().wc_track_morph_coded_frames_received(self._h, int(stream)))
-
-    def frames_formed(self, stream):
-        return int(_lib().wc_track_morph_coded_frames_formed(self._h, int(stream)))
-
-    def pending(self, stream):
-        """rows of the live voice the stream keeps for frames still to be formed"""
-        return int(_lib().wc_track_morph_coded_pending(self._h, int(stream)))
-
-    def get_delay(self, stream):
-        return int(_lib().wc_track_morph_coded_get_delay(self._h, int(stream)))
-
-    def track_length(self, track):
-        return int(_lib().wc_track_morph_coded_track_length(self._h, int(track)))
+        return self._push(rows, positions, self.number_of_dimensions, self.n_ap)
 
     def device_bytes(self):
         """what the handle allocated on the device: tracks + ring + scratch + records (the header's formula)"""
         return int(_lib().wc_track_morph_coded_device_bytes(self._h))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            _lib().wc_track_morph_coded_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
