@@ -15,6 +15,7 @@
 #include "../../include/world_class_io.h"
 #include "wc_device.hpp"
 #include "wc_internal.hpp"
+#include "wc_pcm16.hpp"
 #include "wc_stages.hpp"
 
 using namespace wc;
@@ -176,15 +177,7 @@ int read_matrix(const char *filename, const char *magic, double **rows) {
 	return 1;
 }
 
-// wavwrite's sample conversion: static_cast<int>(x * 32767) on the reference's platform (x86 cvttsd2si: NaN and
-// out-of-range values become INT_MIN), then clamp to int16
-__host__ __device__ inline int pcm16_of(double x) {
-	const double v = x * 32767;
-	int iv;
-	if (!(v > -2147483649.0 && v < 2147483648.0)) iv = INT_MIN;
-	else iv = static_cast<int>(v);
-	return iv < -32768 ? -32768 : (iv > 32767 ? 32767 : iv);
-}
+// (wavwrite's sample conversion, pcm16_of: wc_pcm16.hpp)
 
 // ---- device kernels -------------------------------------------------------------------------------------------
 __global__ void pcm16_to_double_kernel(const int16_t *__restrict__ p, long long n, double *__restrict__ x) {
