@@ -30,7 +30,7 @@
 
 #include "../../include/world_class_resample.h"
 #include "wc_internal.hpp"
-#include "wc_pcm16.hpp"
+#include "wc_resample_dev.hpp"
 
 using namespace wc;
 
@@ -42,7 +42,6 @@ constexpr int kPhaseThreadsWide = 1024;   // where the tile leaves room for one 
 #ifndef WC_RS_UNROLL
 #define WC_RS_UNROLL 16
 #endif
-constexpr int kPlainBlock = 256;
 constexpr long long kMaxTable = 1ll << 21;  // doubles
 constexpr long long kLdsPreferred = 8192;   // doubles of a tile that is made longer than one wavefront row per phase (64 KB)
 constexpr long long kLdsMax = 20480;        // doubles a tile may take at all: the 160 KB of a gfx950 compute unit
@@ -169,14 +168,6 @@ struct RsRec {
 	int block0;       // the record's first block in its launch
 	int pad_;
 };
-// one stream's new samples (resample_widen_kernel)
-struct RsPush {
-	long long c_off;      // first new sample in the packed chunk
-	long long cur_off;    // the stream's buffer of this push, in doubles from the buffers' base
-	long long other_off;  // the buffer of the next push
-	int n_new;
-	int block0;
-};
 struct RsArgs {
 	const RsRec *rec;
 	int n_rec;
@@ -185,27 +176,6 @@ struct RsArgs {
 	int L, M, K, taps;
 	int R, pad, split, half, out_format;  // half: words of one half of a split tile
 };
-
-template <int FMT> __device__ __forceinline__ double rs_load(const void *x, long long i);
-template <> __device__ __forceinline__ double rs_load<0>(const void *x, long long i) { return static_cast<const double *>(x)[i]; }
-template <> __device__ __forceinline__ double rs_load<1>(const void *x, long long i) { return pcm16_to_double(static_cast<const int16_t *>(x)[i]); }
-template <> __device__ __forceinline__ double rs_load<2>(const void *x, long long i) { return static_cast<double>(static_cast<const float *>(x)[i]); }
-
-__device__ __forceinline__ void rs_store(void *y, int out_format, long long i, double v) {
-	if (out_format == 0) static_cast<double *>(y)[i] = v;
-	else static_cast<int16_t *>(y)[i] = static_cast<int16_t>(pcm16_of(v));
-}
-
-// the record of block b: the last one whose block0 is not above b (block0 ascends, rec[0].block0 == 0)
-template <class T> __device__ __forceinline__ int rs_find(const T *rec, int n, int b) {
-	int lo = 0, hi = n - 1;
-	while (lo < hi) {
-		const int mid = (lo + hi + 1) >> 1;
-		if (rec[mid].block0 <= b) lo = mid;
-		else hi = mid - 1;
-	}
-	return lo;
-}
 
 // THE output of the rule: the taps of one table row by ascending j from 0.0, every product rounded, then every sum.  `in` hands out
 // x[q - K], x[q - K + 1], ... wherever the mapping keeps them, in runs: in.at(r) is the r-th sample from where `in` stands, for
@@ -321,19 +291,6 @@ template <int FMT> __global__ __launch_bounds__(kPlainBlock) void resample_plain
 	in.i = r.q0 + dq - a.K;
 	in.lo = r.lo; in.hi = r.hi;
 	rs_store(a.y, a.out_format, r.y_off + i, rs_output(in, G + (size_t)p * a.taps, a.taps));
-}
-
-// A stream's push, first half: the new samples widened behind the 2K of history in the buffer of this push, and the last 2K of
-// (history, new samples) to the head of the other buffer.  Nothing that is read here is written here.
-template <int FMT> __global__ __launch_bounds__(kPlainBlock) void resample_widen_kernel(const RsPush *push, int n_push, const void *chunk, double *buf, int hist) {
-	const RsPush w = push[rs_find(push, n_push, (int)blockIdx.x)];
-	const long long k = ((long long)blockIdx.x - w.block0) * kPlainBlock + threadIdx.x;
-	if (k < w.n_new) {
-		buf[w.cur_off + hist + k] = rs_load<FMT>(chunk, w.c_off + k);
-	} else if (k < (long long)w.n_new + hist) {
-		const long long b = k - w.n_new, s = w.n_new + b;
-		buf[w.other_off + b] = s < hist ? buf[w.cur_off + s] : rs_load<FMT>(chunk, w.c_off + s - hist);
-	}
 }
 
 // ---- what the batch handle and the stream handle share --------------------------------------------------------------------------
