@@ -108,6 +108,22 @@ def test_int16_in_and_int16_out_on_one_stream():
     assert y.dtype == np.int16 and np.array_equal(y, whole(conv, [x], "i16")[0])
 
 
+def test_float32_in_on_one_stream_through_the_phase_mapping():
+    """float32 samples, the third input format a push widens: four pushes of 400 at 48 -> 24 kHz (L = 1, K = 136), each of at least
+    phase_min = 32 outputs, so the pushes take the phase mapping (the batch tests hold the plain one in float32)"""
+    conv = (48000, 24000)
+    tile_outputs, phase_min, _ = rs.tiling(*conv)
+    x = np.random.default_rng(3).uniform(-1, 1, 1600).astype(np.float32)
+    s = rs.ResampleStream(*conv, 1, 400)
+    try:
+        parts = [s.push([x[a:a + 400]], [a + 400 >= len(x)])[0] for a in range(0, len(x), 400)]
+    finally:
+        s.close()
+    assert tile_outputs > 0 and phase_min == 32 and len(parts) == 4 and all(len(p) >= phase_min for p in parts)
+    y = np.concatenate(parts)
+    assert y.dtype == np.float64 and np.array_equal(y, whole(conv, [x])[0])
+
+
 def test_create_refusals():
     for args in ((44100, 48000, 0, 100), (44100, 48000, 1, 0), (44100, 44100, 1, 100), (24000, 48000, 1, 2 ** 30)):
         with pytest.raises(WorldClassError):

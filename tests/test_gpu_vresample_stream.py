@@ -170,6 +170,22 @@ def test_int16_in_and_int16_out_on_one_stream():
     assert y.dtype == np.int16 and np.array_equal(y, whole([x], UPR, "i16")[0])
 
 
+def test_float32_in_on_one_stream_through_the_segment_mapping():
+    """float32 samples, the third input format a push widens: four pushes of 600 at step 2^32 + 1 on the default table, each of at
+    least segment_min = 256 outputs, so the pushes take the segment mapping (the batch tests hold the plain one in float32)"""
+    step = ONE + 1
+    tile_outputs, segment_min, _ = vr.tiling(step, step)
+    x = np.random.default_rng(3).uniform(-1, 1, 2400).astype(np.float32)
+    s = vr.VResampleStream(step, step, 1, 600)
+    try:
+        parts = [s.push([x[a:a + 600]], [a + 600 >= len(x)])[0] for a in range(0, len(x), 600)]
+    finally:
+        s.close()
+    assert tile_outputs > 0 and segment_min == 256 and len(parts) == 4 and all(len(p) >= segment_min for p in parts)
+    y = np.concatenate(parts)
+    assert y.dtype == np.float64 and np.array_equal(y, whole([x], step, lo=step, hi=step)[0])
+
+
 def test_create_refusals():
     for args in ((LO, HI, 0, 100), (LO, HI, 1, 0), (HI, LO, 1, 100), ((1 << 28) - 1, HI, 1, 100)):
         with pytest.raises(WorldClassError):

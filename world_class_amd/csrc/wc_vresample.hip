@@ -2,7 +2,8 @@
 // read at a continuous phase out of a table of piecewise polynomials, as a whole-batch call with a step per utterance and as a streaming
 // handle whose steps move between pushes.  The header states the rule; this file is its only implementation: the batch call and the
 // streams run the same two kernels, and both kernels form an output in vr_output, so what a stream commits is bit for bit the whole
-// call's by construction.
+// call's by construction.  The filter's prototype and the host half of the handles are the rational converter's too:
+// wc_resample_plan.hpp.
 //
 // Two mappings of outputs to lanes.
 //   Segment mapping (vresample_segment_kernel).  Outputs whose fractions f fall into the same segment share the D+1 coefficients of
@@ -19,12 +20,10 @@
 #include <algorithm>
 #include <climits>
 #include <cmath>
-#include <type_traits>
 #include <vector>
 
 #include "../../include/world_class_vresample.h"
-#include "wc_internal.hpp"
-#include "wc_resample_dev.hpp"
+#include "wc_resample_plan.hpp"
 
 using namespace wc;
 
@@ -39,7 +38,6 @@ constexpr int kSegThreadsWide = 1024;   // where the tile leaves room for one bl
 #ifndef WC_VR_FORCE_PLAIN
 #define WC_VR_FORCE_PLAIN 0   // 1: a variant build for measurements that never takes the segment mapping
 #endif
-constexpr long long kMaxTable = 1ll << 21;   // doubles
 constexpr int kMaxSegments = 256;
 constexpr int kMaxDegree = 7;
 #ifndef WC_VR_TILE_MAX
@@ -55,22 +53,23 @@ typedef unsigned __int128 uwide;
 typedef unsigned long long u64;
 
 // ---- the plan ---------------------------------------------------------------------------------------------------------------
+constexpr char kName[] = "vresample";
+
 struct Plan {
 	u64 step_min, step_max;
-	int zeros, B, P, D, K, taps;
-	double s, beta;
+	int B, P, D, K, taps;
+	RsFilter f;
 };
 
 bool step_ok(u64 step) { return step >= kStepLo && step <= kStepHi; }
 
-const char *plan_of(u64 step_min, u64 step_max, int zeros, double rolloff, double beta, int phase_bits, int degree, Plan *out) {
+// the refusal's text, or empty
+std::string plan_of(u64 step_min, u64 step_max, int zeros, double rolloff, double beta, int phase_bits, int degree, Plan *out) {
 	Plan p = {};
 	if (!step_ok(step_min) || !step_ok(step_max)) return "vresample: a step outside [2^28, 2^36]";
 	if (step_min > step_max) return "vresample: step_min above step_max";
-	if (zeros < 0) return "vresample: zeros must be at least 1 (0: the default, 64)";
-	if (!(rolloff >= 0.0 && rolloff <= 1.0)) return "vresample: rolloff must lie in (0, 1] (0.0: the default)";
-	if (!std::isfinite(beta) || beta < 0.0) return "vresample: beta must be finite and not negative (0.0: the default)";
-	if (beta > 700.0) return "vresample: beta above 700 (I0 overflows)";
+	const std::string why = rs_filter_check(kName, zeros, rolloff, beta);
+	if (!why.empty()) return why;
 	if (phase_bits < 0 || phase_bits > 8) return "vresample: phase_bits must lie in 0 .. 8";
 	if (degree != 0 && degree != 3 && degree != 5 && degree != 7) return "vresample: degree must be 3, 5 or 7 (0: the default pair, 3 bits and degree 5)";
 	if (degree == 0 && phase_bits != 0) return "vresample: degree 0 selects the default pair and takes phase_bits 0 only";
@@ -78,36 +77,11 @@ const char *plan_of(u64 step_min, u64 step_max, int zeros, double rolloff, doubl
 	p.B = degree == 0 ? 3 : phase_bits;
 	p.D = degree == 0 ? 5 : degree;
 	p.P = 1 << p.B;
-	p.zeros = zeros == 0 ? 64 : zeros;
-	const double ro = rolloff == 0.0 ? 0.9475937167399596 : rolloff;
-	p.beta = beta == 0.0 ? 14.769656459379492 : beta;
-	p.s = ro * std::min(1.0, 4294967296.0 / (double)step_max);
-	const double kd = std::ceil(p.zeros / p.s);
-	if (!(kd <= (double)kMaxTable) || (long long)p.P * (p.D + 1) * (2 * (long long)kd + 1) > kMaxTable) return "vresample: a table of more than 2^21 doubles";
-	p.K = (int)kd;
+	p.f = rs_filter_of(zeros, rolloff, beta, 4294967296.0 / (double)step_max);
+	if (!(p.K = rs_half_width(p.f, (long long)p.P * (p.D + 1)))) return rs_table_refusal(kName);
 	p.taps = 2 * p.K + 1;
 	*out = p;
-	return nullptr;
-}
-
-// (wc_resample.hip's series: every term is positive, so the sum is good to a few ulp wherever it does not overflow)
-double bessel_i0(double x) {
-	const double h = 0.25 * x * x;
-	double term = 1.0, sum = 1.0;
-	for (int k = 1; k < 4000; ++k) {
-		term = term * h / ((double)k * k);
-		sum += term;
-		if (term < 1e-18 * sum) break;
-	}
-	return sum;
-}
-
-double prototype(const Plan &p, double i0b, double d) {
-	const double pi = 3.14159265358979323846;
-	const double u = d * p.s / p.zeros;
-	const double w = std::fabs(u) < 1.0 ? bessel_i0(p.beta * std::sqrt(1.0 - u * u)) / i0b : 0.0;
-	const double v = p.s * d;
-	return p.s * (v == 0.0 ? 1.0 : std::sin(pi * v) / (pi * v)) * w;
+	return std::string();
 }
 
 // The node system is the same for every segment and tap: its inverse once (Gauss-Jordan with row pivoting in long double), then every
@@ -139,14 +113,14 @@ void build_table(const Plan &p, double *C) {
 			for (int c = 0; c < 2 * n; ++c) A[r][c] -= f * A[col][c];
 		}
 	}
-	const double i0b = bessel_i0(p.beta);
+	const double i0b = bessel_i0(p.f.beta);
 	double g[kMaxDegree + 1];
 	for (int seg = 0; seg < p.P; ++seg)
 		for (int j = 0; j < p.taps; ++j) {
 			const double k = (double)(j - p.K);
 			for (int i = 0; i < n; ++i) {
 				const double phi = ((double)seg + (nu[i] + 1.0) / 2.0) / (double)p.P;
-				g[i] = prototype(p, i0b, k - phi);
+				g[i] = rs_prototype(p.f, i0b, k - phi);
 			}
 			double *c = C + ((size_t)seg * p.taps + j) * n;
 			for (int m = 0; m < n; ++m) {
@@ -173,12 +147,8 @@ long long count_of(long long q, unsigned f, u64 step, int K, long long T, bool f
 }
 
 // ---- the tiling -------------------------------------------------------------------------------------------------------------
-struct Tiling {
-	int tile_out;   // outputs of a tile; 0: no segment mapping
-	int span_max;   // doubles of the input tile (even)
-	int lds_bytes;
-	int threads;    // of a block of the segment mapping
-	long long seg_min;
+struct Tiling : RsTiles {  // tile_out 0: no segment mapping; tiled_min: the segment mapping's segment_min
+	int span_max;  // doubles of the input tile (even)
 };
 
 long long tile_span(const Plan &p, long long tile) {
@@ -192,7 +162,7 @@ long long tile_bytes(const Plan &p, long long tile) {
 
 Tiling tiling_of(const Plan &p) {
 	Tiling t = {};
-	t.seg_min = std::max((long long)kSegMinRows * p.P, (long long)kPlainBlock);
+	t.tiled_min = std::max((long long)kSegMinRows * p.P, (long long)kPlainBlock);
 	int tile = 0;
 	for (int cand = kTileMax; cand >= kTileMin && !tile; cand /= 2)
 		if (tile_bytes(p, cand) <= kLdsPreferred) tile = cand;
@@ -359,165 +329,78 @@ template <int FMT, int D> __global__ __launch_bounds__(kPlainBlock) void vresamp
 }
 
 // f(format, degree) with both as compile-time constants
-template <int N> using Const = std::integral_constant<int, N>;
 template <class F> void with_variant(int fmt, int D, F &&f) {
-	auto by_degree = [&](auto format) {
-		if (D == 3) f(format, Const<3>());
-		else if (D == 5) f(format, Const<5>());
-		else f(format, Const<7>());
-	};
-	if (fmt == 0) by_degree(Const<0>());
-	else if (fmt == 1) by_degree(Const<1>());
-	else by_degree(Const<2>());
+	rs_with_format(fmt, [&](auto format) {
+		if (D == 3) f(format, RsConst<3>());
+		else if (D == 5) f(format, RsConst<5>());
+		else f(format, RsConst<7>());
+	});
 }
 
-// ---- what the batch handle and the stream handle share --------------------------------------------------------------------------
-struct Core {
-	Plan p;
-	Tiling t;
-	bool seg = false;  // the segment mapping is available
-	Device *dev = nullptr;
-	DevBuf C;
-};
-
-void core_destroy(Core *c) {
-	if (!c) return;
-	c->C.release();
-	delete c;
-}
+// ---- the handles (wc_resample_plan.hpp) around them ------------------------------------------------------------------------------
+typedef RsCore<Plan, Tiling> Core;
 
 // the table built and uploaded for a checked plan; nullptr + error on failure
 Core *core_create(const Plan &p) {
-	Device *dev = current_device();
-	if (!dev) return nullptr;
-	DeviceLock lock(dev);
-	Core *c = new Core();
-	c->p = p;
-	c->t = tiling_of(p);
-	c->dev = dev;
-	std::vector<double> C((size_t)p.P * p.taps * (p.D + 1));
-	build_table(p, C.data());
-	if (c->C.reserve(C.size() * sizeof(double)) || hipMemcpy(c->C.p, C.data(), C.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
-		set_error("vresample: the table could not be uploaded");
-		core_destroy(c);
-		return nullptr;
-	}
-	// a tile above the 64 KB every kernel may take has to be asked for (the library is built for gfx950 alone, whose compute units
-	// have the 160 KB that kLdsMax counts on: a device that grants less is an error, not a reason to change the mapping quietly)
-	c->seg = c->t.tile_out > 0 && !WC_VR_FORCE_PLAIN;
-	const size_t bytes = (size_t)c->t.lds_bytes;
-	if (c->seg && bytes > 65536) {
-		int limit = 0;
-		bool ok = hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, dev->id) == hipSuccess && (size_t)limit >= bytes;
-		for (int fmt = 0; fmt < 3 && ok; ++fmt)
-			with_variant(fmt, p.D, [&](auto format, auto degree) {
-				ok = hipFuncSetAttribute((const void *)vresample_segment_kernel<decltype(format)::value, decltype(degree)::value>,
-										 hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
-			});
-		if (!ok) {
-			(void)hipGetLastError();
-			set_error("vresample: the device grants " + std::to_string(limit) + " bytes of local memory per workgroup, the tile needs " + std::to_string(bytes));
-			core_destroy(c);
-			return nullptr;
-		}
-	}
-	return c;
-}
-
-bool rec_is_seg(const Core &c, long long n_out) { return c.seg && n_out >= c.t.seg_min; }
-int rec_blocks(const Core &c, long long n_out) {
-	return rec_is_seg(c, n_out) ? (int)((n_out + c.t.tile_out - 1) / c.t.tile_out) : (int)((n_out + kPlainBlock - 1) / kPlainBlock);
-}
-
-// the host's records sorted into the staging (segment-mapping records first, block0 assigned per launch)
-struct Sorted {
-	int n_seg = 0, n_plain = 0, blocks_seg = 0, blocks_plain = 0;
-};
-Sorted sort_records(const Core &c, const std::vector<VrRec> &recs, VrRec *to) {
-	Sorted s;
-	for (const VrRec &r : recs) s.n_seg += rec_is_seg(c, r.n_out) ? 1 : 0;
-	int ks = 0, kq = s.n_seg;
-	for (const VrRec &r : recs) {
-		const bool sg = rec_is_seg(c, r.n_out);
-		VrRec &d = to[sg ? ks++ : kq++];
-		d = r;
-		d.block0 = sg ? s.blocks_seg : s.blocks_plain;
-		(sg ? s.blocks_seg : s.blocks_plain) += rec_blocks(c, r.n_out);
-	}
-	s.n_plain = (int)recs.size() - s.n_seg;
-	return s;
+	const Tiling t = tiling_of(p);
+	const void *segment_kernels[3];
+	for (int fmt = 0; fmt < 3; ++fmt)
+		with_variant(fmt, p.D, [&](auto format, auto degree) {
+			segment_kernels[fmt] = (const void *)vresample_segment_kernel<decltype(format)::value, decltype(degree)::value>;
+		});
+	return rs_core_create<Core>(kName, "the tile", p, t, t.tile_out > 0 && !WC_VR_FORCE_PLAIN, (size_t)p.P * p.taps * (p.D + 1),
+								[&](double *C) { build_table(p, C); }, segment_kernels);
 }
 
 // the records of a launch are on the device: those of the segment mapping, then those of the plain mapping
-int vr_enqueue(const Core &c, hipStream_t hs, const VrRec *d_rec, const Sorted &s, const void *x, int in_format, void *y, int out_format) {
+int vr_enqueue(const Core &c, hipStream_t hs, const VrRec *d_rec, const RsSorted &s, const void *x, int in_format, void *y, int out_format) {
 	VrArgs a = {};
 	a.x = x; a.y = y;
 	a.K = c.p.K; a.taps = c.p.taps; a.B = c.p.B;
 	a.tile_out = c.t.tile_out; a.span_max = c.t.span_max; a.out_format = out_format;
-	int rc;
-	if ((rc = c.dev->time_begin("vresample_kernels", hs))) return rc;
-	with_variant(in_format, c.p.D, [&](auto format, auto degree) {
-		constexpr int FMT = decltype(format)::value, D = decltype(degree)::value;
-		if (s.n_seg > 0) {
-			a.rec = d_rec; a.n_rec = s.n_seg;
-			hipLaunchKernelGGL((vresample_segment_kernel<FMT, D>), dim3((unsigned)s.blocks_seg), dim3(c.t.threads), (size_t)c.t.lds_bytes, hs, a, c.C.as<double>());
-		}
-		if (s.n_plain > 0) {
-			a.rec = d_rec + s.n_seg; a.n_rec = s.n_plain;
-			hipLaunchKernelGGL((vresample_plain_kernel<FMT, D>), dim3((unsigned)s.blocks_plain), dim3(kPlainBlock), 0, hs, a, c.C.as<double>());
-		}
+	return rs_timed(c, "vresample_kernels", hs, [&] {
+		with_variant(in_format, c.p.D, [&](auto format, auto degree) {
+			constexpr int FMT = decltype(format)::value, D = decltype(degree)::value;
+			rs_launch_pair(c, hs, a, d_rec, s, vresample_segment_kernel<FMT, D>, vresample_plain_kernel<FMT, D>);
+		});
 	});
-	WC_HIP(hipGetLastError());
-	return c.dev->time_end("vresample_kernels", hs);
 }
 
-bool format_ok(int in_format, int out_format) { return in_format >= 0 && in_format <= 2 && (out_format == 0 || out_format == 1); }
+// a stream's state: the rational streams' and the position (q, f) of its next output with its step
+struct State : RsStreamState {
+	long long q = 0;
+	unsigned f = 0;
+	u64 step = 0;
+	void rewind() {  // (the step stays)
+		RsStreamState::rewind();
+		q = 0; f = 0;
+	}
+};
 
 }  // namespace
 
-struct wc_vresampler {
-	Core *c = nullptr;
-	DevBuf drec;
-	HostBuf h_rec[2];  // a pair: a call waits for the copy of the call before the last only
-	int parity = 0;
-};
-
-struct wc_vresample_stream {
-	Core *c = nullptr;
-	int n_streams = 0, max_new = 0, max_out = 0;
-	long long cap = 0;  // doubles per buffer: 2K + max_new
-	struct Stream {
-		long long received = 0, committed = 0;
-		long long q = 0;  // the next output's position
-		unsigned f = 0;
-		u64 step = 0;
-		int parity = 0;  // the buffer whose head holds the history
-		bool flushed = false;
-	};
-	std::vector<Stream> st;
-	DevBuf buf;   // n_streams x 2 x cap
-	DevBuf drec;  // RsPush per stream with samples, then VrRec per stream with outputs
-	HostBuf h_rec[2];
-	int parity = 0;
-};
+struct wc_vresampler : RsBatch<Core> {};
+struct wc_vresample_stream : RsStreams<Core, State> {};
 
 extern "C" {
 
 int wc_vresample_plan(unsigned long long step_min, unsigned long long step_max, int zeros, double rolloff, double beta, int phase_bits,
 					  int degree, int *half_width, int *segments, int *degree_out, double *cutoff) {
 	Plan p;
-	if (const char *why = plan_of(step_min, step_max, zeros, rolloff, beta, phase_bits, degree, &p)) return fail(WC_ERR_INVALID, why);
+	const std::string why = plan_of(step_min, step_max, zeros, rolloff, beta, phase_bits, degree, &p);
+	if (!why.empty()) return fail(WC_ERR_INVALID, why);
 	if (half_width) *half_width = p.K;
 	if (segments) *segments = p.P;
 	if (degree_out) *degree_out = p.D;
-	if (cutoff) *cutoff = p.s;
+	if (cutoff) *cutoff = p.f.s;
 	return WC_OK;
 }
 
 int wc_vresample_filter(unsigned long long step_min, unsigned long long step_max, int zeros, double rolloff, double beta, int phase_bits,
 						int degree, double *table, long long capacity) {
 	Plan p;
-	if (const char *why = plan_of(step_min, step_max, zeros, rolloff, beta, phase_bits, degree, &p)) return fail(WC_ERR_INVALID, why);
+	const std::string why = plan_of(step_min, step_max, zeros, rolloff, beta, phase_bits, degree, &p);
+	if (!why.empty()) return fail(WC_ERR_INVALID, why);
 	if (!table || capacity < (long long)p.P * p.taps * (p.D + 1)) return fail(WC_ERR_INVALID, "vresample filter: the array holds fewer than P x (2K+1) x (D+1) doubles");
 	build_table(p, table);
 	return WC_OK;
@@ -540,10 +423,11 @@ long long wc_vresample_committed(long long q, unsigned int f, unsigned long long
 int wc_vresample_tiling(unsigned long long step_min, unsigned long long step_max, int zeros, double rolloff, int phase_bits, int degree,
 						int *tile_outputs, int *segment_min, int *plain_block) {
 	Plan p;
-	if (const char *why = plan_of(step_min, step_max, zeros, rolloff, 0.0, phase_bits, degree, &p)) return fail(WC_ERR_INVALID, why);
+	const std::string why = plan_of(step_min, step_max, zeros, rolloff, 0.0, phase_bits, degree, &p);
+	if (!why.empty()) return fail(WC_ERR_INVALID, why);
 	const Tiling t = tiling_of(p);
 	if (tile_outputs) *tile_outputs = t.tile_out;
-	if (segment_min) *segment_min = (int)t.seg_min;
+	if (segment_min) *segment_min = (int)t.tiled_min;
 	if (plain_block) *plain_block = kPlainBlock;
 	return WC_OK;
 }
@@ -552,106 +436,50 @@ int wc_vresample_tiling(unsigned long long step_min, unsigned long long step_max
 wc_vresampler *wc_vresampler_create(unsigned long long step_min, unsigned long long step_max, int zeros, double rolloff, double beta,
 									int phase_bits, int degree) {
 	Plan p;
-	if (const char *why = plan_of(step_min, step_max, zeros, rolloff, beta, phase_bits, degree, &p)) { set_error(why); return nullptr; }
-	Core *c = core_create(p);
-	if (!c) return nullptr;
-	wc_vresampler *r = new wc_vresampler();
-	r->c = c;
-	return r;
+	const std::string why = plan_of(step_min, step_max, zeros, rolloff, beta, phase_bits, degree, &p);
+	if (!why.empty()) { set_error(why); return nullptr; }
+	return rs_batch_create<wc_vresampler>(core_create(p));
 }
 
-void wc_vresampler_destroy(wc_vresampler *r) {
-	if (!r) return;
-	r->c->dev->quiesce();
-	r->drec.release(); r->h_rec[0].release(); r->h_rec[1].release();
-	core_destroy(r->c);
-	delete r;
-}
+void wc_vresampler_destroy(wc_vresampler *r) { rs_batch_destroy(r); }
 
 int wc_vresample_device(wc_vresampler *r, int n_utt, const void *d_x, int in_format, const int *x_length, const unsigned long long *step,
 						void *d_y, int out_format) {
-	if (!r || !x_length || !step || !d_x || !d_y) return fail(WC_ERR_INVALID, "vresample: null argument");
-	if (n_utt < 1) return fail(WC_ERR_INVALID, "vresample: n_utt must be at least 1");
-	if (!format_ok(in_format, out_format)) return fail(WC_ERR_INVALID, "vresample: in_format is 0, 1 or 2 and out_format 0 or 1");
-	const Core &c = *r->c;
-	DeviceLock lock(c.dev);
-	std::vector<VrRec> recs((size_t)n_utt);
-	long long x_off = 0, y_off = 0;
-	for (int u = 0; u < n_utt; ++u) {
-		if (x_length[u] < 1) return fail(WC_ERR_INVALID, "vresample: every length must be at least 1");
-		if (step[u] < c.p.step_min || step[u] > c.p.step_max) return fail(WC_ERR_INVALID, "vresample: a step outside the handle's [step_min, step_max]");
-		const long long n_out = out_length_of(step[u], x_length[u]);
-		if (n_out < 0 || y_off + n_out > INT_MAX) return fail(WC_ERR_INVALID, "vresample: the packed output exceeds 2^31 - 1 samples");
-		VrRec &q = recs[u];
-		q = VrRec();
-		q.x_off = x_off; q.y_off = y_off;
-		q.step = step[u];
-		q.lo = 0; q.hi = x_length[u];
-		q.n_out = (int)n_out;
-		x_off += x_length[u];
-		y_off += n_out;
-	}
-	// ---- no refusal is left ----
-	const size_t bytes = sizeof(VrRec) * (size_t)n_utt;
-	WC_HIP(hipSetDevice(c.dev->id));
-	hipStream_t hs = c.dev->active();
-	HostBuf &hb = r->h_rec[r->parity];
-	if (hb.reserve(bytes) || r->drec.reserve(bytes)) return WC_ERR_DEVICE;
-	const Sorted s = sort_records(c, recs, hb.as<VrRec>());
-	WC_HIP(hipMemcpyAsync(r->drec.p, hb.p, bytes, hipMemcpyHostToDevice, hs));
-	int rc;
-	if ((rc = hb.mark(hs))) return rc;
-	r->parity = 1 - r->parity;
-	return vr_enqueue(c, hs, r->drec.as<VrRec>(), s, d_x, in_format, d_y, out_format);
+	return rs_batch_run<VrRec>(
+		kName, r, x_length && step && d_x && d_y, n_utt, in_format, out_format, x_length,
+		[&](int u, VrRec &q, long long *n_out) -> const char * {
+			if (step[u] < r->c->p.step_min || step[u] > r->c->p.step_max) return ": a step outside the handle's [step_min, step_max]";
+			*n_out = out_length_of(step[u], x_length[u]);
+			q.step = step[u];
+			return nullptr;
+		},
+		[&](hipStream_t hs, const VrRec *d_rec, const RsSorted &s) { return vr_enqueue(*r->c, hs, d_rec, s, d_x, in_format, d_y, out_format); });
 }
 
 // ---- streams ------------------------------------------------------------------------------------------------------------------
 wc_vresample_stream *wc_vresample_stream_create(unsigned long long step_min, unsigned long long step_max, int zeros, double rolloff,
 												double beta, int phase_bits, int degree, int n_streams, int max_samples_per_push) {
-	if (n_streams < 1 || max_samples_per_push < 1) { set_error("vresample stream: n_streams and max_samples_per_push must be at least 1"); return nullptr; }
+	if (!rs_stream_counts_ok(kName, n_streams, max_samples_per_push)) return nullptr;
 	Plan p;
-	if (const char *why = plan_of(step_min, step_max, zeros, rolloff, beta, phase_bits, degree, &p)) { set_error(why); return nullptr; }
+	const std::string why = plan_of(step_min, step_max, zeros, rolloff, beta, phase_bits, degree, &p);
+	if (!why.empty()) { set_error(why); return nullptr; }
 	// a push's outputs lie in [pos, lim x 2^32) with pos >= (T_before - K) 2^32 and lim <= T_after: at most ceil((max + K) 2^32 / step_min)
 	const long long max_out = out_length_of(p.step_min, (long long)max_samples_per_push + p.K);
 	if (max_out < 0 || max_out > (long long)INT_MAX) { set_error("vresample stream: max_out_per_push leaves 31 bits"); return nullptr; }
-	Core *c = core_create(p);
-	if (!c) return nullptr;
-	DeviceLock lock(c->dev);
-	wc_vresample_stream *h = new wc_vresample_stream();
-	h->c = c;
-	h->n_streams = n_streams; h->max_new = max_samples_per_push; h->max_out = (int)max_out;
-	h->cap = 2ll * p.K + max_samples_per_push;
-	h->st.assign((size_t)n_streams, wc_vresample_stream::Stream());
-	for (auto &s : h->st) s.step = p.step_max;
-	const size_t rec = (sizeof(RsPush) + sizeof(VrRec)) * (size_t)n_streams;
-	if (h->buf.reserve(sizeof(double) * (size_t)n_streams * 2 * (size_t)h->cap) || h->drec.reserve(rec) || h->h_rec[0].reserve(rec) || h->h_rec[1].reserve(rec)) {
-		wc_vresample_stream_destroy(h);
-		return nullptr;
-	}
+	wc_vresample_stream *h = rs_stream_create<wc_vresample_stream, VrRec>(core_create(p), n_streams, max_samples_per_push, (int)max_out);
+	if (h)
+		for (State &s : h->st) s.step = p.step_max;
 	return h;
 }
 
-void wc_vresample_stream_destroy(wc_vresample_stream *h) {
-	if (!h) return;
-	h->c->dev->quiesce();
-	h->buf.release(); h->drec.release(); h->h_rec[0].release(); h->h_rec[1].release();
-	core_destroy(h->c);
-	delete h;
-}
+void wc_vresample_stream_destroy(wc_vresample_stream *h) { rs_stream_destroy(h); }
 
-int wc_vresample_stream_max_out_per_push(const wc_vresample_stream *h) { return h ? h->max_out : WC_ERR_INVALID; }
+int wc_vresample_stream_max_out_per_push(const wc_vresample_stream *h) { return rs_stream_max_out(h); }
 
-int wc_vresample_stream_reset(wc_vresample_stream *h, int stream) {
-	if (!h || stream < 0 || stream >= h->n_streams) return fail(WC_ERR_INVALID, "vresample stream: bad stream index");
-	DeviceLock lock(h->c->dev);
-	// (the history is not cleared: the records say how much of it exists)
-	wc_vresample_stream::Stream &s = h->st[stream];
-	s.received = 0; s.committed = 0; s.q = 0; s.f = 0; s.flushed = false;
-	return WC_OK;
-}
+int wc_vresample_stream_reset(wc_vresample_stream *h, int stream) { return rs_stream_reset(kName, h, stream); }
 
 int wc_vresample_stream_set_step(wc_vresample_stream *h, int stream, unsigned long long step) {
-	if (!h || stream < 0 || stream >= h->n_streams) return fail(WC_ERR_INVALID, "vresample stream: bad stream index");
+	if (!rs_stream_ok(h, stream)) return fail(WC_ERR_INVALID, "vresample stream: bad stream index");
 	if (step < h->c->p.step_min || step > h->c->p.step_max) return fail(WC_ERR_INVALID, "vresample stream: a step outside the handle's [step_min, step_max]");
 	DeviceLock lock(h->c->dev);
 	h->st[stream].step = step;
@@ -660,101 +488,31 @@ int wc_vresample_stream_set_step(wc_vresample_stream *h, int stream, unsigned lo
 
 int wc_vresample_stream_push_device(wc_vresample_stream *h, const void *d_chunk, int in_format, const int *n_new, const int *flush,
 									void *d_y, int out_format, int *samples_out) {
-	if (!h || !n_new || !samples_out) return fail(WC_ERR_INVALID, "vresample stream push: null argument");
-	if (!format_ok(in_format, out_format)) return fail(WC_ERR_INVALID, "vresample stream push: in_format is 0, 1 or 2 and out_format 0 or 1");
-	const Core &c = *h->c;
-	const Plan &p = c.p;
-	DeviceLock lock(c.dev);
-	const int n = h->n_streams, hist = 2 * p.K;
-	std::vector<long long> count((size_t)n);
-	long long total_in = 0, total_out = 0;
-	int n_push = 0;
-	for (int u = 0; u < n; ++u) {
-		const wc_vresample_stream::Stream &s = h->st[u];
-		if (n_new[u] < 0 || n_new[u] > h->max_new) return fail(WC_ERR_INVALID, "vresample stream push: a count outside 0 .. max_samples_per_push");
-		if (s.flushed && n_new[u] > 0) return fail(WC_ERR_INVALID, "vresample stream push: samples for a flushed stream (reset it first)");
-		const bool fl = s.flushed || (flush && flush[u]);
-		count[u] = count_of(s.q, s.f, s.step, p.K, s.received + n_new[u], fl);
-		if (count[u] < 0 || count[u] > h->max_out) return fail(WC_ERR_INVALID, "vresample stream push: the output count leaves max_out_per_push");
-		total_in += n_new[u];
-		total_out += count[u];
-		n_push += n_new[u] > 0 ? 1 : 0;
-	}
-	if ((total_in > 0 && !d_chunk) || (total_out > 0 && !d_y)) return fail(WC_ERR_INVALID, "vresample stream push: null array");
-	// ---- no refusal is left: the records ----
-	HostBuf &hb = h->h_rec[h->parity];
-	if (hb.reserve(0)) return WC_ERR_DEVICE;  // (the copy of the push before the last has read this staging)
-	RsPush *push = hb.as<RsPush>();
-	std::vector<VrRec> recs;
-	long long c_off = 0, y_off = 0;
-	int kp = 0, widen_blocks = 0;
-	for (int u = 0; u < n; ++u) {
-		const wc_vresample_stream::Stream &s = h->st[u];
-		const long long cur = ((long long)u * 2 + s.parity) * h->cap, other = ((long long)u * 2 + (1 - s.parity)) * h->cap;
-		if (n_new[u] > 0) {
-			RsPush &w = push[kp++];
-			w.c_off = c_off; w.cur_off = cur; w.other_off = other;
-			w.n_new = n_new[u]; w.block0 = widen_blocks;
-			widen_blocks += (n_new[u] + hist + kPlainBlock - 1) / kPlainBlock;
-		}
-		samples_out[u] = (int)count[u];  // (<= max_out)
-		if (count[u] > 0) {
-			// the buffer's double b is the stream's sample received - 2K + b; the first uncommitted output has q >= received - K
-			VrRec q = VrRec();
-			q.x_off = cur; q.y_off = y_off;
-			q.q0 = s.q - (s.received - hist);
+	return rs_stream_push<VrRec>(
+		kName, " stream push: the output count leaves max_out_per_push", h, d_chunk, in_format, n_new, flush, d_y, out_format, samples_out,
+		// the count: the outputs from the stream's position on, at its step, that the samples reach
+		[&](const State &s, long long T, bool flushed) {
+			const long long count = count_of(s.q, s.f, s.step, h->c->p.K, T, flushed);
+			return count > h->max_out ? -1 : count;
+		},
+		// the first output: the stream's position; the first uncommitted output has q >= received - K
+		[&](const State &s, VrRec &q) {
+			q.q0 = s.q - (s.received - 2 * h->c->p.K);
 			q.f0 = s.f;
 			q.step = s.step;
-			q.lo = s.received >= hist ? 0 : (int)(hist - s.received);
-			q.hi = hist + n_new[u];
-			q.n_out = (int)count[u];
-			recs.push_back(q);
-		}
-		c_off += n_new[u];
-		y_off += count[u];
-	}
-	WC_HIP(hipSetDevice(c.dev->id));
-	hipStream_t hs = c.dev->active();
-	if (n_push > 0 || !recs.empty()) {
-		VrRec *rec = reinterpret_cast<VrRec *>(push + n_push);
-		const Sorted so = sort_records(c, recs, rec);
-		const size_t bytes = sizeof(RsPush) * (size_t)n_push + sizeof(VrRec) * recs.size();
-		WC_HIP(hipMemcpyAsync(h->drec.p, hb.p, bytes, hipMemcpyHostToDevice, hs));
-		int rc;
-		if ((rc = hb.mark(hs))) return rc;
-		h->parity = 1 - h->parity;
-		if (n_push > 0) {
-			const RsPush *d_push = h->drec.as<RsPush>();
-			double *buf = h->buf.as<double>();
-			if (in_format == 0) hipLaunchKernelGGL(resample_widen_kernel<0>, dim3((unsigned)widen_blocks), dim3(kPlainBlock), 0, hs, d_push, n_push, d_chunk, buf, hist);
-			else if (in_format == 1) hipLaunchKernelGGL(resample_widen_kernel<1>, dim3((unsigned)widen_blocks), dim3(kPlainBlock), 0, hs, d_push, n_push, d_chunk, buf, hist);
-			else hipLaunchKernelGGL(resample_widen_kernel<2>, dim3((unsigned)widen_blocks), dim3(kPlainBlock), 0, hs, d_push, n_push, d_chunk, buf, hist);
-			WC_HIP(hipGetLastError());
-		}
-		if (!recs.empty()) {
-			const VrRec *d_rec = reinterpret_cast<const VrRec *>(h->drec.as<RsPush>() + n_push);
-			if ((rc = vr_enqueue(c, hs, d_rec, so, h->buf.p, 0, d_y, out_format))) return rc;
-		}
-	}
-	for (int u = 0; u < n; ++u) {
-		wc_vresample_stream::Stream &s = h->st[u];
-		const uwide pos = (((uwide)s.q << 32) | s.f) + (uwide)count[u] * s.step;
-		s.q = (long long)(pos >> 32);
-		s.f = (unsigned)pos;
-		s.received += n_new[u];
-		s.committed += count[u];
-		if (flush && flush[u]) s.flushed = true;
-		if (n_new[u] > 0) s.parity = 1 - s.parity;
-	}
-	return WC_OK;
+		},
+		// the position moves on by count x step
+		[](State &s, long long count) {
+			const uwide pos = (((uwide)s.q << 32) | s.f) + (uwide)count * s.step;
+			s.q = (long long)(pos >> 32);
+			s.f = (unsigned)pos;
+		},
+		[&](hipStream_t hs, const VrRec *d_rec, const RsSorted &s, const void *x) { return vr_enqueue(*h->c, hs, d_rec, s, x, 0, d_y, out_format); });
 }
 
-long long wc_vresample_stream_samples_received(const wc_vresample_stream *h, int stream) {
-	return h && stream >= 0 && stream < h->n_streams ? h->st[stream].received : -1;
-}
+long long wc_vresample_stream_samples_received(const wc_vresample_stream *h, int stream) { return rs_stream_received(h, stream); }
 
-long long wc_vresample_stream_samples_committed(const wc_vresample_stream *h, int stream) {
-	return h && stream >= 0 && stream < h->n_streams ? h->st[stream].committed : -1;
-}
+long long wc_vresample_stream_samples_committed(const wc_vresample_stream *h, int stream) { return rs_stream_committed(h, stream); }
 
 }  // extern "C"
+

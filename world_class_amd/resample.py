@@ -31,19 +31,25 @@ WAVE = 64  # outputs of one phase that a wavefront of the phase mapping takes
 IN_FORMATS = {"f64": (0, np.float64), "i16": (1, np.int16), "f32": (2, np.float32)}
 OUT_FORMATS = {"f64": (0, np.float64), "i16": (1, np.int16)}
 
-_bound = False
+
+def _binder(signatures):
+    """the library with a module's signatures bound on first use"""
+    done = []
+
+    def get():
+        L = lib()
+        if not done:
+            for name, (res, args) in signatures.items():
+                fn = getattr(L, name)
+                fn.restype = res
+                fn.argtypes = args
+            done.append(True)
+        return L
+
+    return get
 
 
-def _L():
-    global _bound
-    L = lib()
-    if not _bound:
-        for name, (res, args) in RESAMPLE_SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.restype = res
-            fn.argtypes = args
-        _bound = True
-    return L
+_L = _binder(RESAMPLE_SIGNATURES)
 
 
 def _count(n):
@@ -95,44 +101,23 @@ def _in_format(arrays):
     return "f64"
 
 
-class Resampler:
-    """whole signals from fs_in to fs_out: the rule of the header on the device"""
+class _Handle:
+    """a handle of either converter: _lib is its module's binder, _sym the prefix of its symbols, _kind what follows the prefix in
+    the names of its create and destroy"""
+    _lib = staticmethod(_L)
+    _sym = "wc_resample"
+    _kind = None
+    _h = None
 
-    def __init__(self, fs_in, fs_out, zeros=0, rolloff=0.0, beta=0.0):
-        self.fs_in, self.fs_out = int(fs_in), int(fs_out)
-        self._h = _handle(_L().wc_resampler_create(self.fs_in, self.fs_out, int(zeros), float(rolloff), float(beta)))
+    def _fn(self, name):
+        return getattr(self._lib(), self._sym + name)
 
-    def out_length(self, n):
-        return out_length(self.fs_in, self.fs_out, n)
-
-    def run_device(self, d_x, x_lengths, d_y, in_format="f64", out_format="f64"):
-        """packed device arrays in and out (utterance u's output at the sum of the out_length before it); enqueue-only"""
-        _check(_L().wc_resample_device(self._h, len(x_lengths), _opt(d_x), IN_FORMATS[in_format][0], _ints(x_lengths), _opt(d_y),
-                                       OUT_FORMATS[out_format][0]))
-
-    def run(self, xs, out_format="f64"):
-        """a list of 1-D host arrays (all int16, all float32, or anything else as float64) -> the list of their conversions"""
-        fmt = _in_format(xs)
-        xs = [np.ascontiguousarray(x, dtype=IN_FORMATS[fmt][1]).ravel() for x in xs]
-        if not xs or any(len(x) == 0 for x in xs):
-            raise ValueError("at least one signal, none of them empty")
-        lengths = [len(x) for x in xs]
-        outs = [self.out_length(n) for n in lengths]
-        odt = OUT_FORMATS[out_format][1]
-        d_x = DeviceArray.from_host(np.concatenate(xs), dtype=IN_FORMATS[fmt][1])
-        d_y = DeviceArray(sum(outs), dtype=odt)
-        try:
-            self.run_device(d_x, lengths, d_y, fmt, out_format)
-            y = d_y.to_host()  # (the copy waits for the stream)
-        finally:
-            d_x.free()
-            d_y.free()
-        cuts = np.cumsum(outs)[:-1]
-        return [part.copy() for part in np.split(y, cuts)]
+    def _create(self, *args):
+        self._h = _handle(self._fn(self._kind + "_create")(*args))
 
     def close(self):
         if self._h:
-            _L().wc_resampler_destroy(self._h)
+            self._fn(self._kind + "_destroy")(self._h)
             self._h = None
 
     def __del__(self):
@@ -142,39 +127,90 @@ class Resampler:
             pass
 
 
-class ResampleStream:
-    """n_streams concurrent signals from fs_in to fs_out, pushed piece by piece: the concatenated outputs of a stream are bit for
-    bit Resampler.run of its whole signal.  Output n is committed once its last tap has arrived (K samples of latency); the flush
-    adds the zero tail."""
+class _Batch(_Handle):
+    """the batch handle of either converter: the packing of host arrays around its run_device"""
+    _kind = "r"
 
-    def __init__(self, fs_in, fs_out, n_streams, max_samples, zeros=0, rolloff=0.0, beta=0.0):
+    def _device(self, d_x, x_lengths, extra, d_y, in_format, out_format):
+        _check(self._fn("_device")(self._h, len(x_lengths), _opt(d_x), IN_FORMATS[in_format][0], _ints(x_lengths), *extra, _opt(d_y),
+                                   OUT_FORMATS[out_format][0]))
+
+    @staticmethod
+    def _pack(xs):
+        """(the in_format name, the signals as contiguous arrays of its type)"""
+        fmt = _in_format(xs)
+        xs = [np.ascontiguousarray(x, dtype=IN_FORMATS[fmt][1]).ravel() for x in xs]
+        if not xs or any(len(x) == 0 for x in xs):
+            raise ValueError("at least one signal, none of them empty")
+        return fmt, xs
+
+    @staticmethod
+    def _run(fmt, xs, outs, out_format, run_device):
+        """the packed signals up, run_device(d_x, d_y), the outputs of lengths outs down"""
+        d_x = DeviceArray.from_host(np.concatenate(xs), dtype=IN_FORMATS[fmt][1])
+        d_y = DeviceArray(sum(outs), dtype=OUT_FORMATS[out_format][1])
+        try:
+            run_device(d_x, d_y)
+            y = d_y.to_host()  # (the copy waits for the stream)
+        finally:
+            d_x.free()
+            d_y.free()
+        cuts = np.cumsum(outs)[:-1]
+        return [part.copy() for part in np.split(y, cuts)]
+
+
+class Resampler(_Batch):
+    """whole signals from fs_in to fs_out: the rule of the header on the device"""
+
+    def __init__(self, fs_in, fs_out, zeros=0, rolloff=0.0, beta=0.0):
         self.fs_in, self.fs_out = int(fs_in), int(fs_out)
+        self._create(self.fs_in, self.fs_out, int(zeros), float(rolloff), float(beta))
+
+    def out_length(self, n):
+        return out_length(self.fs_in, self.fs_out, n)
+
+    def run_device(self, d_x, x_lengths, d_y, in_format="f64", out_format="f64"):
+        """packed device arrays in and out (utterance u's output at the sum of the out_length before it); enqueue-only"""
+        self._device(d_x, x_lengths, (), d_y, in_format, out_format)
+
+    def run(self, xs, out_format="f64"):
+        """a list of 1-D host arrays (all int16, all float32, or anything else as float64) -> the list of their conversions"""
+        fmt, xs = self._pack(xs)
+        lengths = [len(x) for x in xs]
+        return self._run(fmt, xs, [self.out_length(n) for n in lengths], out_format,
+                         lambda d_x, d_y: self.run_device(d_x, lengths, d_y, fmt, out_format))
+
+
+class _Stream(_Handle):
+    """the stream handle of either converter: everything but its create and what only one of them has"""
+    _kind = "_stream"
+
+    def _create(self, n_streams, max_samples, *plan):
         self.n_streams, self.max_samples = int(n_streams), int(max_samples)
-        self._h = _handle(_L().wc_resample_stream_create(self.fs_in, self.fs_out, int(zeros), float(rolloff), float(beta), self.n_streams,
-                                                         self.max_samples))
         self._out = {}  # the output arrays of push, by format: allocated on first use
+        super()._create(*plan, self.n_streams, self.max_samples)
 
     @property
     def max_out_per_push(self):
-        return int(_L().wc_resample_stream_max_out_per_push(self._h))
+        return int(self._fn("_stream_max_out_per_push")(self._h))
 
     def reset(self, stream):
-        _check(_L().wc_resample_stream_reset(self._h, int(stream)))
+        _check(self._fn("_stream_reset")(self._h, int(stream)))
 
     def samples_received(self, stream):
-        return int(_L().wc_resample_stream_samples_received(self._h, int(stream)))
+        return int(self._fn("_stream_samples_received")(self._h, int(stream)))
 
     def samples_committed(self, stream):
-        return int(_L().wc_resample_stream_samples_committed(self._h, int(stream)))
+        return int(self._fn("_stream_samples_committed")(self._h, int(stream)))
 
     def push_device(self, n_new, d_chunk, flush, d_y, in_format="f64", out_format="f64"):
         """device pointers in and out (packed by n_new and by the counts that come back); enqueue-only.  Returns samples_out"""
         if len(n_new) != self.n_streams or (flush is not None and len(flush) != self.n_streams):
             raise ValueError("one entry per stream")
         got = (C.c_int * self.n_streams)()
-        _check(_L().wc_resample_stream_push_device(self._h, _opt(d_chunk), IN_FORMATS[in_format][0], _ints(n_new),
-                                                   None if flush is None else _ints([1 if f else 0 for f in flush]), _opt(d_y),
-                                                   OUT_FORMATS[out_format][0], got))
+        _check(self._fn("_stream_push_device")(self._h, _opt(d_chunk), IN_FORMATS[in_format][0], _ints(n_new),
+                                               None if flush is None else _ints([1 if f else 0 for f in flush]), _opt(d_y),
+                                               OUT_FORMATS[out_format][0], got))
         return list(got)
 
     def push(self, chunks, flush=None, out_format="f64"):
@@ -200,15 +236,19 @@ class ResampleStream:
         return [part.copy() for part in np.split(y, cuts)]
 
     def close(self):
-        if self._h:
-            _L().wc_resample_stream_destroy(self._h)
-            self._h = None
+        super().close()
         for d in self._out.values():
             d.free()
         self._out = {}
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+
+class ResampleStream(_Stream):
+    """n_streams concurrent signals from fs_in to fs_out, pushed piece by piece: the concatenated outputs of a stream are bit for
+    bit Resampler.run of its whole signal.  Output n is committed once its last tap has arrived (K samples of latency); the flush
+    adds the zero tail."""
+
+    def __init__(self, fs_in, fs_out, n_streams, max_samples, zeros=0, rolloff=0.0, beta=0.0):
+        self.fs_in, self.fs_out = int(fs_in), int(fs_out)
+        self._create(n_streams, max_samples, self.fs_in, self.fs_out, int(zeros), float(rolloff), float(beta))
+
+

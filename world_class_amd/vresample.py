@@ -4,8 +4,8 @@ import ctypes as C
 
 import numpy as np
 
-from . import DeviceArray, _check, _handle, _ints, _opt, lib
-from .resample import IN_FORMATS, OUT_FORMATS, WAVE, _count, _in_format  # noqa: F401  (the formats are the rational converter's)
+from . import _check, _ints  # noqa: F401  (_ints: for raw calls through _L(), as the tests make them)
+from .resample import IN_FORMATS, OUT_FORMATS, WAVE, _Batch, _binder, _count, _Stream  # noqa: F401  (the formats are the rational converter's)
 
 _ip = C.POINTER(C.c_int)
 _vp = C.c_void_p
@@ -34,19 +34,7 @@ VRESAMPLE_SIGNATURES = {
 ONE = 1 << 32  # the step of ratio 1
 STEP_LO, STEP_HI = 1 << 28, 1 << 36
 
-_bound = False
-
-
-def _L():
-    global _bound
-    L = lib()
-    if not _bound:
-        for name, (res, args) in VRESAMPLE_SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.restype = res
-            fn.argtypes = args
-        _bound = True
-    return L
+_L = _binder(VRESAMPLE_SIGNATURES)
 
 
 def _step(step):
@@ -97,128 +85,47 @@ def tiling(step_min, step_max, zeros=0, rolloff=0.0, phase_bits=0, degree=0):
     return tuple(x.value for x in v)
 
 
-class VResampler:
+class VResampler(_Batch):
     """whole signals at a step each, anywhere in [step_min, step_max]: the rule of the header on the device"""
+    _lib = staticmethod(_L)
+    _sym = "wc_vresample"
 
     def __init__(self, step_min, step_max, zeros=0, rolloff=0.0, beta=0.0, phase_bits=0, degree=0):
         self.step_min, self.step_max = int(step_min), int(step_max)
-        self._h = _handle(_L().wc_vresampler_create(_step(step_min), _step(step_max), int(zeros), float(rolloff), float(beta),
-                                                    int(phase_bits), int(degree)))
+        self._create(_step(step_min), _step(step_max), int(zeros), float(rolloff), float(beta), int(phase_bits), int(degree))
 
     def run_device(self, d_x, x_lengths, steps, d_y, in_format="f64", out_format="f64"):
         """packed device arrays in and out (utterance u's output at the sum of the out_length before it); enqueue-only"""
         if len(steps) != len(x_lengths):
             raise ValueError("one step per utterance")
-        _check(_L().wc_vresample_device(self._h, len(x_lengths), _opt(d_x), IN_FORMATS[in_format][0], _ints(x_lengths),
-                                        (_u64 * len(steps))(*[_step(s) for s in steps]), _opt(d_y), OUT_FORMATS[out_format][0]))
+        self._device(d_x, x_lengths, ((_u64 * len(steps))(*[_step(s) for s in steps]),), d_y, in_format, out_format)
 
     def run(self, xs, steps, out_format="f64"):
         """a list of 1-D host arrays (all int16, all float32, or anything else as float64) and their steps (one int: the same for
         all) -> the list of their conversions"""
-        fmt = _in_format(xs)
-        xs = [np.ascontiguousarray(x, dtype=IN_FORMATS[fmt][1]).ravel() for x in xs]
-        if not xs or any(len(x) == 0 for x in xs):
-            raise ValueError("at least one signal, none of them empty")
+        fmt, xs = self._pack(xs)
         steps = [int(steps)] * len(xs) if np.isscalar(steps) else [int(s) for s in steps]
         if len(steps) != len(xs):
             raise ValueError("one step per utterance")
         lengths = [len(x) for x in xs]
-        outs = [out_length(s, n) for s, n in zip(steps, lengths)]
-        odt = OUT_FORMATS[out_format][1]
-        d_x = DeviceArray.from_host(np.concatenate(xs), dtype=IN_FORMATS[fmt][1])
-        d_y = DeviceArray(sum(outs), dtype=odt)
-        try:
-            self.run_device(d_x, lengths, steps, d_y, fmt, out_format)
-            y = d_y.to_host()  # (the copy waits for the stream)
-        finally:
-            d_x.free()
-            d_y.free()
-        cuts = np.cumsum(outs)[:-1]
-        return [part.copy() for part in np.split(y, cuts)]
-
-    def close(self):
-        if self._h:
-            _L().wc_vresampler_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._run(fmt, xs, [out_length(s, n) for s, n in zip(steps, lengths)], out_format,
+                         lambda d_x, d_y: self.run_device(d_x, lengths, steps, d_y, fmt, out_format))
 
 
-class VResampleStream:
+class VResampleStream(_Stream):
     """n_streams concurrent signals, pushed piece by piece, each at a step of its own that set_step moves between pushes (step_max
     after create).  With a constant step the concatenated outputs of a stream are bit for bit VResampler.run of its whole signal.  An
     output is committed once its last tap has arrived (K samples of latency); the flush adds the zero tail."""
+    _lib = staticmethod(_L)
+    _sym = "wc_vresample"
 
     def __init__(self, step_min, step_max, n_streams, max_samples, zeros=0, rolloff=0.0, beta=0.0, phase_bits=0, degree=0):
         self.step_min, self.step_max = int(step_min), int(step_max)
-        self.n_streams, self.max_samples = int(n_streams), int(max_samples)
-        self._h = _handle(_L().wc_vresample_stream_create(_step(step_min), _step(step_max), int(zeros), float(rolloff), float(beta),
-                                                          int(phase_bits), int(degree), self.n_streams, self.max_samples))
-        self._out = {}  # the output arrays of push, by format: allocated on first use
-
-    @property
-    def max_out_per_push(self):
-        return int(_L().wc_vresample_stream_max_out_per_push(self._h))
-
-    def reset(self, stream):
-        _check(_L().wc_vresample_stream_reset(self._h, int(stream)))
+        self._create(n_streams, max_samples, _step(step_min), _step(step_max), int(zeros), float(rolloff), float(beta), int(phase_bits),
+                     int(degree))
 
     def set_step(self, stream, step):
         """from the stream's next uncommitted output on, which keeps its position"""
-        _check(_L().wc_vresample_stream_set_step(self._h, int(stream), _step(step)))
+        _check(self._fn("_stream_set_step")(self._h, int(stream), _step(step)))
 
-    def samples_received(self, stream):
-        return int(_L().wc_vresample_stream_samples_received(self._h, int(stream)))
 
-    def samples_committed(self, stream):
-        return int(_L().wc_vresample_stream_samples_committed(self._h, int(stream)))
-
-    def push_device(self, n_new, d_chunk, flush, d_y, in_format="f64", out_format="f64"):
-        """device pointers in and out (packed by n_new and by the counts that come back); enqueue-only.  Returns samples_out"""
-        if len(n_new) != self.n_streams or (flush is not None and len(flush) != self.n_streams):
-            raise ValueError("one entry per stream")
-        got = (C.c_int * self.n_streams)()
-        _check(_L().wc_vresample_stream_push_device(self._h, _opt(d_chunk), IN_FORMATS[in_format][0], _ints(n_new),
-                                                    None if flush is None else _ints([1 if f else 0 for f in flush]), _opt(d_y),
-                                                    OUT_FORMATS[out_format][0], got))
-        return list(got)
-
-    def push(self, chunks, flush=None, out_format="f64"):
-        """chunks[u]: the new samples of stream u (None: none; all int16, all float32, or anything else as float64); flush[u]: the
-        stream ends here.  Returns the committed outputs per stream"""
-        if len(chunks) != self.n_streams:
-            raise ValueError("one entry per stream")
-        fmt = _in_format(chunks)
-        idt, odt = IN_FORMATS[fmt][1], OUT_FORMATS[out_format][1]
-        parts = [np.zeros(0, dtype=idt) if c is None else np.ascontiguousarray(c, dtype=idt).ravel() for c in chunks]
-        counts = [len(p) for p in parts]
-        if out_format not in self._out:
-            self._out[out_format] = DeviceArray(self.n_streams * self.max_out_per_push, dtype=odt)
-        d_y = self._out[out_format]
-        d = DeviceArray.from_host(np.concatenate(parts), dtype=idt) if sum(counts) else None
-        try:
-            got = self.push_device(counts, d, flush, d_y, fmt, out_format)
-            y = d_y.to_host()[:sum(got)] if sum(got) else np.zeros(0, dtype=odt)
-        finally:
-            if d is not None:
-                d.free()
-        cuts = np.cumsum(got)[:-1]
-        return [part.copy() for part in np.split(y, cuts)]
-
-    def close(self):
-        if self._h:
-            _L().wc_vresample_stream_destroy(self._h)
-            self._h = None
-        for d in self._out.values():
-            d.free()
-        self._out = {}
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
