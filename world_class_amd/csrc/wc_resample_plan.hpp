@@ -115,10 +115,10 @@ template <class Core> void rs_core_destroy(Core *c) {
 }
 
 // The table of a checked plan built (build(double *), n_table doubles) and uploaded, and more than 64 KB of local memory asked for
-// on the format variants of the tiled kernel; nullptr + error on failure.  tile_name: "the input tile" / "the tile".
-template <class Core, class Plan, class Tiling, class Build>
+// on the N variants of the tiled kernels; nullptr + error on failure.  tile_name: "the input tile" / "the tile".
+template <class Core, class Plan, class Tiling, class Build, size_t N>
 Core *rs_core_create(const char *name, const char *tile_name, const Plan &p, const Tiling &t, bool tiled, size_t n_table, Build build,
-					 const void *const (&tiled_kernels)[3]) {
+					 const void *const (&tiled_kernels)[N]) {
 	Device *dev = current_device();
 	if (!dev) return nullptr;
 	DeviceLock lock(dev);
@@ -140,8 +140,8 @@ Core *rs_core_create(const char *name, const char *tile_name, const Plan &p, con
 	if (tiled && bytes > 65536) {
 		int limit = 0;
 		bool ok = hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, dev->id) == hipSuccess && (size_t)limit >= bytes;
-		for (int fmt = 0; fmt < 3 && ok; ++fmt)
-			ok = hipFuncSetAttribute(tiled_kernels[fmt], hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
+		for (size_t k = 0; k < N && ok; ++k)
+			ok = hipFuncSetAttribute(tiled_kernels[k], hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
 		if (!ok) {
 			(void)hipGetLastError();
 			set_error(std::string(name) + ": the device grants " + std::to_string(limit) + " bytes of local memory per workgroup, " + tile_name + " needs " +
@@ -178,15 +178,15 @@ template <class Core, class Rec> RsSorted rs_sort_records(const Core &c, const s
 	return s;
 }
 
-// the sorted records are on the device: the tiled launch, then the plain launch
+// the sorted records are on the device: the tiled launch, then the plain launch (records without outputs take no block)
 template <class Core, class Args, class Rec>
 void rs_launch_pair(const Core &c, hipStream_t hs, Args a, const Rec *d_rec, const RsSorted &s, void (*tiled_kernel)(Args, const double *),
 					void (*plain_kernel)(Args, const double *)) {
-	if (s.n_tiled > 0) {
+	if (s.blocks_tiled > 0) {
 		a.rec = d_rec; a.n_rec = s.n_tiled;
 		hipLaunchKernelGGL(tiled_kernel, dim3((unsigned)s.blocks_tiled), dim3(c.t.threads), (size_t)c.t.lds_bytes, hs, a, c.table.template as<double>());
 	}
-	if (s.n_plain > 0) {
+	if (s.blocks_plain > 0) {
 		a.rec = d_rec + s.n_tiled; a.n_rec = s.n_plain;
 		hipLaunchKernelGGL(plain_kernel, dim3((unsigned)s.blocks_plain), dim3(kPlainBlock), 0, hs, a, c.table.template as<double>());
 	}

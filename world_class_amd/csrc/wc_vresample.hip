@@ -15,6 +15,9 @@
 //   order; a bucket may hold the whole tile (step = 2^32 keeps every output of a tile in one segment).
 //   Plain mapping (vresample_plain_kernel).  Adjacent lanes take adjacent outputs and read inputs and their own segment's rows from
 //   global memory.  It serves signals and pushes of fewer than segment_min outputs and plans whose tile would not fit the local memory.
+// Warping (include/world_class_warp.h) is the same rule at positions read from device memory, one per output: warp_segment_kernel and
+// warp_plain_kernel are the two mappings again, on the same tiling, sort (vr_sort_starts, vr_sort_place), task loop (vr_tasks) and vr_output, so at
+// the positions n x step they give wc_vresample_device's bits; warp_map_kernel turns frame-level time maps into such positions.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -22,7 +25,7 @@
 #include <cmath>
 #include <vector>
 
-#include "../../include/world_class_vresample.h"
+#include "../../include/world_class_warp.h"  // (with world_class_vresample.h)
 #include "wc_resample_plan.hpp"
 
 using namespace wc;
@@ -247,14 +250,78 @@ template <int FMT> struct VrGlobalIn {
 	__device__ __forceinline__ double at(int j) const { return i + j >= lo && i + j < hi ? rs_load<FMT>(x, x_off + i + j) : 0.0; }
 };
 
+// the local memory of a tile's block (tile_bytes)
+struct VrLds {
+	double *tile;           // span_max inputs
+	int *cnt;               // outputs per segment, then the buckets' fill
+	int *start;             // P + 1: a bucket's first place in the sorted tile
+	int *tstart;            // P + 1: and its first task
+	unsigned short *order;  // the sorted tile: every place's output
+};
+__device__ __forceinline__ VrLds vr_lds_of(double *base, int span_max) {
+	VrLds l;
+	l.tile = base;
+	l.cnt = reinterpret_cast<int *>(base + span_max);
+	l.start = l.cnt + kMaxSegments;
+	l.tstart = l.start + kMaxSegments + 1;
+	l.order = reinterpret_cast<unsigned short *>(l.tstart + kMaxSegments + 1);
+	return l;
+}
+
+// The counting sort of a tile's outputs by segment, in three steps with a barrier of the caller's behind each.  The count: cnt[s]
+// outputs fall into segment s.  The starts (one thread): a bucket's first place and first task out of the counts, which are zero
+// again afterwards.
+__device__ __forceinline__ void vr_sort_starts(const VrLds &l, int P) {
+	if (threadIdx.x == 0) {
+		int at = 0, task = 0;
+		for (int s = 0; s < P; ++s) {
+			const int n = l.cnt[s];
+			l.start[s] = at; l.tstart[s] = task;
+			at += n;
+			task += (n + kWave - 1) / kWave;
+			l.cnt[s] = 0;
+		}
+		l.start[P] = at; l.tstart[P] = task;
+	}
+}
+// The places: every output that was counted takes the next place of its bucket.  seg_of(k) is output k's segment; where not ALL
+// outputs were counted, a negative one leaves k out.
+template <bool ALL, class SegOf> __device__ __forceinline__ void vr_sort_place(const VrLds &l, int n_here, SegOf seg_of) {
+	for (int k = threadIdx.x; k < n_here; k += blockDim.x) {
+		const int s = seg_of(k);
+		if (ALL || s >= 0) l.order[l.start[s] + atomicAdd(&l.cnt[s], 1)] = (unsigned short)k;
+	}
+}
+// all three for a tile whose n_here outputs all take part, on counts that are zero and visible to the block
+template <class SegOf> __device__ __forceinline__ void vr_sort_tile(const VrLds &l, int P, int n_here, SegOf seg_of) {
+	for (int k = threadIdx.x; k < n_here; k += blockDim.x) atomicAdd(&l.cnt[seg_of(k)], 1);
+	__syncthreads();
+	vr_sort_starts(l, P);
+	__syncthreads();
+	vr_sort_place<true>(l, n_here, seg_of);
+	__syncthreads();
+}
+
+// The sorted tile's tasks: a wavefront takes 64 places of ONE bucket at a time.  body(seg, k, live): seg is wave-uniform, k the
+// output at the lane's place -- at lane 0's place, which lies inside the bucket, where the lane has none (live false).
+template <class Body> __device__ __forceinline__ void vr_tasks(const VrLds &l, int P, Body body) {
+	const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x / kWave), lane = threadIdx.x % kWave;
+	const int n_tasks = l.tstart[P];
+	int seg = 0;
+	for (int task = wave; task < n_tasks; task += blockDim.x / kWave) {
+		while (l.tstart[seg + 1] <= task) ++seg;
+		seg = __builtin_amdgcn_readfirstlane(seg);
+		const int first = __builtin_amdgcn_readfirstlane(l.start[seg] + (task - l.tstart[seg]) * kWave);
+		const int end = __builtin_amdgcn_readfirstlane(l.start[seg + 1]);
+		const bool live = first + lane < end;
+		body(seg, (int)l.order[live ? first + lane : first], live);
+	}
+}
+
 // (C apart from the other arguments and __restrict__: the coefficients of a wavefront's segment then come by scalar loads)
 template <int FMT, int D> __global__ __launch_bounds__(kSegThreadsWide) void vresample_segment_kernel(VrArgs a, const double *__restrict__ C) {
 	extern __shared__ double vr_lds[];
-	double *tile = vr_lds;
-	int *cnt = reinterpret_cast<int *>(tile + a.span_max);  // outputs per segment, then the buckets' fill
-	int *start = cnt + kMaxSegments;                        // P + 1: a bucket's first place in the sorted tile
-	int *tstart = start + kMaxSegments + 1;                 // P + 1: and its first task
-	unsigned short *order = reinterpret_cast<unsigned short *>(tstart + kMaxSegments + 1);
+	const VrLds l = vr_lds_of(vr_lds, a.span_max);
 	const int P = 1 << a.B;
 	const VrRec r = a.rec[rs_find(a.rec, a.n_rec, (int)blockIdx.x)];
 	const long long i_base = ((long long)blockIdx.x - r.block0) * a.tile_out;  // the tile's first output, counted from the record's first
@@ -266,52 +333,183 @@ template <int FMT, int D> __global__ __launch_bounds__(kSegThreadsWide) void vre
 	const int span = min((int)(q_last - q_first) + a.taps, a.span_max);  // (the host sized span_max for step_max: never less)
 	for (int idx = threadIdx.x; idx < span; idx += blockDim.x) {
 		const long long g = q_first - a.K + idx;
-		tile[idx] = g >= r.lo && g < r.hi ? rs_load<FMT>(a.x, r.x_off + g) : 0.0;
+		l.tile[idx] = g >= r.lo && g < r.hi ? rs_load<FMT>(a.x, r.x_off + g) : 0.0;
 	}
-	for (int s = threadIdx.x; s < P; s += blockDim.x) cnt[s] = 0;
+	for (int s = threadIdx.x; s < P; s += blockDim.x) l.cnt[s] = 0;
 	__syncthreads();
-	for (int k = threadIdx.x; k < n_here; k += blockDim.x) {
+	vr_sort_tile(l, P, n_here, [&](int k) {
 		long long q;
-		vr_pos(r, i_base + k, &q, &f);
-		atomicAdd(&cnt[vr_seg(f, a.B)], 1);
-	}
-	__syncthreads();
-	if (threadIdx.x == 0) {
-		int at = 0, task = 0;
-		for (int s = 0; s < P; ++s) {
-			const int n = cnt[s];
-			start[s] = at; tstart[s] = task;
-			at += n;
-			task += (n + kWave - 1) / kWave;
-			cnt[s] = 0;
-		}
-		start[P] = at; tstart[P] = task;
-	}
-	__syncthreads();
-	for (int k = threadIdx.x; k < n_here; k += blockDim.x) {
+		unsigned fk;
+		vr_pos(r, i_base + k, &q, &fk);
+		return vr_seg(fk, a.B);
+	});
+	vr_tasks(l, P, [&](int seg, int k, bool live) {
 		long long q;
-		vr_pos(r, i_base + k, &q, &f);
-		const int s = vr_seg(f, a.B);
-		order[start[s] + atomicAdd(&cnt[s], 1)] = (unsigned short)k;
-	}
-	__syncthreads();
-	const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x / kWave), lane = threadIdx.x % kWave;
-	const int n_tasks = tstart[P];
-	int seg = 0;
-	for (int task = wave; task < n_tasks; task += blockDim.x / kWave) {
-		while (tstart[seg + 1] <= task) ++seg;
-		seg = __builtin_amdgcn_readfirstlane(seg);
-		const int first = __builtin_amdgcn_readfirstlane(start[seg] + (task - tstart[seg]) * kWave);  // lane 0's place: inside the bucket
-		const int end = __builtin_amdgcn_readfirstlane(start[seg + 1]);
-		const bool live = first + lane < end;
-		const int k = order[live ? first + lane : first];
-		long long q;
-		vr_pos(r, i_base + k, &q, &f);
+		unsigned fk;
+		vr_pos(r, i_base + k, &q, &fk);
 		VrTileIn in;
-		in.at0 = tile + (int)(q - q_first);  // x[q - K]
-		const double v = vr_output<D>(in, C + (size_t)seg * a.taps * (D + 1), a.taps, vr_nu(f, a.B));
+		in.at0 = l.tile + (int)(q - q_first);  // x[q - K]
+		const double v = vr_output<D>(in, C + (size_t)seg * a.taps * (D + 1), a.taps, vr_nu(fk, a.B));
 		if (live) rs_store(a.y, a.out_format, r.y_off + i_base + k, v);
+	});
+}
+
+// ---- warping (include/world_class_warp.h): the same outputs at positions read from device memory --------------------------------------
+// A tile of the segment mapping does not know its input span in advance: the pass that counts its outputs by segment reduces the
+// lowest and highest q of its live outputs as well.  A near tile (the span fits span_max) then goes as vresample_segment_kernel's;
+// a far tile keeps the sort and reads x from global memory with bounds.  An output that is not live has every tap outside the
+// signal: it is +0.0 by the rule, takes no part in the sort, and no address is formed for it.  The positions are read three times,
+// by the counting pass, the placing pass and the tasks: in local memory they would take 8 bytes per output and halve the tile
+// (what the re-reads cost: DESIGN.md section 10, "Warping").
+struct WpArgs : VrArgs {
+	const long long *pos;  // packed like y
+};
+
+// output i of a record: (q, f) of its position and whether it is live (one tap at least inside the signal)
+__device__ __forceinline__ bool wp_pos(const WpArgs &a, const VrRec &r, long long i, long long *q, unsigned *f) {
+	const long long pos = a.pos[r.y_off + i];
+	*q = pos >> 32;
+	*f = (unsigned)pos;
+	return *q >= (long long)r.lo - a.K && *q <= (long long)r.hi - 1 + a.K;
+}
+
+// x of an output at q, read from global memory with the signal's bounds
+template <int FMT> __device__ __forceinline__ VrGlobalIn<FMT> wp_global_in(const WpArgs &a, const VrRec &r, long long q) {
+	VrGlobalIn<FMT> in;
+	in.x = a.x; in.x_off = r.x_off;
+	in.i = q - a.K;
+	in.lo = r.lo; in.hi = r.hi;
+	return in;
+}
+
+template <int FMT, int D> __global__ __launch_bounds__(kSegThreadsWide) void warp_segment_kernel(WpArgs a, const double *__restrict__ C) {
+	extern __shared__ double vr_lds[];
+	const VrLds l = vr_lds_of(vr_lds, a.span_max);
+	const int P = 1 << a.B;
+	const VrRec r = a.rec[rs_find(a.rec, a.n_rec, (int)blockIdx.x)];
+	const long long i_base = ((long long)blockIdx.x - r.block0) * a.tile_out;
+	const int n_here = (int)min((long long)a.tile_out, (long long)r.n_out - i_base);
+	const int wave = (int)threadIdx.x / kWave, lane = threadIdx.x % kWave, n_waves = blockDim.x / kWave;
+	for (int s = threadIdx.x; s < P; s += blockDim.x) l.cnt[s] = 0;
+	__syncthreads();
+	// one pass over the positions counts the live outputs by segment, writes the others' +0.0 and finds the live ones' lowest and
+	// highest q: per lane, per wavefront, then one exchange where the sorted tile will stand
+	long long q_min = LLONG_MAX, q_max = LLONG_MIN;
+	for (int k = threadIdx.x; k < n_here; k += blockDim.x) {
+		long long q;
+		unsigned f;
+		if (wp_pos(a, r, i_base + k, &q, &f)) {
+			q_min = min(q_min, q);
+			q_max = max(q_max, q);
+			atomicAdd(&l.cnt[vr_seg(f, a.B)], 1);
+		} else {
+			rs_store(a.y, a.out_format, r.y_off + i_base + k, 0.0);
+		}
 	}
+	for (int d = kWave / 2; d > 0; d >>= 1) {
+		q_min = min(q_min, __shfl_xor(q_min, d));
+		q_max = max(q_max, __shfl_xor(q_max, d));
+	}
+	long long *ends = reinterpret_cast<long long *>(l.order);  // (8-byte aligned: span_max is even; 2 x 16 of them in 256 places and more)
+	if (lane == 0) {
+		ends[2 * wave] = q_min;
+		ends[2 * wave + 1] = q_max;
+	}
+	__syncthreads();
+	for (int w = 0; w < n_waves; ++w) {
+		q_min = min(q_min, ends[2 * w]);
+		q_max = max(q_max, ends[2 * w + 1]);
+	}
+	if (q_min > q_max) return;  // no live output (the whole block leaves)
+	vr_sort_starts(l, P);
+	const bool near = __builtin_amdgcn_readfirstlane((int)(q_max - q_min + a.taps <= (long long)a.span_max)) != 0;
+	const int span = near ? (int)(q_max - q_min) + a.taps : 0;
+	for (int idx = threadIdx.x; idx < span; idx += blockDim.x) {
+		const long long g = q_min - a.K + idx;
+		l.tile[idx] = g >= r.lo && g < r.hi ? rs_load<FMT>(a.x, r.x_off + g) : 0.0;
+	}
+	__syncthreads();  // (every thread has read the ends)
+	vr_sort_place<false>(l, n_here, [&](int k) {
+		long long q;
+		unsigned f;
+		return wp_pos(a, r, i_base + k, &q, &f) ? vr_seg(f, a.B) : -1;
+	});
+	__syncthreads();
+	// (only live outputs stand in the sorted tile)  in_at(q): where the tile keeps x[q - K] and the taps behind it
+	const auto run = [&](auto in_at) {
+		vr_tasks(l, P, [&](int seg, int k, bool live) {
+			long long q;
+			unsigned f;
+			wp_pos(a, r, i_base + k, &q, &f);
+			const double v = vr_output<D>(in_at(q), C + (size_t)seg * a.taps * (D + 1), a.taps, vr_nu(f, a.B));
+			if (live) rs_store(a.y, a.out_format, r.y_off + i_base + k, v);
+		});
+	};
+	if (near) {
+		run([&](long long q) {
+			VrTileIn in;
+			in.at0 = l.tile + (int)(q - q_min);
+			return in;
+		});
+	} else {
+		run([&](long long q) { return wp_global_in<FMT>(a, r, q); });
+	}
+}
+
+template <int FMT, int D> __global__ __launch_bounds__(kPlainBlock) void warp_plain_kernel(WpArgs a, const double *__restrict__ C) {
+	const VrRec r = a.rec[rs_find(a.rec, a.n_rec, (int)blockIdx.x)];
+	const long long i = ((long long)blockIdx.x - r.block0) * kPlainBlock + threadIdx.x;
+	if (i >= r.n_out) return;
+	long long q;
+	unsigned f;
+	if (!wp_pos(a, r, i, &q, &f)) {
+		rs_store(a.y, a.out_format, r.y_off + i, 0.0);
+		return;
+	}
+	rs_store(a.y, a.out_format, r.y_off + i, vr_output<D>(wp_global_in<FMT>(a, r, q), C + (size_t)vr_seg(f, a.B) * a.taps * (D + 1), a.taps, vr_nu(f, a.B)));
+}
+
+// THE map rule (world_class_warp.h), on the host and on the device: every operation in double and rounded apart
+constexpr long long kNoPosition = LLONG_MIN;
+__host__ __device__ inline long long wm_position(const double *map, int L, double out_per_entry, double in_per_unit, long long n) {
+#pragma clang fp contract(off)
+	const double t = (double)n / out_per_entry;
+	double v;
+	if (t >= (double)(L - 1)) {
+		v = map[L - 1];
+	} else {
+		const double fl = floor(t);
+		const int i = (int)fl;
+		const double w = t - fl;
+		if (w == 0.0) {
+			v = map[i];
+		} else {
+			const double d = map[i + 1] - map[i];
+			const double wd = w * d;
+			v = map[i] + wd;
+		}
+	}
+	const double p = v * in_per_unit;
+	if (!(p >= -1073741824.0 && p < 1073741824.0)) return kNoPosition;  // (a NaN and the infinities fail the comparisons)
+	return (long long)floor(p * 4294967296.0);
+}
+
+// a record's x_off, hi and y_off are its map's first entry, its length and its first position; a record of the tiled group counts
+// its blocks in tiles of `sub` blocks of the plain size (rs_sort_records), and every thread still takes one output
+struct WmArgs {
+	const VrRec *rec;
+	int n_rec;
+	const double *map;
+	long long *pos;
+	double out_per_entry, in_per_unit;
+	int sub;
+};
+__global__ __launch_bounds__(kPlainBlock) void warp_map_kernel(WmArgs a) {
+	const int b = (int)blockIdx.x / a.sub;
+	const VrRec r = a.rec[rs_find(a.rec, a.n_rec, b)];
+	const long long i = (((long long)b - r.block0) * a.sub + (int)blockIdx.x % a.sub) * kPlainBlock + threadIdx.x;
+	if (i >= r.n_out) return;
+	a.pos[r.y_off + i] = wm_position(a.map + r.x_off, r.hi, a.out_per_entry, a.in_per_unit, i);
 }
 
 template <int FMT, int D> __global__ __launch_bounds__(kPlainBlock) void vresample_plain_kernel(VrArgs a, const double *__restrict__ C) {
@@ -343,10 +541,11 @@ typedef RsCore<Plan, Tiling> Core;
 // the table built and uploaded for a checked plan; nullptr + error on failure
 Core *core_create(const Plan &p) {
 	const Tiling t = tiling_of(p);
-	const void *segment_kernels[3];
+	const void *segment_kernels[6];  // the converter's and the warp's
 	for (int fmt = 0; fmt < 3; ++fmt)
 		with_variant(fmt, p.D, [&](auto format, auto degree) {
 			segment_kernels[fmt] = (const void *)vresample_segment_kernel<decltype(format)::value, decltype(degree)::value>;
+			segment_kernels[3 + fmt] = (const void *)warp_segment_kernel<decltype(format)::value, decltype(degree)::value>;
 		});
 	return rs_core_create<Core>(kName, "the tile", p, t, t.tile_out > 0 && !WC_VR_FORCE_PLAIN, (size_t)p.P * p.taps * (p.D + 1),
 								[&](double *C) { build_table(p, C); }, segment_kernels);
@@ -365,6 +564,41 @@ int vr_enqueue(const Core &c, hipStream_t hs, const VrRec *d_rec, const RsSorted
 		});
 	});
 }
+
+// the warp's launch: the same records (their position fields unused) and the positions, packed like y
+int wp_enqueue(const Core &c, hipStream_t hs, const VrRec *d_rec, const RsSorted &s, const void *x, int in_format, const long long *pos, void *y,
+			   int out_format) {
+	WpArgs a = {};
+	a.x = x; a.y = y; a.pos = pos;
+	a.K = c.p.K; a.taps = c.p.taps; a.B = c.p.B;
+	a.tile_out = c.t.tile_out; a.span_max = c.t.span_max; a.out_format = out_format;
+	return rs_timed(c, "warp_kernels", hs, [&] {
+		with_variant(in_format, c.p.D, [&](auto format, auto degree) {
+			constexpr int FMT = decltype(format)::value, D = decltype(degree)::value;
+			rs_launch_pair(c, hs, a, d_rec, s, warp_segment_kernel<FMT, D>, warp_plain_kernel<FMT, D>);
+		});
+	});
+}
+
+// the map kernel over both groups of records: one thread per output in blocks of the plain size
+int wm_enqueue(const Core &c, hipStream_t hs, const VrRec *d_rec, const RsSorted &s, const double *map, double out_per_entry, double in_per_unit,
+			   long long *pos) {
+	WmArgs a = {};
+	a.map = map; a.pos = pos;
+	a.out_per_entry = out_per_entry; a.in_per_unit = in_per_unit;
+	return rs_timed(c, "warp_map_kernel", hs, [&] {
+		if (s.blocks_tiled > 0) {
+			a.rec = d_rec; a.n_rec = s.n_tiled; a.sub = c.t.tile_out / kPlainBlock;
+			hipLaunchKernelGGL(warp_map_kernel, dim3((unsigned)s.blocks_tiled * (unsigned)a.sub), dim3(kPlainBlock), 0, hs, a);
+		}
+		if (s.blocks_plain > 0) {
+			a.rec = d_rec + s.n_tiled; a.n_rec = s.n_plain; a.sub = 1;
+			hipLaunchKernelGGL(warp_map_kernel, dim3((unsigned)s.blocks_plain), dim3(kPlainBlock), 0, hs, a);
+		}
+	});
+}
+
+bool wm_scale_ok(double v) { return std::isfinite(v) && v > 0.0; }
 
 // a stream's state: the rational streams' and the position (q, f) of its next output with its step
 struct State : RsStreamState {
@@ -513,6 +747,62 @@ int wc_vresample_stream_push_device(wc_vresample_stream *h, const void *d_chunk,
 long long wc_vresample_stream_samples_received(const wc_vresample_stream *h, int stream) { return rs_stream_received(h, stream); }
 
 long long wc_vresample_stream_samples_committed(const wc_vresample_stream *h, int stream) { return rs_stream_committed(h, stream); }
+
+// ---- warping (world_class_warp.h) -----------------------------------------------------------------------------------------------
+int wc_warp_tiling(unsigned long long step_min, unsigned long long step_max, int zeros, double rolloff, int phase_bits, int degree,
+				   int *tile_outputs, int *span_max, int *segment_min, int *plain_block) {
+	Plan p;
+	const std::string why = plan_of(step_min, step_max, zeros, rolloff, 0.0, phase_bits, degree, &p);
+	if (!why.empty()) return fail(WC_ERR_INVALID, why);
+	const Tiling t = tiling_of(p);  // the converter's own: at arithmetic positions both kernels cut the same tiles
+	if (tile_outputs) *tile_outputs = t.tile_out;
+	if (span_max) *span_max = t.tile_out ? t.span_max : (int)tile_span(p, kTileMin);
+	if (segment_min) *segment_min = (int)t.tiled_min;
+	if (plain_block) *plain_block = kPlainBlock;
+	return WC_OK;
+}
+
+long long wc_warp_map_out_length(int map_length, double out_per_entry) {
+	if (map_length < 1) return fail(WC_ERR_INVALID, "warp map: a map holds one entry at least");
+	if (!wm_scale_ok(out_per_entry)) return fail(WC_ERR_INVALID, "warp map: out_per_entry must be finite and positive");
+	const double last = std::floor((double)(map_length - 1) * out_per_entry);
+	if (!(last < 4611686018427387904.0)) return fail(WC_ERR_INVALID, "warp map: the output length leaves 62 bits");
+	return (long long)last + 1;
+}
+
+int wc_warp_map_positions(const double *map, int map_length, double out_per_entry, double in_per_unit, long long n_out, long long *pos) {
+	if (!map || !pos) return fail(WC_ERR_INVALID, "warp map: null argument");
+	if (map_length < 1 || n_out < 0) return fail(WC_ERR_INVALID, "warp map: a map holds one entry at least and n_out is not negative");
+	if (!wm_scale_ok(out_per_entry) || !wm_scale_ok(in_per_unit)) return fail(WC_ERR_INVALID, "warp map: out_per_entry and in_per_unit must be finite and positive");
+	for (long long n = 0; n < n_out; ++n) pos[n] = wm_position(map, map_length, out_per_entry, in_per_unit, n);
+	return WC_OK;
+}
+
+int wc_warp_device(wc_vresampler *r, int n_utt, const void *d_x, int in_format, const int *x_length, const long long *d_pos,
+				   const int *out_length, void *d_y, int out_format) {
+	return rs_batch_run<VrRec>(
+		"warp", r, x_length && out_length && d_x && d_pos && d_y, n_utt, in_format, out_format, x_length,
+		[&](int u, VrRec &, long long *n_out) -> const char * {
+			if (out_length[u] < 0) return ": an output length below 0";
+			*n_out = out_length[u];
+			return nullptr;
+		},
+		[&](hipStream_t hs, const VrRec *d_rec, const RsSorted &s) { return wp_enqueue(*r->c, hs, d_rec, s, d_x, in_format, d_pos, d_y, out_format); });
+}
+
+int wc_warp_map_positions_device(wc_vresampler *r, int n_utt, const double *d_map, const int *map_length, double out_per_entry,
+								 double in_per_unit, const int *out_length, long long *d_pos) {
+	if (!wm_scale_ok(out_per_entry) || !wm_scale_ok(in_per_unit)) return fail(WC_ERR_INVALID, "warp map: out_per_entry and in_per_unit must be finite and positive");
+	// (the records of a batch of signals: a map is the input, its length the record's hi)
+	return rs_batch_run<VrRec>(
+		"warp map", r, map_length && out_length && d_map && d_pos, n_utt, 0, 0, map_length,
+		[&](int u, VrRec &, long long *n_out) -> const char * {
+			if (out_length[u] < 0) return ": an output length below 0";
+			*n_out = out_length[u];
+			return nullptr;
+		},
+		[&](hipStream_t hs, const VrRec *d_rec, const RsSorted &s) { return wm_enqueue(*r->c, hs, d_rec, s, d_map, out_per_entry, in_per_unit, d_pos); });
+}
 
 }  // extern "C"
 
