@@ -55,6 +55,8 @@ struct D4cArgs {
 	const int *uidx;  // [total_frames] utterance of every frame (d4c_lt_count_kernel): the one-wavefront kernels read it instead of bisecting
 	int rare_only;  // (unused)
 	int *rare_list;  // [0]: count, then the gated frames the one-wavefront kernels leave to the block kernel
+	int *lt_list;  // [0]: count, then the voiced frames whose LoveTrain window exceeds 2048 samples (d4c_lt_count_kernel); NULL: d4c2_lovetrain_kernel<true> on a grid of every frame
+	unsigned int *band_tails;  // NULL, or the count of d4c2_band_kernel<3>'s wavefronts that entered the 64-bit tail of the search (WC_D4C_BAND_TAILS=1: the tests)
 };
 
 // F0-adaptive window of reference src/d4c.cpp:246-303 for the calling block; each thread keeps its
@@ -203,13 +205,17 @@ __host__ __device__ __forceinline__ bool d4c2_can(double f0, int fs) {
 // number of draws of one frame's LoveTrain window / of its three D4C windows
 __global__ void d4c_lt_count_kernel(const double *__restrict__ f0, long long total, int fs, uint32_t *__restrict__ cnt,
 									const UttDesc *__restrict__ utts, int n_utt, int *__restrict__ uidx, int *__restrict__ long_cnt,
-									int *__restrict__ rare_cnt) {
+									int *__restrict__ rare_cnt, int *__restrict__ lt_list) {
 	long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
 	if (g >= total) return;
 	if (g == 0) { *long_cnt = 0; *rare_cnt = 0; }
 	uidx[g] = find_utt(utts, n_utt, g);  // (looked up once here rather than by every frame's wavefront, a chain of dependent loads each)
 	double f = f0[g];
-	cnt[g] = (f == 0.0) ? 0u : (uint32_t)(2 * mround(3.0 * fs / fmax(f, 40.0) / 2.0) + 1);
+	const uint32_t wl = (f == 0.0) ? 0u : (uint32_t)(2 * mround(3.0 * fs / fmax(f, 40.0) / 2.0) + 1);
+	cnt[g] = wl;
+	// the frames of d4c2_lovetrain_kernel<true> (its own is_long).  Their count was zeroed on the stream in front of this launch
+	// (a reset by thread 0 here is not ordered against the other blocks' appends); the order of the list reaches no result.
+	if (lt_list && wl > 2048u) lt_list[1 + atomicAdd(lt_list, 1)] = (int)g;
 }
 
 template <int N, int T>
@@ -843,12 +849,8 @@ __device__ __forceinline__ int d4c2_groups(int wl) { return wl > 2048 ? 4 : (wl 
 // halves of the transform; LONG = true: the others (F0 below 70 Hz at 48 kHz), window formed per half.  Every frame is done by
 // exactly one of the two launches.
 template <bool LONG>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WC_D4C2_LT_OCC, WC_D4C2_LT_OCC))) void d4c2_lovetrain_kernel(D4cArgs a) {
+__device__ __forceinline__ void d4c2_lovetrain_frame(const D4cArgs &a, long long g, double *L, int lane) {
 	constexpr int N = 4096, M = 2048;
-	__shared__ __attribute__((aligned(16))) double L[kWfLds];
-	const int lane = threadIdx.x;
-	const long long g = xcd_frame(blockIdx.x, a.total_frames);
-	if (g >= a.total_frames) return;
 	const int bins_out = a.fft_size_out / 2 + 1;
 	double *__restrict__ row = a.ap + g * (long long)bins_out;
 	const double f0v = a.f0[g];
@@ -909,6 +911,29 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WC_D4C2_LT_O
 	if (!gate) {
 		const double init_val = 1.0 - kSafe;
 		for (int k = lane; k < bins_out; k += 64) row[k] = init_val;
+	}
+}
+// <true> by default walks the list d4c_lt_count_kernel left (a.lt_list) on a grid sized for the chip: a contour out of Harvest has
+// next to no frame below 70 Hz, and a grid of every frame whose blocks all leave at once is a launch of 64 k workgroups for nothing
+// (see d4c2_frames_kernel<true>).  WC_D4C_LT_LIST=0 (a.lt_list == NULL): the grid of every frame, the A/B and bit-identity twin.
+template <bool LONG>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WC_D4C2_LT_OCC, WC_D4C2_LT_OCC))) void d4c2_lovetrain_kernel(D4cArgs a) {
+	__shared__ __attribute__((aligned(16))) double L[kWfLds];
+	const int lane = threadIdx.x;
+	if constexpr (!LONG) {
+		const long long g = xcd_frame(blockIdx.x, a.total_frames);
+		if (g >= a.total_frames) return;
+		d4c2_lovetrain_frame<false>(a, g, L, lane);
+	} else {
+		// (one copy of the frame's code for both grids: without a list every block has the one frame of its own index)
+		const bool listed = a.lt_list != nullptr;
+		const unsigned int n = listed ? (unsigned int)a.lt_list[0] : gridDim.x;
+#pragma unroll 1
+		for (unsigned int i = blockIdx.x; i < n; i += gridDim.x) {
+			const long long g = listed ? (long long)a.lt_list[1 + i] : xcd_frame(i, a.total_frames);
+			if (g < a.total_frames) d4c2_lovetrain_frame<true>(a, g, L, lane);
+			wf_fence();
+		}
 	}
 }
 
@@ -1325,9 +1350,23 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WC_D4C2_OCC,
 #ifndef WC_D4C2_BAND_PF
 #define WC_D4C2_BAND_PF 0
 #endif
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WC_D4C2_BAND_OCC, WC_D4C2_BAND_OCC))) void d4c2_band_kernel(D4cArgs a) {
+// WAVES = 3: the same kernel at THREE wavefronts per SIMD (168 VGPRs, no scratch, 13 312 B of LDS of the 13 653 that twelve wavefronts
+// per CU leave each): the same grid, arithmetic, order and bits with a smaller live set.  Forced to three the compiler alone spills 156
+// registers; what it takes by hand:
+//   the second stage's twiddles (60 VGPRs across the first exchange of either transform) come from 4 KB of LDS behind the exchange
+//     buffer, copied once per wavefront (wf_t2_to_lds): the same values into the same wrot;
+//   each half's samples are asked for right in front of its transform -- through an opaque lane index, or the second half's loads
+//     are hoisted over the first transform;
+//   each half's keys are formed where they are written -- through opaque values, or the compiler sinks them below the other half's
+//     first stage and holds re[] and im[], 64 VGPRs, until then.
+// WAVES = 2 is the form of rounds 4-6 and the twin (WC_D4C_BAND_WAVES=2; WC_D4C_SELECT=64 always runs on it).
+template <int WAVES>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES == 3 ? 3 : WC_D4C2_BAND_OCC, WAVES == 3 ? 3 : WC_D4C2_BAND_OCC))) void d4c2_band_kernel(D4cArgs a) {
 	constexpr int N = 4096, M = 2048;
-	__shared__ __attribute__((aligned(16))) double L[kWfLds];
+	constexpr bool W3 = WAVES == 3;
+	__shared__ __attribute__((aligned(16))) double L[kWfLds + (W3 ? kWfT2Lds : 0)];
+	const double *T2 = W3 ? L + kWfLds : nullptr;
+	if constexpr (W3) __builtin_assume(T2 != nullptr);  // (so that wf_fft1024_dit_rest_p's `if (T2)` is decided when it is compiled)
 	const int lane = threadIdx.x;
 	const int n_ap = a.n_ap;
 	const long long blk = xcd_frame(blockIdx.x, (long long)gridDim.x);
@@ -1336,6 +1375,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WC_D4C2_BAND
 	if (g >= a.total_frames) return;
 	const double f0v = a.f0[g];
 	if (f0v == 0.0 || a.ap0[g] <= a.threshold) return;
+	if constexpr (W3) wf_t2_to_lds(L + kWfLds, a.tw, lane);  // (the first exchange orders these writes before the first look-up)
 	const double f0 = fmax(47.0, f0v);
 	const int fs = a.fs;
 	const int wln = a.window_length, hwl = wln / 2;  // <= 1023 samples = 512 packed points: slots 0 .. 7
@@ -1346,15 +1386,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WC_D4C2_BAND
 	const int ng = wln > 512 ? 2 : 1;
 	double key[2][16], keyM = 0.0;
 	[[maybe_unused]] double pf = 0.0;
-#pragma unroll
-	for (int odd = 0; odd < 2; ++odd) {
+	auto half = [&](auto parity) {
+		constexpr int odd = decltype(parity)::value;
 		// the packed windowed group delay, elements lane + 64 q (read again for the second half rather than held across the first)
 		double re[16], im[16], nyq;
+		int ln = lane;
+		if constexpr (W3) WC_FRESH(ln);
 		{
 			double sv[16], nv[16];
 #pragma unroll
 			for (int k = 0; k < 16; ++k) {
-				const int i = min(2 * lane + 128 * (k >> 1) + (k & 1), wln - 1);
+				const int i = min(2 * ln + 128 * (k >> 1) + (k & 1), wln - 1);
 				sv[k] = src[i];
 				nv[k] = a.nuttall[i];
 			}
@@ -1374,22 +1416,27 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WC_D4C2_BAND
 			for (int q = 0; q < 16; ++q) {
 				re[q] = im[q] = 0.0;
 				if (q < 8) {
-					const int i0 = 2 * lane + 128 * q;
+					const int i0 = 2 * ln + 128 * q;
 					re[q] = (i0 < wln) ? sv[2 * q] * nv[2 * q] : 0.0;
 					im[q] = (i0 + 1 < wln) ? sv[2 * q + 1] * nv[2 * q + 1] : 0.0;
 				}
 			}
 		}
-		if (odd) wf_odd_twist(re, im, a.tw, lane, 8);
+		if (odd) wf_odd_twist(re, im, a.tw, ln, 8);
 		if (ng == 1) wdft16<+1, 1>(re, im);
 		else wdft16<+1, 2>(re, im);
-		wf_fft1024_dit_rest_p<+1>(re, im, L, a.tw, lane, odd);
-		if (odd) wf_r2c_unpack_odd(re, im, a.tw, lane);
-		else wf_r2c_unpack(re, im, nyq, a.tw, lane);  // 2 X: a common factor of all powers
+		wf_fft1024_dit_rest_p<+1>(re, im, L, a.tw, ln, odd, T2);
+		if (odd) wf_r2c_unpack_odd(re, im, a.tw, ln);
+		else wf_r2c_unpack(re, im, nyq, a.tw, ln);  // 2 X: a common factor of all powers
 #pragma unroll
-		for (int s = 0; s < 16; ++s) key[odd][s] = fma(re[s], re[s], im[s] * im[s]);
+		for (int s = 0; s < 16; ++s) {
+			key[odd][s] = fma(re[s], re[s], im[s] * im[s]);
+			if constexpr (W3) WC_FRESH(key[odd][s]);
+		}
 		if (!odd) keyM = nyq * nyq;  // lane 0
-	}
+	};
+	half(std::integral_constant<int, 0>());
+	half(std::integral_constant<int, 1>());
 	// largest key
 	double mx = (lane == 0) ? keyM : 0.0;
 #pragma unroll
@@ -1399,7 +1446,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WC_D4C2_BAND
 	mx = uniform_d(mx);
 	long long lo = -1, hi = __double_as_longlong(mx);
 	unsigned int c_lo = 0;
-	if (!a.select64) {
+	if (W3 || !a.select64) {  // (select64 never reaches the three-wavefront form)
 		// The same search on the keys' HIGH words first (round 6): a threshold (h, 0xFFFFFFFF) has a key at or below it exactly when the
 		// key's high word is at most h -- a 32-bit compare per key and step instead of a 64-bit one, on registers that are there anyway.
 		// It ends with exactly K keys below a threshold (nearly always: two neighbours of the ranking share a high word only when they
@@ -1451,6 +1498,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WC_D4C2_BAND
 			hi = cand > 0 && c >= K ? cand : hi;  // (more than K below: the K-th smallest is at or below cand)
 		}
 	}
+	if constexpr (W3)
+		if (a.band_tails && lane == 0 && hi - lo > 1 && c_lo != K) atomicAdd(a.band_tails, 1u);  // (the tests: this wavefront enters the 64-bit search)
 	for (int it = 0; it < 64 && hi - lo > 1 && c_lo != K; ++it) {
 		const long long mid = lo + ((hi - lo) >> 1);
 		unsigned int c = (unsigned int)__popcll(__ballot(lane == 0 && __double_as_longlong(keyM) <= mid));
@@ -1903,11 +1952,14 @@ struct wc_d4c {
 	int fs, fft_size_d4c, fft_size_lt, n_ap, window_length;
 	double threshold;
 	bool select64 = false;  // WC_D4C_SELECT=64 (D4cArgs::select64)
+	int band_waves = 3;  // N = 4096 band stage: d4c2_band_kernel<3> at three wavefronts per SIMD (default), WC_D4C_BAND_WAVES=2: <2>, its twin (select64 always takes the twin)
+	bool lt_listed = true;  // d4c2_lovetrain_kernel<true> walks a list of its frames (default); WC_D4C_LT_LIST=0: a grid of every frame (the A/B and bit-identity twin)
+	bool count_tails = false;  // WC_D4C_BAND_TAILS=1: count the band wavefronts that enter the 64-bit tail of the search (wc_debug_d4c_band_tails)
 	bool split;  // band loop and row output as separate kernels (default; WC_D4C_SPLIT=0: one fused kernel)
 	bool wave2;  // 4096-point transforms by two wavefronts per frame (d4c2_*; default where they apply, WC_D4C_IMPL=block: never)
 	Device *dev;
 	double f0_bound = 0.0;  // (a caller's promise about the contour's highest F0: no longer relied on -- the frames the wavefront kernels leave out are listed on the device)
-	DevBuf nuttall, utts, cnt, uidx, long_list, rare_list, off, endpos, endpos2, ap0, sgd, coarse, d_x, d_tpos, d_f0, d_ap;
+	DevBuf nuttall, utts, cnt, uidx, long_list, rare_list, lt_list, tails, off, endpos, endpos2, ap0, sgd, coarse, d_x, d_tpos, d_f0, d_ap;
 	HostBuf h_stage, h_rows, h_x;
 };
 
@@ -1983,8 +2035,18 @@ int d4c_enqueue(wc_d4c *d, hipStream_t s, int n_utt, const double *d_x, const in
 	WC_HIP(hipMemcpyAsync(d->utts.p, d->h_stage.p, sizeof(UttDesc) * n_utt, hipMemcpyHostToDevice, s));
 	if ((rc = d->h_stage.mark(s))) return rc;
 	const unsigned grid1 = (unsigned)((total + 255) / 256);
+	// LoveTrain's long-window frames are listed by the count kernel itself: the list's count is zeroed here, in front of it
+	const bool lt_listed = d->lt_listed && d->wave2 && d->fft_size_lt == 4096;
+	if (lt_listed) {
+		if ((rc = d->lt_list.reserve(sizeof(int) * (total + 1)))) return rc;  // [0]: the count
+		WC_HIP(hipMemsetAsync(d->lt_list.p, 0, sizeof(int), s));
+	}
+	if (d->count_tails) {
+		if ((rc = d->tails.reserve(sizeof(unsigned int)))) return rc;
+		WC_HIP(hipMemsetAsync(d->tails.p, 0, sizeof(unsigned int), s));
+	}
 	hipLaunchKernelGGL(d4c_lt_count_kernel, dim3(grid1), dim3(256), 0, s, d_f0, total, d->fs, d->cnt.as<uint32_t>(), d->utts.as<UttDesc>(), n_utt,
-					   d->uidx.as<int>(), d->long_list.as<int>(), d->rare_list.as<int>());
+					   d->uidx.as<int>(), d->long_list.as<int>(), d->rare_list.as<int>(), lt_listed ? d->lt_list.as<int>() : nullptr);
 	hipLaunchKernelGGL(utt_scan_kernel, dim3(n_utt), dim3(256), 0, s, d->cnt.as<uint32_t>(), d->utts.as<UttDesc>(),
 					   d_start, d->off.as<unsigned long long>(), d->endpos.as<unsigned long long>());
 	D4cArgs a;
@@ -1996,12 +2058,14 @@ int d4c_enqueue(wc_d4c *d, hipStream_t s, int n_utt, const double *d_x, const in
 	a.n_ap = d->n_ap; a.window_length = d->window_length; a.threshold = d->threshold; a.select64 = d->select64 ? 1 : 0;
 	a.rare_only = 0;
 	a.rare_list = d->rare_list.as<int>();
+	a.lt_list = lt_listed ? d->lt_list.as<int>() : nullptr;
+	a.band_tails = d->count_tails ? d->tails.as<unsigned int>() : nullptr;
 	a.sgd_stride = main2 ? row2 : (long long)(d->fft_size_d4c / 2 + 1);
 	const long long blocks8 = ((total + 7) / 8) * 8;
 	if ((rc = dev->time_begin("d4c_lovetrain", s))) return rc;
 	if (d->wave2 && d->fft_size_lt == 4096) {
 		hipLaunchKernelGGL(d4c2_lovetrain_kernel<false>, dim3((unsigned)blocks8), dim3(64), 0, s, a);
-		hipLaunchKernelGGL(d4c2_lovetrain_kernel<true>, dim3((unsigned)blocks8), dim3(64), 0, s, a);
+		hipLaunchKernelGGL(d4c2_lovetrain_kernel<true>, dim3((unsigned)(lt_listed ? std::min<long long>(blocks8, 4096) : blocks8)), dim3(64), 0, s, a);
 	} else if (d->wave2 && d->fft_size_lt == 2048) {
 		hipLaunchKernelGGL(d4c1_lovetrain_kernel, dim3((unsigned)blocks8), dim3(64), 0, s, a);
 	}
@@ -2035,7 +2099,8 @@ int d4c_enqueue(wc_d4c *d, hipStream_t s, int n_utt, const double *d_x, const in
 			a.rare_only = 0;
 		} else if (main2 && part == 1) {
 			if (a.n_ap > 0) {
-				if (d->fft_size_d4c == 4096) hipLaunchKernelGGL(d4c2_band_kernel, dim3((unsigned)(blocks8 * a.n_ap)), dim3(64), 0, s, a);
+				if (d->fft_size_d4c == 4096 && d->band_waves == 3 && !d->select64) hipLaunchKernelGGL(d4c2_band_kernel<3>, dim3((unsigned)(blocks8 * a.n_ap)), dim3(64), 0, s, a);
+				else if (d->fft_size_d4c == 4096) hipLaunchKernelGGL(d4c2_band_kernel<2>, dim3((unsigned)(blocks8 * a.n_ap)), dim3(64), 0, s, a);
 				else hipLaunchKernelGGL(d4c1_band_kernel, dim3((unsigned)(blocks8 * a.n_ap)), dim3(64), 0, s, a);
 			}
 			hipLaunchKernelGGL(d4c_rows_kernel, dim3((unsigned)a.total_frames), dim3(256), 0, s, a);
@@ -2063,6 +2128,67 @@ int d4c_enqueue(wc_d4c *d, hipStream_t s, int n_utt, const double *d_x, const in
 		if (FILE *f = fopen(path, "wb")) { fwrite(out.data(), 8, out.size(), f); fclose(f); }
 	}
 #endif
+	return WC_OK;
+}
+
+// the band wavefronts of the handle's last call that entered the 64-bit tail of the search (handles created under WC_D4C_BAND_TAILS=1)
+extern "C" int wc_debug_d4c_band_tails(wc_d4c *d, unsigned int *tails) {
+	if (!d || !tails || !d->count_tails || !d->tails.p) return fail(WC_ERR_INVALID, "d4c: no tail count on this handle");
+	WC_HIP(hipSetDevice(d->dev->id));
+	DeviceLock lock(d->dev);
+	WC_HIP(hipStreamSynchronize(d->dev->active()));
+	WC_HIP(hipMemcpy(tails, d->tails.p, sizeof(unsigned int), hipMemcpyDeviceToHost));
+	return WC_OK;
+}
+
+// the length of the list the handle's last call left for d4c2_lovetrain_kernel<true> (-1: that call built none)
+extern "C" int wc_debug_d4c_lt_listed(wc_d4c *d, int *n) {
+	if (!d || !n) return fail(WC_ERR_INVALID, "d4c: null argument");
+	*n = -1;
+	if (!(d->lt_listed && d->wave2 && d->fft_size_lt == 4096) || !d->lt_list.p) return WC_OK;
+	WC_HIP(hipSetDevice(d->dev->id));
+	DeviceLock lock(d->dev);
+	WC_HIP(hipStreamSynchronize(d->dev->active()));
+	WC_HIP(hipMemcpy(n, d->lt_list.p, sizeof(int), hipMemcpyDeviceToHost));
+	return WC_OK;
+}
+
+// Development / test hook (not part of include/world_class_c.h): the N = 4096 band stage alone, in the form the handle would launch
+// (WC_D4C_BAND_WAVES, WC_D4C_SELECT), on group-delay rows the caller makes up -- rows[n_frames][2049] (host), every frame voiced at
+// 100 Hz and past the gate; coarse[n_frames][5] (host) receives the bands' values.  With rows whose band segments are an impulse all
+// keys of a band share their high word: the one input that is certain to send the selection into its 64-bit tail.
+extern "C" int wc_debug_d4c_bands(wc_d4c *d, int n_frames, const double *rows, double *coarse) {
+	if (!d || n_frames <= 0 || !rows || !coarse) return fail(WC_ERR_INVALID, "d4c: null argument");
+	if (d->fft_size_d4c != 4096 || d->window_length > 1023 || d->n_ap <= 0) return fail(WC_ERR_UNSUPPORTED, "d4c: no 4096-point band stage at this rate");
+	constexpr long long row = 2049;
+	WC_HIP(hipSetDevice(d->dev->id));
+	DeviceLock lock(d->dev);
+	hipStream_t s = d->dev->active();
+	int rc;
+	const long long blocks8 = ((n_frames + 7) / 8) * 8;
+	if ((rc = d->sgd.reserve(sizeof(double) * (size_t)(n_frames * row)))) return rc;
+	if ((rc = d->coarse.reserve(sizeof(double) * (size_t)n_frames * kMaxBands))) return rc;
+	if ((rc = d->d_f0.reserve(sizeof(double) * (size_t)n_frames))) return rc;
+	if ((rc = d->ap0.reserve(sizeof(double) * (size_t)n_frames))) return rc;
+	std::vector<double> f0((size_t)n_frames, 100.0), ap0((size_t)n_frames, 2.0);
+	WC_HIP(hipMemcpy(d->sgd.p, rows, sizeof(double) * (size_t)(n_frames * row), hipMemcpyHostToDevice));
+	WC_HIP(hipMemcpy(d->d_f0.p, f0.data(), sizeof(double) * (size_t)n_frames, hipMemcpyHostToDevice));
+	WC_HIP(hipMemcpy(d->ap0.p, ap0.data(), sizeof(double) * (size_t)n_frames, hipMemcpyHostToDevice));
+	WC_HIP(hipMemsetAsync(d->coarse.p, 0, sizeof(double) * (size_t)n_frames * kMaxBands, s));
+	if (d->count_tails) {
+		if ((rc = d->tails.reserve(sizeof(unsigned int)))) return rc;
+		WC_HIP(hipMemsetAsync(d->tails.p, 0, sizeof(unsigned int), s));
+	}
+	D4cArgs a = {};
+	a.f0 = d->d_f0.as<double>(); a.ap0 = d->ap0.as<double>(); a.threshold = 1.0; a.tw = d->dev->twiddle;
+	a.sgd = d->sgd.as<double>(); a.sgd_stride = row; a.coarse = d->coarse.as<double>(); a.nuttall = d->nuttall.as<double>();
+	a.total_frames = n_frames; a.fs = d->fs; a.n_ap = d->n_ap; a.window_length = d->window_length; a.select64 = d->select64 ? 1 : 0;
+	a.band_tails = d->count_tails ? d->tails.as<unsigned int>() : nullptr;
+	if (d->band_waves == 3 && !d->select64) hipLaunchKernelGGL(d4c2_band_kernel<3>, dim3((unsigned)(blocks8 * a.n_ap)), dim3(64), 0, s, a);
+	else hipLaunchKernelGGL(d4c2_band_kernel<2>, dim3((unsigned)(blocks8 * a.n_ap)), dim3(64), 0, s, a);
+	WC_HIP(hipGetLastError());
+	WC_HIP(hipStreamSynchronize(s));
+	WC_HIP(hipMemcpy(coarse, d->coarse.p, sizeof(double) * (size_t)n_frames * kMaxBands, hipMemcpyDeviceToHost));
 	return WC_OK;
 }
 
@@ -2118,6 +2244,12 @@ wc_d4c *wc_d4c_create(int fs, double threshold) {
 		d->split = !(sp && sp[0] == '0');
 		const char *sel = getenv("WC_D4C_SELECT");
 		d->select64 = sel && std::strcmp(sel, "64") == 0;
+		const char *bw = getenv("WC_D4C_BAND_WAVES");
+		if (bw && (std::strcmp(bw, "2") == 0 || std::strcmp(bw, "3") == 0)) d->band_waves = bw[0] - '0';
+		const char *ll = getenv("WC_D4C_LT_LIST");
+		d->lt_listed = !(ll && ll[0] == '0');
+		const char *ct = getenv("WC_D4C_BAND_TAILS");
+		d->count_tails = ct && ct[0] == '1';
 		const char *impl = getenv("WC_D4C_IMPL");
 		d->wave2 = !(impl && std::strcmp(impl, "block") == 0);
 	}
@@ -2152,7 +2284,7 @@ void wc_d4c_destroy(wc_d4c *d) {
 	if (!d) return;
 	d->dev->quiesce();
 	d->dev->handle_gone();
-	d->nuttall.release(); d->utts.release(); d->cnt.release(); d->uidx.release(); d->long_list.release(); d->rare_list.release(); d->off.release(); d->endpos.release(); d->endpos2.release();
+	d->nuttall.release(); d->utts.release(); d->cnt.release(); d->uidx.release(); d->long_list.release(); d->rare_list.release(); d->lt_list.release(); d->tails.release(); d->off.release(); d->endpos.release(); d->endpos2.release();
 	d->ap0.release(); d->sgd.release(); d->coarse.release(); d->d_x.release(); d->d_tpos.release(); d->d_f0.release(); d->d_ap.release(); d->h_stage.release(); d->h_rows.release(); d->h_x.release();
 	delete d;
 }
