@@ -18,6 +18,9 @@
 // Warping (include/world_class_warp.h) is the same rule at positions read from device memory, one per output: warp_segment_kernel and
 // warp_plain_kernel are the two mappings again, on the same tiling, sort (vr_sort_starts, vr_sort_place), task loop (vr_tasks) and vr_output, so at
 // the positions n x step they give wc_vresample_device's bits; warp_map_kernel turns frame-level time maps into such positions.
+// Where the positions come from is a template argument of the two kernels: an array (wc_warp_device), or the map rule evaluated
+// where the array would have been read (include/world_class_warp_stream.h: wc_warp_along_map_device and the warp streams, whose
+// pushes are that call's records with a first output and a first entry of their own).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -25,7 +28,7 @@
 #include <cmath>
 #include <vector>
 
-#include "../../include/world_class_warp.h"  // (with world_class_vresample.h)
+#include "../../include/world_class_warp_stream.h"  // (with world_class_warp.h and world_class_vresample.h)
 #include "wc_resample_plan.hpp"
 
 using namespace wc;
@@ -192,14 +195,15 @@ struct VrRec {
 	int block0;       // the record's first block in its launch
 	int pad_;
 };
-struct VrArgs {
-	const VrRec *rec;
+template <class Rec> struct VrArgsOf {
+	const Rec *rec;
 	int n_rec;
 	const void *x;
 	void *y;
 	int K, taps, B;
 	int tile_out, span_max, out_format;
 };
+typedef VrArgsOf<VrRec> VrArgs;
 
 // (i < 2^31 and the step's low word < 2^32: the product stays inside 64 bits)
 __device__ __forceinline__ void vr_pos(const VrRec &r, long long i, long long *q, unsigned *f) {
@@ -360,21 +364,97 @@ template <int FMT, int D> __global__ __launch_bounds__(kSegThreadsWide) void vre
 // a far tile keeps the sort and reads x from global memory with bounds.  An output that is not live has every tap outside the
 // signal: it is +0.0 by the rule, takes no part in the sort, and no address is formed for it.  The positions are read three times,
 // by the counting pass, the placing pass and the tasks: in local memory they would take 8 bytes per output and halve the tile
-// (what the re-reads cost: DESIGN.md section 10, "Warping").
+// (what the re-reads cost: DESIGN.md section 10, "Warping").  With the map as the source each of the three is the map rule
+// evaluated again -- three divisions that do not show beside the taps, on entries that stay in the caches (section 10, "Warp
+// streams").
+
+// THE map rule (world_class_warp.h), on the host and on the device: every operation in double and rounded apart.  entry(i) is map
+// entry i, 0 <= i < L, from one of the sources below; i and n are 64-bit, since a stream counts both from its reset.
+constexpr long long kNoPosition = LLONG_MIN;
+template <class Entry> __host__ __device__ inline long long wm_position(Entry entry, long long L, double out_per_entry, double in_per_unit, long long n) {
+#pragma clang fp contract(off)
+	const double t = (double)n / out_per_entry;
+	double v;
+	if (t >= (double)(L - 1)) {
+		v = entry(L - 1);
+	} else {
+		const double fl = floor(t);
+		const long long i = (long long)fl;
+		const double w = t - fl;
+		if (w == 0.0) {
+			v = entry(i);
+		} else {
+			const double d = entry(i + 1) - entry(i);
+			const double wd = w * d;
+			v = entry(i) + wd;
+		}
+	}
+	const double p = v * in_per_unit;
+	if (!(p >= -1073741824.0 && p < 1073741824.0)) return kNoPosition;  // (a NaN and the infinities fail the comparisons)
+	return (long long)floor(p * 4294967296.0);
+}
+// The sources of an entry.  An array: the whole map.  A stream's push: the entry the stream carries -- the last one an earlier push
+// consumed, entry first - 1, which is all a push reads below its own -- in front of the push's new entries, fresh[0] being entry
+// `first`.  A stream's flush: the same with the tail's remaining entries as the new ones.  (A whole map is the second with first 0.)
+struct WmArray {
+	const double *map;
+	__host__ __device__ double operator()(long long i) const { return map[i]; }
+};
+struct WmCarried {
+	const double *carried, *fresh;
+	long long first;
+	__host__ __device__ double operator()(long long i) const { return i < first ? *carried : fresh[i - first]; }
+};
+
 struct WpArgs : VrArgs {
 	const long long *pos;  // packed like y
+	__device__ __forceinline__ long long position(const VrRec &r, long long i) const { return pos[r.y_off + i]; }
+	__device__ __forceinline__ bool keeps(int, int) const { return false; }
+};
+
+// The map source.  A record is one utterance of wc_warp_along_map_device or one stream's share of a push or flush: output i of the
+// record is output n0 + i of a map of L entries.
+struct WmRec : VrRec {
+	long long map_off;  // element of the entries that holds entry `first`
+	long long first;    // the record's first new entry; an entry below it is the carried one
+	long long L;
+	long long n0;
+	double out_per_entry, in_per_unit;
+	int carry;          // where the carried entry stands
+	int pad2_;
+};
+// an entry that a push carries on: the last one it consumed, to the stream's other place
+struct WsKeep {
+	long long from;  // element of the entries
+	int to, pad_;
+};
+struct WsArgs : VrArgsOf<WmRec> {
+	const double *map;  // the new entries
+	double *carry;      // the streams' carried entries: a pair each, of which a push reads one and writes the other
+	const WsKeep *keep;
+	int n_keep, keep_block0;  // the plain launch's blocks from keep_block0 on keep the n_keep entries and form no output
+	__device__ __forceinline__ long long position(const WmRec &r, long long i) const {
+		const WmCarried entry = {carry + r.carry, map + r.map_off, r.first};
+		return wm_position(entry, r.L, r.out_per_entry, r.in_per_unit, r.n0 + i);
+	}
+	__device__ __forceinline__ bool keeps(int block, int thread) const {
+		if (block < keep_block0) return false;
+		const int k = (block - keep_block0) * kPlainBlock + thread;
+		if (k < n_keep) carry[keep[k].to] = map[keep[k].from];
+		return true;
+	}
 };
 
 // output i of a record: (q, f) of its position and whether it is live (one tap at least inside the signal)
-__device__ __forceinline__ bool wp_pos(const WpArgs &a, const VrRec &r, long long i, long long *q, unsigned *f) {
-	const long long pos = a.pos[r.y_off + i];
+template <class Args, class Rec> __device__ __forceinline__ bool wp_pos(const Args &a, const Rec &r, long long i, long long *q, unsigned *f) {
+	const long long pos = a.position(r, i);
 	*q = pos >> 32;
 	*f = (unsigned)pos;
 	return *q >= (long long)r.lo - a.K && *q <= (long long)r.hi - 1 + a.K;
 }
 
 // x of an output at q, read from global memory with the signal's bounds
-template <int FMT> __device__ __forceinline__ VrGlobalIn<FMT> wp_global_in(const WpArgs &a, const VrRec &r, long long q) {
+template <int FMT, class Args> __device__ __forceinline__ VrGlobalIn<FMT> wp_global_in(const Args &a, const VrRec &r, long long q) {
 	VrGlobalIn<FMT> in;
 	in.x = a.x; in.x_off = r.x_off;
 	in.i = q - a.K;
@@ -382,11 +462,11 @@ template <int FMT> __device__ __forceinline__ VrGlobalIn<FMT> wp_global_in(const
 	return in;
 }
 
-template <int FMT, int D> __global__ __launch_bounds__(kSegThreadsWide) void warp_segment_kernel(WpArgs a, const double *__restrict__ C) {
+template <int FMT, int D, class Args> __global__ __launch_bounds__(kSegThreadsWide) void warp_segment_kernel(Args a, const double *__restrict__ C) {
 	extern __shared__ double vr_lds[];
 	const VrLds l = vr_lds_of(vr_lds, a.span_max);
 	const int P = 1 << a.B;
-	const VrRec r = a.rec[rs_find(a.rec, a.n_rec, (int)blockIdx.x)];
+	const auto r = a.rec[rs_find(a.rec, a.n_rec, (int)blockIdx.x)];
 	const long long i_base = ((long long)blockIdx.x - r.block0) * a.tile_out;
 	const int n_here = (int)min((long long)a.tile_out, (long long)r.n_out - i_base);
 	const int wave = (int)threadIdx.x / kWave, lane = threadIdx.x % kWave, n_waves = blockDim.x / kWave;
@@ -456,8 +536,9 @@ template <int FMT, int D> __global__ __launch_bounds__(kSegThreadsWide) void war
 	}
 }
 
-template <int FMT, int D> __global__ __launch_bounds__(kPlainBlock) void warp_plain_kernel(WpArgs a, const double *__restrict__ C) {
-	const VrRec r = a.rec[rs_find(a.rec, a.n_rec, (int)blockIdx.x)];
+template <int FMT, int D, class Args> __global__ __launch_bounds__(kPlainBlock) void warp_plain_kernel(Args a, const double *__restrict__ C) {
+	if (a.keeps((int)blockIdx.x, (int)threadIdx.x)) return;
+	const auto r = a.rec[rs_find(a.rec, a.n_rec, (int)blockIdx.x)];
 	const long long i = ((long long)blockIdx.x - r.block0) * kPlainBlock + threadIdx.x;
 	if (i >= r.n_out) return;
 	long long q;
@@ -467,31 +548,6 @@ template <int FMT, int D> __global__ __launch_bounds__(kPlainBlock) void warp_pl
 		return;
 	}
 	rs_store(a.y, a.out_format, r.y_off + i, vr_output<D>(wp_global_in<FMT>(a, r, q), C + (size_t)vr_seg(f, a.B) * a.taps * (D + 1), a.taps, vr_nu(f, a.B)));
-}
-
-// THE map rule (world_class_warp.h), on the host and on the device: every operation in double and rounded apart
-constexpr long long kNoPosition = LLONG_MIN;
-__host__ __device__ inline long long wm_position(const double *map, int L, double out_per_entry, double in_per_unit, long long n) {
-#pragma clang fp contract(off)
-	const double t = (double)n / out_per_entry;
-	double v;
-	if (t >= (double)(L - 1)) {
-		v = map[L - 1];
-	} else {
-		const double fl = floor(t);
-		const int i = (int)fl;
-		const double w = t - fl;
-		if (w == 0.0) {
-			v = map[i];
-		} else {
-			const double d = map[i + 1] - map[i];
-			const double wd = w * d;
-			v = map[i] + wd;
-		}
-	}
-	const double p = v * in_per_unit;
-	if (!(p >= -1073741824.0 && p < 1073741824.0)) return kNoPosition;  // (a NaN and the infinities fail the comparisons)
-	return (long long)floor(p * 4294967296.0);
 }
 
 // a record's x_off, hi and y_off are its map's first entry, its length and its first position; a record of the tiled group counts
@@ -509,7 +565,8 @@ __global__ __launch_bounds__(kPlainBlock) void warp_map_kernel(WmArgs a) {
 	const VrRec r = a.rec[rs_find(a.rec, a.n_rec, b)];
 	const long long i = (((long long)b - r.block0) * a.sub + (int)blockIdx.x % a.sub) * kPlainBlock + threadIdx.x;
 	if (i >= r.n_out) return;
-	a.pos[r.y_off + i] = wm_position(a.map + r.x_off, r.hi, a.out_per_entry, a.in_per_unit, i);
+	const WmArray entry = {a.map + r.x_off};
+	a.pos[r.y_off + i] = wm_position(entry, r.hi, a.out_per_entry, a.in_per_unit, i);
 }
 
 template <int FMT, int D> __global__ __launch_bounds__(kPlainBlock) void vresample_plain_kernel(VrArgs a, const double *__restrict__ C) {
@@ -541,11 +598,12 @@ typedef RsCore<Plan, Tiling> Core;
 // the table built and uploaded for a checked plan; nullptr + error on failure
 Core *core_create(const Plan &p) {
 	const Tiling t = tiling_of(p);
-	const void *segment_kernels[6];  // the converter's and the warp's
+	const void *segment_kernels[9];  // the converter's and the warp's two
 	for (int fmt = 0; fmt < 3; ++fmt)
 		with_variant(fmt, p.D, [&](auto format, auto degree) {
 			segment_kernels[fmt] = (const void *)vresample_segment_kernel<decltype(format)::value, decltype(degree)::value>;
-			segment_kernels[3 + fmt] = (const void *)warp_segment_kernel<decltype(format)::value, decltype(degree)::value>;
+			segment_kernels[3 + fmt] = (const void *)warp_segment_kernel<decltype(format)::value, decltype(degree)::value, WpArgs>;
+			segment_kernels[6 + fmt] = (const void *)warp_segment_kernel<decltype(format)::value, decltype(degree)::value, WsArgs>;
 		});
 	return rs_core_create<Core>(kName, "the tile", p, t, t.tile_out > 0 && !WC_VR_FORCE_PLAIN, (size_t)p.P * p.taps * (p.D + 1),
 								[&](double *C) { build_table(p, C); }, segment_kernels);
@@ -575,7 +633,25 @@ int wp_enqueue(const Core &c, hipStream_t hs, const VrRec *d_rec, const RsSorted
 	return rs_timed(c, "warp_kernels", hs, [&] {
 		with_variant(in_format, c.p.D, [&](auto format, auto degree) {
 			constexpr int FMT = decltype(format)::value, D = decltype(degree)::value;
-			rs_launch_pair(c, hs, a, d_rec, s, warp_segment_kernel<FMT, D>, warp_plain_kernel<FMT, D>);
+			rs_launch_pair(c, hs, a, d_rec, s, warp_segment_kernel<FMT, D, WpArgs>, warp_plain_kernel<FMT, D, WpArgs>);
+		});
+	});
+}
+
+// the same launch with the map rule as the source of the positions: entries at `map`, carried entries at `carry`; n_keep entries
+// are carried on by blocks behind the plain group's own (a launch of those blocks alone where the group is empty)
+int ws_enqueue(const Core &c, hipStream_t hs, const WmRec *d_rec, RsSorted s, const void *x, int in_format, const double *map, double *carry,
+			   const WsKeep *keep, int n_keep, void *y, int out_format) {
+	WsArgs a = {};
+	a.x = x; a.y = y; a.map = map; a.carry = carry;
+	a.keep = keep; a.n_keep = n_keep; a.keep_block0 = s.blocks_plain;
+	a.K = c.p.K; a.taps = c.p.taps; a.B = c.p.B;
+	a.tile_out = c.t.tile_out; a.span_max = c.t.span_max; a.out_format = out_format;
+	s.blocks_plain += (n_keep + kPlainBlock - 1) / kPlainBlock;
+	return rs_timed(c, "warp_map_kernels", hs, [&] {
+		with_variant(in_format, c.p.D, [&](auto format, auto degree) {
+			constexpr int FMT = decltype(format)::value, D = decltype(degree)::value;
+			rs_launch_pair(c, hs, a, d_rec, s, warp_segment_kernel<FMT, D, WsArgs>, warp_plain_kernel<FMT, D, WsArgs>);
 		});
 	});
 }
@@ -611,10 +687,168 @@ struct State : RsStreamState {
 	}
 };
 
+// ---- warp streams (world_class_warp_stream.h): the host's arithmetic on counts ------------------------------------------------------
+// c(E): the n >= 0 with (double)n / out_per_entry <= (double)(E - 1), found from the product and corrected with the predicate;
+// -1 where the count leaves 62 bits
+long long ws_committed(long long entries, double out_per_entry) {
+	if (entries < 1) return 0;
+	const double last = (double)(entries - 1);
+	const double guess = std::floor(last * out_per_entry);
+	if (!(guess < 4611686018427387904.0)) return -1;
+	const auto in = [&](long long n) { return (double)n / out_per_entry <= last; };
+	long long n = (long long)guess;  // (n = 0 is always in)
+	while (in(n + 1)) ++n;
+	while (n > 0 && !in(n)) --n;
+	return n + 1;
+}
+
+// what `entries` more entries can commit at most at out_per_entry: c moves by floor(a + b) - floor(a) <= ceil(b), and by one more
+// at either end where a quotient rounds across the predicate; -1 where it leaves 31 bits
+long long ws_max_out(int entries, double out_per_entry) {
+	if (entries < 1) return 0;
+	const double v = std::ceil((double)entries * out_per_entry) + 2.0;
+	return v <= (double)INT_MAX ? (long long)v : -1;
+}
+
+struct WsState {
+	int track = -1;  // -1: not attached
+	int delay = 0;
+	int parity = 0;  // where of its pair the carried entry stands
+	bool ended = false;
+	double out_per_entry = 0.0, in_per_unit = 0.0;
+	long long rows = 0, entries = 0, committed = 0;
+};
+
+constexpr char kWsName[] = "warp stream";
+int ws_bytes_of(int format) { return format == 0 ? 8 : format == 1 ? 2 : 4; }
+
 }  // namespace
 
 struct wc_vresampler : RsBatch<Core> {};
 struct wc_vresample_stream : RsStreams<Core, State> {};
+struct wc_warp_stream {
+	Core *c = nullptr;
+	int n_streams = 0, n_tracks = 0, max_track = 0, track_format = 0, max_entries = 0, max_delay = 0;
+	int max_out_push = 0, max_out_flush = 0;
+	double max_out_per_entry = 0.0;
+	std::vector<WsState> st;
+	std::vector<int> track_len;  // 0: the slot has not been set
+	DevBuf tracks;               // n_tracks x max_track samples of track_format
+	DevBuf carry;                // n_streams x 2 doubles
+	DevBuf drec;                 // a record per stream with outputs, then a WsKeep per stream with entries
+	HostBuf h_rec[2];
+	int parity = 0;
+};
+
+namespace {
+
+// The whole of a push (flush false: counts are n_rows, entries are d_settled's) and of a flush (counts are want, entries are the
+// tail's).  Everything is planned from the counts before the first enqueue; the plan becomes the state behind the last one.
+int ws_push(wc_warp_stream *h, bool flush, const int *counts, const double *d_entries, void *d_y, int out_format, int *samples_out) {
+	const char *what = flush ? " flush" : " push";
+	const auto refuse = [&](const char *why) { return rs_refuse(kWsName, (std::string(what) + why).c_str()); };
+	if (!h || !counts || !samples_out) return refuse(": null argument");
+	if (out_format != 0 && out_format != 1) return refuse(": out_format is 0 or 1");
+	const Core &c = *h->c;
+	DeviceLock lock(c.dev);
+	const int n = h->n_streams, max_out = flush ? h->max_out_flush : h->max_out_push;
+	struct Share {
+		int slice, consumed;    // doubles of the stream in d_entries; entries consumed, the last ones of the slice
+		long long after, outs;  // c(E_after); outputs
+	};
+	std::vector<Share> share((size_t)n);
+	long long total_read = 0, total_out = 0;
+	for (int u = 0; u < n; ++u) {
+		const WsState &s = h->st[u];
+		Share &p = share[u];
+		p = Share();
+		p.after = s.committed;
+		if (flush) {
+			if (!counts[u]) continue;
+			if (s.track < 0 || s.ended) return refuse(": a wanted stream is not attached or has ended");
+			if (s.delay == 0 || s.rows == 0) return refuse(": a wanted stream has delay 0 or no rows (nothing waits)");
+			p.slice = (int)std::min<long long>((long long)s.delay + 1, s.rows);
+			p.consumed = (int)std::min<long long>(s.delay, s.rows);
+		} else {
+			if (counts[u] < 0 || counts[u] > h->max_entries) return refuse(": a count outside 0 .. max_entries_per_push");
+			if (counts[u] > 0 && (s.track < 0 || s.ended)) return refuse(": rows for a stream that is not attached or has ended (reset it first)");
+			p.slice = counts[u];
+			p.consumed = (int)(std::max<long long>(s.rows + counts[u] - s.delay, 0) - std::max<long long>(s.rows - s.delay, 0));
+		}
+		if (p.consumed > 0) {
+			p.after = ws_committed(s.entries + p.consumed, s.out_per_entry);
+			if (p.after < 0 || p.after - s.committed > max_out) return refuse(": the output count leaves the handle's bound");
+		}
+		p.outs = p.after - s.committed;
+		total_read += p.consumed;
+		total_out += p.outs;
+	}
+	if ((total_read > 0 && !d_entries) || (total_out > 0 && !d_y)) return refuse(": null array");
+	// ---- no refusal is left: the records ----
+	HostBuf &hb = h->h_rec[h->parity];
+	if (hb.reserve(0)) return WC_ERR_DEVICE;  // (the copy of the push before the last has read this staging)
+	std::vector<WmRec> recs;
+	std::vector<WsKeep> keeps;
+	long long e_off = 0, y_off = 0;
+	for (int u = 0; u < n; ++u) {
+		const WsState &s = h->st[u];
+		const Share &p = share[u];
+		samples_out[u] = (int)p.outs;
+		if (p.outs > 0) {
+			WmRec q = WmRec();
+			q.x_off = (long long)s.track * h->max_track; q.y_off = y_off;
+			q.lo = 0; q.hi = h->track_len[s.track];
+			q.n_out = (int)p.outs;
+			q.map_off = e_off + (p.slice - p.consumed);
+			q.first = s.entries; q.L = s.entries + p.consumed;
+			q.n0 = s.committed;
+			q.out_per_entry = s.out_per_entry; q.in_per_unit = s.in_per_unit;
+			q.carry = 2 * u + s.parity;
+			recs.push_back(q);
+		}
+		if (p.consumed > 0 && !flush) {
+			WsKeep k = {e_off + p.slice - 1, 2 * u + (1 - s.parity), 0};
+			keeps.push_back(k);
+		}
+		e_off += p.slice;
+		y_off += p.outs;
+	}
+	if (!recs.empty() || !keeps.empty()) {
+		WC_HIP(hipSetDevice(c.dev->id));
+		hipStream_t hs = c.dev->active();
+		WmRec *rec = hb.as<WmRec>();
+		const RsSorted so = rs_sort_records(c, recs, rec);
+		WsKeep *keep = reinterpret_cast<WsKeep *>(rec + recs.size());
+		std::copy(keeps.begin(), keeps.end(), keep);
+		const size_t bytes = sizeof(WmRec) * recs.size() + sizeof(WsKeep) * keeps.size();
+		WC_HIP(hipMemcpyAsync(h->drec.p, hb.p, bytes, hipMemcpyHostToDevice, hs));
+		int rc;
+		if ((rc = hb.mark(hs))) return rc;
+		h->parity = 1 - h->parity;
+		const WmRec *d_rec = h->drec.as<WmRec>();
+		if ((rc = ws_enqueue(c, hs, d_rec, so, h->tracks.p, h->track_format, d_entries, h->carry.as<double>(),
+							 reinterpret_cast<const WsKeep *>(d_rec + recs.size()), (int)keeps.size(), d_y, out_format)))
+			return rc;
+	}
+	for (int u = 0; u < n; ++u) {
+		WsState &s = h->st[u];
+		const Share &p = share[u];
+		if (flush) {
+			if (!counts[u]) continue;
+			s.ended = true;
+		} else {
+			s.rows += counts[u];
+			if (p.consumed > 0) s.parity = 1 - s.parity;
+		}
+		s.entries += p.consumed;
+		s.committed = p.after;
+	}
+	return WC_OK;
+}
+
+bool ws_stream_ok(const wc_warp_stream *h, int stream) { return h && stream >= 0 && stream < h->n_streams; }
+
+}  // namespace
 
 extern "C" {
 
@@ -774,7 +1008,8 @@ int wc_warp_map_positions(const double *map, int map_length, double out_per_entr
 	if (!map || !pos) return fail(WC_ERR_INVALID, "warp map: null argument");
 	if (map_length < 1 || n_out < 0) return fail(WC_ERR_INVALID, "warp map: a map holds one entry at least and n_out is not negative");
 	if (!wm_scale_ok(out_per_entry) || !wm_scale_ok(in_per_unit)) return fail(WC_ERR_INVALID, "warp map: out_per_entry and in_per_unit must be finite and positive");
-	for (long long n = 0; n < n_out; ++n) pos[n] = wm_position(map, map_length, out_per_entry, in_per_unit, n);
+	const WmArray entry = {map};
+	for (long long n = 0; n < n_out; ++n) pos[n] = wm_position(entry, map_length, out_per_entry, in_per_unit, n);
 	return WC_OK;
 }
 
@@ -803,6 +1038,129 @@ int wc_warp_map_positions_device(wc_vresampler *r, int n_utt, const double *d_ma
 		},
 		[&](hipStream_t hs, const VrRec *d_rec, const RsSorted &s) { return wm_enqueue(*r->c, hs, d_rec, s, d_map, out_per_entry, in_per_unit, d_pos); });
 }
+
+// ---- warp streams (world_class_warp_stream.h) ---------------------------------------------------------------------------------------
+long long wc_warp_stream_committed(long long entries, double out_per_entry) {
+	if (entries < 0) return fail(WC_ERR_INVALID, "warp stream: a negative entry count");
+	if (!wm_scale_ok(out_per_entry)) return fail(WC_ERR_INVALID, "warp stream: out_per_entry must be finite and positive");
+	const long long n = ws_committed(entries, out_per_entry);
+	return n < 0 ? fail(WC_ERR_INVALID, "warp stream: the output count leaves 62 bits") : n;
+}
+
+int wc_warp_along_map_device(wc_vresampler *r, int n_utt, const void *d_x, int in_format, const int *x_length, const double *d_map,
+							 const int *map_length, double out_per_entry, double in_per_unit, const int *out_length, void *d_y,
+							 int out_format) {
+	if (!wm_scale_ok(out_per_entry) || !wm_scale_ok(in_per_unit)) return fail(WC_ERR_INVALID, "warp along map: out_per_entry and in_per_unit must be finite and positive");
+	long long map_off = 0;  // (the utterances are formed in their order)
+	return rs_batch_run<WmRec>(
+		"warp along map", r, x_length && map_length && out_length && d_x && d_map && d_y, n_utt, in_format, out_format, x_length,
+		[&](int u, WmRec &q, long long *n_out) -> const char * {
+			if (map_length[u] < 1) return ": a map holds one entry at least";
+			if (out_length[u] < 0) return ": an output length below 0";
+			*n_out = out_length[u];
+			q.map_off = map_off; q.L = map_length[u];
+			q.out_per_entry = out_per_entry; q.in_per_unit = in_per_unit;
+			map_off += map_length[u];
+			return nullptr;
+		},
+		[&](hipStream_t hs, const WmRec *d_rec, const RsSorted &s) {
+			return ws_enqueue(*r->c, hs, d_rec, s, d_x, in_format, d_map, nullptr, nullptr, 0, d_y, out_format);
+		});
+}
+
+wc_warp_stream *wc_warp_stream_create(unsigned long long step_min, unsigned long long step_max, int zeros, double rolloff, double beta,
+									  int phase_bits, int degree, int n_streams, int n_tracks, int max_track_samples, int track_format,
+									  int max_entries_per_push, int max_delay, double max_out_per_entry) {
+	if (n_streams < 1 || n_tracks < 1 || max_track_samples < 1 || max_entries_per_push < 1) {
+		set_error("warp stream: n_streams, n_tracks, max_track_samples and max_entries_per_push must be at least 1");
+		return nullptr;
+	}
+	if (max_delay < 0) { set_error("warp stream: max_delay must not be negative"); return nullptr; }
+	if (track_format < 0 || track_format > 2) { set_error("warp stream: track_format is 0, 1 or 2"); return nullptr; }
+	if (!wm_scale_ok(max_out_per_entry)) { set_error("warp stream: max_out_per_entry must be finite and positive"); return nullptr; }
+	Plan p;
+	const std::string why = plan_of(step_min, step_max, zeros, rolloff, beta, phase_bits, degree, &p);
+	if (!why.empty()) { set_error(why); return nullptr; }
+	const long long out_push = ws_max_out(max_entries_per_push, max_out_per_entry), out_flush = ws_max_out(max_delay, max_out_per_entry);
+	if (out_push < 0 || out_flush < 0 || std::max(out_push, out_flush) * n_streams > (long long)INT_MAX) {
+		set_error("warp stream: max_out_per_push or the packed output leaves 31 bits");
+		return nullptr;
+	}
+	Core *c = core_create(p);
+	if (!c) return nullptr;
+	DeviceLock lock(c->dev);
+	wc_warp_stream *h = new wc_warp_stream();
+	h->c = c;
+	h->n_streams = n_streams; h->n_tracks = n_tracks; h->max_track = max_track_samples; h->track_format = track_format;
+	h->max_entries = max_entries_per_push; h->max_delay = max_delay; h->max_out_per_entry = max_out_per_entry;
+	h->max_out_push = (int)out_push; h->max_out_flush = (int)out_flush;
+	h->st.resize((size_t)n_streams);
+	h->track_len.assign((size_t)n_tracks, 0);
+	const size_t rec = (sizeof(WmRec) + sizeof(WsKeep)) * (size_t)n_streams;
+	if (h->tracks.reserve((size_t)ws_bytes_of(track_format) * (size_t)n_tracks * (size_t)max_track_samples) ||
+		h->carry.reserve(sizeof(double) * 2 * (size_t)n_streams) || h->drec.reserve(rec) || h->h_rec[0].reserve(rec) || h->h_rec[1].reserve(rec)) {
+		wc_warp_stream_destroy(h);
+		return nullptr;
+	}
+	return h;
+}
+
+void wc_warp_stream_destroy(wc_warp_stream *h) {
+	if (!h) return;
+	h->c->dev->quiesce();
+	h->tracks.release(); h->carry.release(); h->drec.release(); h->h_rec[0].release(); h->h_rec[1].release();
+	rs_core_destroy(h->c);
+	delete h;
+}
+
+int wc_warp_stream_set_track_device(wc_warp_stream *h, int track, int n_samples, const void *d_x) {
+	if (!h || !d_x) return rs_refuse(kWsName, " set_track: null argument");
+	if (track < 0 || track >= h->n_tracks) return rs_refuse(kWsName, " set_track: bad track index");
+	if (n_samples < 1 || n_samples > h->max_track) return rs_refuse(kWsName, " set_track: n_samples outside 1 .. max_track_samples");
+	DeviceLock lock(h->c->dev);
+	for (const WsState &s : h->st)
+		if (s.track == track && s.rows > 0) return rs_refuse(kWsName, " set_track: a stream that has received rows is attached to the slot");
+	const size_t each = (size_t)ws_bytes_of(h->track_format);
+	WC_HIP(hipSetDevice(h->c->dev->id));
+	WC_HIP(hipMemcpyAsync(static_cast<char *>(h->tracks.p) + each * (size_t)track * (size_t)h->max_track, d_x, each * (size_t)n_samples,
+						  hipMemcpyDeviceToDevice, h->c->dev->active()));
+	h->track_len[track] = n_samples;
+	return WC_OK;
+}
+
+int wc_warp_stream_reset(wc_warp_stream *h, int stream, int track, int delay, double out_per_entry, double in_per_unit) {
+	if (!ws_stream_ok(h, stream)) return rs_refuse(kWsName, " reset: bad stream index");
+	if (track < 0 || track >= h->n_tracks) return rs_refuse(kWsName, " reset: bad track index");
+	if (delay < 0 || delay > h->max_delay) return rs_refuse(kWsName, " reset: a delay outside 0 .. max_delay");
+	if (!wm_scale_ok(out_per_entry) || out_per_entry > h->max_out_per_entry) return rs_refuse(kWsName, " reset: out_per_entry must be finite, positive and at most max_out_per_entry");
+	if (!wm_scale_ok(in_per_unit)) return rs_refuse(kWsName, " reset: in_per_unit must be finite and positive");
+	DeviceLock lock(h->c->dev);
+	if (h->track_len[track] == 0) return rs_refuse(kWsName, " reset: the slot has not been set");
+	WsState &s = h->st[stream];
+	const int parity = s.parity;  // (the carried entry is not cleared: no output reads one before an entry has been consumed)
+	s = WsState();
+	s.parity = parity;
+	s.track = track; s.delay = delay;
+	s.out_per_entry = out_per_entry; s.in_per_unit = in_per_unit;
+	return WC_OK;
+}
+
+int wc_warp_stream_max_out_per_push(const wc_warp_stream *h) { return h ? h->max_out_push : WC_ERR_INVALID; }
+int wc_warp_stream_max_out_per_flush(const wc_warp_stream *h) { return h ? h->max_out_flush : WC_ERR_INVALID; }
+
+int wc_warp_stream_push_device(wc_warp_stream *h, const int *n_rows, const double *d_map, void *d_y, int out_format, int *samples_out) {
+	return ws_push(h, false, n_rows, d_map, d_y, out_format, samples_out);
+}
+
+int wc_warp_stream_flush_device(wc_warp_stream *h, const int *want, const double *d_tail, void *d_y, int out_format, int *samples_out) {
+	return ws_push(h, true, want, d_tail, d_y, out_format, samples_out);
+}
+
+long long wc_warp_stream_rows_received(const wc_warp_stream *h, int stream) { return ws_stream_ok(h, stream) ? h->st[stream].rows : -1; }
+long long wc_warp_stream_entries_consumed(const wc_warp_stream *h, int stream) { return ws_stream_ok(h, stream) ? h->st[stream].entries : -1; }
+long long wc_warp_stream_samples_committed(const wc_warp_stream *h, int stream) { return ws_stream_ok(h, stream) ? h->st[stream].committed : -1; }
+int wc_warp_stream_get_delay(const wc_warp_stream *h, int stream) { return ws_stream_ok(h, stream) ? h->st[stream].delay : -1; }
+int wc_warp_stream_track_length(const wc_warp_stream *h, int track) { return h && track >= 0 && track < h->n_tracks ? h->track_len[track] : -1; }
 
 }  // extern "C"
 
