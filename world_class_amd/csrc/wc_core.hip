@@ -256,6 +256,7 @@ void Device::release_batch_staging() {
 	quiesce();  // (a copy out of the staging may still be in flight on a caller's stream)
 	for (Staging &st : batch) { st.h.release(); st.d.release(); }
 	align_scratch.release();
+	features_scratch.release();
 }
 void Device::handle_born() {
 	std::lock_guard<std::recursive_mutex> lk(mu);

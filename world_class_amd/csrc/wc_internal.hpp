@@ -84,6 +84,11 @@ struct Device {
 	DevBuf align_scratch;
 	hipEvent_t align_done = nullptr;
 	hipStream_t align_last = nullptr;
+	// Scratch of the model-feature calls (wc_features.hip): pack's continuous lf0 and gap ends, MLPG's parked l1, l2 and z / d.  Kept
+	// and handed from stream to stream like align_scratch.
+	DevBuf features_scratch;
+	hipEvent_t features_done = nullptr;
+	hipStream_t features_last = nullptr;
 	int live_handles = 0;  // stage handles alive on this device (under mu)
 	void handle_born();
 	void handle_gone();  // the last one takes the batch staging with it
