@@ -1976,6 +1976,76 @@ __global__ __launch_bounds__(OA_T) void syn_overlap_add_kernel(SynArgs a) {
 	}
 }
 
+// ---- development hooks (wc_debug_minimum_phase below; not part of include/world_class_c.h) ---------------------------------
+// The three minimum-phase analyses on their own, one workgroup per log spectrum, doing around the call what the pulse kernels
+// do: in `ls` M + 1 doubles per spectrum, out M + 1 complex values (tests/test_gpu_minimum_phase.py).
+template <int N, int T>
+__global__ __launch_bounds__(T) void hook_minphase_lds_kernel(const double *__restrict__ ls_all, double2 *__restrict__ out,
+															   const double2 *__restrict__ tw) {
+	constexpr int M = N / 2;
+	constexpr int BPT = (M + T) / T;
+	__shared__ double2 A[WC_SYN_MINPHASE_REAL ? fft_lds_size(N / 2) + 1 : fft_lds_size(N)];
+	const int tid = threadIdx.x;
+	const double *__restrict__ src = ls_all + (size_t)blockIdx.x * (M + 1);
+	double2 *__restrict__ X = out + (size_t)blockIdx.x * (M + 1);
+	double ls[BPT];
+#pragma unroll
+	for (int e = 0; e < BPT; ++e) {
+		const int k = tid + e * T;
+		ls[e] = k <= M ? src[k] : 0.0;
+	}
+	minimum_phase_lds<N, T>(A, ls, tw, tid);
+#pragma unroll
+	for (int e = 0; e < BPT; ++e) {
+		const int k = tid + e * T;
+		if (k <= M) X[k] = A[k];
+	}
+}
+__global__ __launch_bounds__(64) void hook_minphase_wave_kernel(const double *__restrict__ ls_all, double2 *__restrict__ out,
+																const double2 *__restrict__ tw) {
+	constexpr int M = 1024;
+	__shared__ __attribute__((aligned(16))) double L[kWfLds];
+	__shared__ __attribute__((aligned(16))) double T[kWfTabLds];
+	const int lane = threadIdx.x;
+	wf_tables_to_lds(T, tw, lane);
+	const double *__restrict__ src = ls_all + (size_t)blockIdx.x * (M + 1);
+	double2 *__restrict__ X = out + (size_t)blockIdx.x * (M + 1);
+#pragma unroll
+	for (int g = 0; g < 4; ++g)
+#pragma unroll
+		for (int q = 0; q < 4; ++q) L[wf_bin(lane, g, q)] = src[wf_bin(lane, g, q)];
+	if (lane == 0) L[M] = src[M];
+	double mr[16], mi[16], mM;
+	minimum_phase_wave(mr, mi, mM, L, T, tw, lane);
+#pragma unroll
+	for (int g = 0; g < 4; ++g)
+#pragma unroll
+		for (int q = 0; q < 4; ++q) X[wf_bin(lane, g, q)] = make_double2(mr[4 * g + q], mi[4 * g + q]);
+	if (lane == 0) X[M] = make_double2(mM, 0.0);
+}
+__global__ __launch_bounds__(64) void hook_minphase_wave8_kernel(const double *__restrict__ ls_all, double2 *__restrict__ out,
+																 const double2 *__restrict__ tw) {
+	constexpr int M = 512;
+	__shared__ __attribute__((aligned(16))) double L[kWf8Lds];
+	__shared__ __attribute__((aligned(16))) double T[kWfTabLds];
+	const int lane = threadIdx.x;
+	wf_tables_to_lds(T, tw, lane);
+	const double *__restrict__ src = ls_all + (size_t)blockIdx.x * (M + 1);
+	double2 *__restrict__ X = out + (size_t)blockIdx.x * (M + 1);
+#pragma unroll
+	for (int g = 0; g < 2; ++g)
+#pragma unroll
+		for (int q = 0; q < 4; ++q) L[wf8_bin(lane, g, q)] = src[wf8_bin(lane, g, q)];
+	if (lane == 0) L[M] = src[M];
+	double mr[8], mi[8], mM;
+	minimum_phase_wave8(mr, mi, mM, L, T, tw, lane);
+#pragma unroll
+	for (int g = 0; g < 2; ++g)
+#pragma unroll
+		for (int q = 0; q < 4; ++q) X[wf8_bin(lane, g, q)] = make_double2(mr[4 * g + q], mi[4 * g + q]);
+	if (lane == 0) X[M] = make_double2(mM, 0.0);
+}
+
 }  // namespace wc
 
 using namespace wc;
@@ -2004,12 +2074,15 @@ struct wc_synthesis {
 	int n_utt = 0, max_out = 0;
 };
 
+// threads of a workgroup-per-pulse block:
+// eight samples per thread up to N = 2048 (at N = 1024 / 512 a 256-thread block idles half / three quarters of its threads in
+// every FFT pass: 3.53 -> 3.35 ms per 64 x 10 s at 16 kHz, 2.08 -> 1.53 ms at 8 kHz); 512 threads per 2048-point pulse measured
+// slower (13.2 vs 10.0 ms per 64 x 10 s batch)
+static constexpr int pulse_threads(int n) { return (n >= 2048) ? 256 : (n / 8 < 64 ? 64 : n / 8); }
+
 template <int N>
 static void launch_pulses(const SynArgs &a, hipStream_t s) {
-	// eight samples per thread up to N = 2048 (at N = 1024 / 512 a 256-thread block idles half / three quarters of its threads in
-	// every FFT pass: 3.53 -> 3.35 ms per 64 x 10 s at 16 kHz, 2.08 -> 1.53 ms at 8 kHz); 512 threads per 2048-point pulse measured
-	// slower (13.2 vs 10.0 ms per 64 x 10 s batch)
-	constexpr int TP = (N >= 2048) ? 256 : (N / 8 < 64 ? 64 : N / 8);
+	constexpr int TP = pulse_threads(N);
 	// (the pulses are dealt to the XCDs in eighths: the grid is a multiple of eight, the kernel drops what lies beyond the count)
 	hipLaunchKernelGGL((syn_pulse_kernel<N, TP>), dim3((unsigned)(8 * ((a.total_pulses + 7) / 8))), dim3(TP), 0, s, a);
 }
@@ -2631,3 +2704,50 @@ int wc_synthesis_compute(wc_synthesis *s, const double *f0, int f0_length, const
 }
 
 }  // extern "C"
+
+// Development hook (undeclared, like the wc_debug_* of wc_testhooks.hip; it lives here because the analyses are defined here):
+// `batch` log spectra of n / 2 + 1 doubles each in `ls`, their minimum-phase spectra, n / 2 + 1 complex values each, in `out`;
+// host pointers.  form 0: minimum_phase_lds<n, T> with the pulse kernel's block size, n = 512, 1024, 2048, 4096; form 1: the
+// one-wavefront forms, minimum_phase_wave8 for n = 1024 and minimum_phase_wave for n = 2048.
+namespace {
+struct HookBuf {
+	void *p = nullptr;
+	~HookBuf() { if (p) (void)hipFree(p); }
+};
+template <int N>
+void launch_minphase_lds(int batch, const double *ls, double2 *out, const double2 *tw, hipStream_t s) {
+	hipLaunchKernelGGL((hook_minphase_lds_kernel<N, pulse_threads(N)>), dim3(batch), dim3(pulse_threads(N)), 0, s, ls, out, tw);
+}
+}  // namespace
+
+extern "C" int wc_debug_minimum_phase(int form, int n, int batch, const double *ls, double *out) {
+	if (batch <= 0 || !ls || !out) return fail(WC_ERR_INVALID, "debug minimum phase: bad argument");
+	const bool ok = form == 0 ? (n == 512 || n == 1024 || n == 2048 || n == 4096) : form == 1 ? (n == 1024 || n == 2048) : false;
+	if (!ok) return fail(WC_ERR_UNSUPPORTED, "debug minimum phase: form 0 takes n = 512, 1024, 2048, 4096, form 1 n = 1024, 2048");
+	Device *dev = current_device();
+	if (!dev) return WC_ERR_DEVICE;
+	DeviceLock lock(dev);
+	hipStream_t s = dev->active();
+	const size_t bins = (size_t)(n / 2 + 1) * batch;
+	HookBuf d_in, d_out;
+	WC_HIP(hipMalloc(&d_in.p, sizeof(double) * bins));
+	WC_HIP(hipMalloc(&d_out.p, sizeof(double2) * bins));
+	WC_HIP(hipMemcpyAsync(d_in.p, ls, sizeof(double) * bins, hipMemcpyHostToDevice, s));
+	const double *di = static_cast<const double *>(d_in.p);
+	double2 *dout = static_cast<double2 *>(d_out.p);
+	if (form == 1) {
+		if (n == 1024) hipLaunchKernelGGL(hook_minphase_wave8_kernel, dim3(batch), dim3(64), 0, s, di, dout, dev->twiddle);
+		else hipLaunchKernelGGL(hook_minphase_wave_kernel, dim3(batch), dim3(64), 0, s, di, dout, dev->twiddle);
+	} else {
+		switch (n) {
+			case 512: launch_minphase_lds<512>(batch, di, dout, dev->twiddle, s); break;
+			case 1024: launch_minphase_lds<1024>(batch, di, dout, dev->twiddle, s); break;
+			case 2048: launch_minphase_lds<2048>(batch, di, dout, dev->twiddle, s); break;
+			default: launch_minphase_lds<4096>(batch, di, dout, dev->twiddle, s); break;
+		}
+	}
+	WC_HIP(hipGetLastError());
+	WC_HIP(hipMemcpyAsync(out, d_out.p, sizeof(double2) * bins, hipMemcpyDeviceToHost, s));
+	WC_HIP(hipStreamSynchronize(s));
+	return WC_OK;
+}

@@ -1,7 +1,11 @@
 // Development / test hooks (not part of include/world_class_c.h): the device building blocks of wc_device.hpp run on
 // their own, so that -m gpu tests can pin them directly -- the in-LDS FFT against the reference's transform conventions
 // (reference src/world_fft.cpp:31-167; goldens fft/* made by the real reference), the order-faithful cumulative sum
-// against a sequential loop.  One workgroup per transform / sequence; nothing here is on the product path.
+// against a sequential loop, the lean sin / cos / log / exp and the two reciprocal interpolators against wide references
+// (tests/test_gpu_lean_math.py).  One workgroup per transform / sequence; nothing here is on the product path.
+// (the minimum-phase analyses have their hook, wc_debug_minimum_phase, in wc_synthesis.hip, where they are defined)
+#include <algorithm>
+#include <cmath>
 #include <vector>
 
 #include "wc_device.hpp"
@@ -237,6 +241,41 @@ __global__ void hook_logexp_kernel(int kind, const double *__restrict__ in, doub
 	const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
 	if (i < n) out[i] = kind == 0 ? wf_log(in[i], tw) : wf_exp(in[i], tw);
 }
+// kind 0: wf_sincos, 1: wf_sincospi; out[i] = sin, out[n + i] = cos
+__global__ __launch_bounds__(256) void hook_sincos_kernel(int kind, const double *__restrict__ in, double *__restrict__ out, long long n) {
+	const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+	if (i >= n) return;
+	double sn, cs;
+	if (kind == 0) wf_sincos(in[i], sn, cs);
+	else wf_sincospi(in[i], sn, cs);
+	out[i] = sn;
+	out[n + i] = cs;
+}
+// kind 2: wf_log_l, 3: wf_exp_l, one wavefront per 64 values behind the copy of the tables it made itself in LDS
+__global__ __launch_bounds__(64) void hook_logexp_lds_kernel(int kind, const double *__restrict__ in, double *__restrict__ out, long long n,
+															 const double2 *__restrict__ tw) {
+	__shared__ __attribute__((aligned(16))) double T[kWfTabLds];
+	const int lane = threadIdx.x;
+	wf_tables_to_lds(T, tw, lane);
+	const long long i = (long long)blockIdx.x * 64 + lane;
+	if (i < n) out[i] = kind == 2 ? wf_log_l(in[i], T) : wf_exp_l(in[i], T);
+}
+// interp1Q of m abscissae on the table y[0 .. n) at x0 + i dx.  KIND 0: interp1q (the reference's division) and 1: interp1q_rcp,
+// both on the table where it lies; 2: wf_interp1q on a copy in LDS (n <= 4096).  The abscissae lie inside the table.
+template <int KIND>
+__global__ __launch_bounds__(256) void hook_interp1q_kernel(double x0, double dx, double rdx, const double *__restrict__ y, int n, long long m,
+															const double *__restrict__ xi, double *__restrict__ out) {
+	__shared__ double S[KIND == 2 ? 4096 : 1];
+	if constexpr (KIND == 2) {
+		for (int i = threadIdx.x; i < n; i += 256) S[i] = y[i];
+		__syncthreads();
+	}
+	for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < m; i += (long long)gridDim.x * 256) {
+		if constexpr (KIND == 0) out[i] = interp1q(x0, dx, [&](int b) { return y[b]; }, n, xi[i]);
+		else if constexpr (KIND == 1) out[i] = interp1q_rcp(x0, dx, rdx, [&](int b) { return y[b]; }, n, xi[i]);
+		else out[i] = wf_interp1q(x0, dx, rdx, S, n, xi[i]);
+	}
+}
 
 }  // namespace wc
 
@@ -385,6 +424,69 @@ int wc_debug_logexp(int kind, long long n, const double *in, double *out) {
 					   static_cast<double *>(d_out.p), n, dev->twiddle);
 	WC_HIP(hipGetLastError());
 	WC_HIP(hipMemcpyAsync(out, d_out.p, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+	WC_HIP(hipStreamSynchronize(s));
+	return WC_OK;
+}
+
+// the lean sin / cos and the LDS-table forms of the lean log / exp (wc_wavefft.hpp) on n host values.
+// kind 0: wf_sincos, 1: wf_sincospi -- out holds 2 n doubles, the sines, then the cosines; 2: wf_log_l, 3: wf_exp_l -- n doubles;
+// 4, 5: wf_sincos / wf_sincospi compiled for the host (the same bodies, __host__ __device__), run here: they need no device
+int wc_debug_lean_math(int kind, long long n, const double *in, double *out) {
+	if (kind < 0 || kind > 5 || n <= 0 || !in || !out) return fail(WC_ERR_INVALID, "debug lean math: bad argument");
+	if (kind >= 4) {
+		for (long long i = 0; i < n; ++i) {
+			if (kind == 4) wf_sincos(in[i], out[i], out[n + i]);
+			else wf_sincospi(in[i], out[i], out[n + i]);
+		}
+		return WC_OK;
+	}
+	Device *dev = current_device();
+	if (!dev) return WC_ERR_DEVICE;
+	DeviceLock lock(dev);
+	hipStream_t s = dev->active();
+	const size_t n_out = (kind < 2 ? 2 : 1) * (size_t)n;
+	Scoped d_in, d_out;
+	WC_HIP(hipMalloc(&d_in.p, sizeof(double) * n));
+	WC_HIP(hipMalloc(&d_out.p, sizeof(double) * n_out));
+	WC_HIP(hipMemcpyAsync(d_in.p, in, sizeof(double) * n, hipMemcpyHostToDevice, s));
+	const double *di = static_cast<const double *>(d_in.p);
+	double *dout = static_cast<double *>(d_out.p);
+	if (kind < 2) hipLaunchKernelGGL(hook_sincos_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, kind, di, dout, n);
+	else hipLaunchKernelGGL(hook_logexp_lds_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, kind, di, dout, n, dev->twiddle);
+	WC_HIP(hipGetLastError());
+	WC_HIP(hipMemcpyAsync(out, d_out.p, sizeof(double) * n_out, hipMemcpyDeviceToHost, s));
+	WC_HIP(hipStreamSynchronize(s));
+	return WC_OK;
+}
+
+// interp1Q on the table y[0 .. n) with knots x0 + i dx at the m abscissae xi.  kind 0: interp1q, the reference's division;
+// 1: interp1q_rcp; 2: wf_interp1q with the table in LDS (n <= 4096).  The device forms read their table unchecked, as their callers
+// clamp: an abscissa outside [x0, x0 + (n - 1) dx] is refused here.
+int wc_debug_interp1q(int kind, double x0, double dx, const double *y, int n, long long m, const double *xi, double *out) {
+	if (kind < 0 || kind > 2 || n < 2 || m <= 0 || !y || !xi || !out || !(dx != 0.0) || (kind == 2 && n > 4096))
+		return fail(WC_ERR_INVALID, "debug interp1q: bad argument");
+	const double end = x0 + (n - 1) * dx, lo = std::fmin(x0, end), hi = std::fmax(x0, end);
+	for (long long i = 0; i < m; ++i)
+		if (!(xi[i] >= lo && xi[i] <= hi)) return fail(WC_ERR_INVALID, "debug interp1q: abscissa outside the table");
+	Device *dev = current_device();
+	if (!dev) return WC_ERR_DEVICE;
+	DeviceLock lock(dev);
+	hipStream_t s = dev->active();
+	Scoped d_y, d_xi, d_out;
+	WC_HIP(hipMalloc(&d_y.p, sizeof(double) * n));
+	WC_HIP(hipMalloc(&d_xi.p, sizeof(double) * m));
+	WC_HIP(hipMalloc(&d_out.p, sizeof(double) * m));
+	WC_HIP(hipMemcpyAsync(d_y.p, y, sizeof(double) * n, hipMemcpyHostToDevice, s));
+	WC_HIP(hipMemcpyAsync(d_xi.p, xi, sizeof(double) * m, hipMemcpyHostToDevice, s));
+	const double *dy = static_cast<const double *>(d_y.p), *dxi = static_cast<const double *>(d_xi.p);
+	double *dout = static_cast<double *>(d_out.p);
+	const dim3 grid((unsigned)std::min<long long>((m + 255) / 256, 1024));
+	const double rdx = 1.0 / dx;
+	if (kind == 0) hipLaunchKernelGGL(hook_interp1q_kernel<0>, grid, dim3(256), 0, s, x0, dx, rdx, dy, n, m, dxi, dout);
+	else if (kind == 1) hipLaunchKernelGGL(hook_interp1q_kernel<1>, grid, dim3(256), 0, s, x0, dx, rdx, dy, n, m, dxi, dout);
+	else hipLaunchKernelGGL(hook_interp1q_kernel<2>, grid, dim3(256), 0, s, x0, dx, rdx, dy, n, m, dxi, dout);
+	WC_HIP(hipGetLastError());
+	WC_HIP(hipMemcpyAsync(out, d_out.p, sizeof(double) * m, hipMemcpyDeviceToHost, s));
 	WC_HIP(hipStreamSynchronize(s));
 	return WC_OK;
 }

@@ -1062,10 +1062,13 @@ __device__ __forceinline__ double wf_exp_l(double x, const double *T) {
 	return ldexp(fma(t, p, t), ni >> 6);
 }
 
-// sin and cos of x to ~1 ulp for |x| up to ~1e5 (the phases here are a few radians): x = n pi/2 + r, |r| <= pi/4, by
-// two fused steps; the kernels are fdlibm's polynomials.  ~35 vector instructions against ~120 of ocml's sincos with
-// its large-argument path, 17 times per minimum-phase spectrum.
-__device__ __forceinline__ void wf_sincos(double x, double &sn, double &cs) {
+// sin and cos of x to 2^-52 ABSOLUTE for |x| up to 1e5 (the phases here are a few radians), within 2 ulp for |x| <= pi/4:
+// x = n pi/2 + r, |r| <= pi/4, by two fused steps; the kernels are fdlibm's polynomials.  The two steps carry about 107 bits
+// of pi/2, so next to a multiple of pi/2, where the small one of the two results is itself tiny, its RELATIVE error grows to
+// thousands of ulp (the absolute one does not); nothing here divides by such a value.  Both bounds are held on the host twin
+// by tests/test_lean_math.py, and the device is held to the twin bit for bit by tests/test_gpu_lean_math.py.  ~35 vector
+// instructions against ~120 of ocml's sincos with its large-argument path, 17 times per minimum-phase spectrum.
+__host__ __device__ __forceinline__ void wf_sincos(double x, double &sn, double &cs) {
 	const double n = rint(x * 0.63661977236758134308);
 	double r = fma(n, -1.57079632679489655800e+00, x);
 	r = fma(n, -6.12323399573676603587e-17, r);
@@ -1091,7 +1094,7 @@ __device__ __forceinline__ void wf_sincos(double x, double &sn, double &cs) {
 // sin(pi x), cos(pi x) for the window phases (|x| of a few units): the reduction x = n / 2 + r, |r| <= 1/4, is exact, so
 // the results keep sincospi's symmetries (sin(pi) = 0 exactly, ...); then wf_sincos' kernels on pi r.  ~35 vector
 // instructions against ocml's 70.
-__device__ __forceinline__ void wf_sincospi(double x, double &sn, double &cs) {
+__host__ __device__ __forceinline__ void wf_sincospi(double x, double &sn, double &cs) {
 	const double n = rint(x + x);
 	const double r = fma(n, -0.5, x) * 3.14159265358979311600e+00;  // (n / 2 and the difference are exact)
 	const int q = (int)n;
