@@ -19,6 +19,7 @@
 #include <mutex>
 
 #include "../../include/world_class_features.h"
+#include "wc_features_rows.hpp"
 #include "wc_internal.hpp"
 
 using namespace wc;
@@ -87,13 +88,6 @@ __global__ __launch_bounds__(64) void feat_lf0_kernel(const FtUtt *__restrict__ 
 			out[i] = v;
 		}
 	}
-}
-
-// the static column c < S = nd + 1 + n_ap of a row: where its order 0 stands, and the step from one order to the next
-__device__ __forceinline__ void ft_column(int c, int nd, int n_ap, int orders, int *col0, int *cstep) {
-	if (c < nd) { *col0 = c; *cstep = nd; }
-	else if (c == nd) { *col0 = orders * nd; *cstep = 1; }
-	else { *col0 = orders * (nd + 1) + 1 + (c - nd - 1); *cstep = n_ap; }
 }
 
 template <class T>
@@ -324,12 +318,6 @@ long long width_of(int nd, int n_ap, int orders) {
 	if (nd < 1 || n_ap < 0 || orders < 1 || orders > 3) return -1;
 	const long long w = (long long)orders * ((long long)nd + 1 + n_ap) + 1;
 	return w > 0x7fffffffll ? -1 : w;
-}
-
-bool overlap(const void *a, unsigned long long a_bytes, const void *b, unsigned long long b_bytes) {
-	if (!a || !b || !a_bytes || !b_bytes) return false;
-	const unsigned long long x = (unsigned long long)(uintptr_t)a, y = (unsigned long long)(uintptr_t)b;
-	return x < y + b_bytes && y < x + a_bytes;
 }
 
 // the shape arguments every call shares; *total: the frames of the batch
