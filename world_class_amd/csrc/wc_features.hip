@@ -34,8 +34,6 @@ struct FtUtt {
 constexpr int kPackFrames = 8;  // frames of one block of feat_pack_kernel
 constexpr long long kMaxFrames = 4294967295ll;
 
-__device__ __forceinline__ bool ft_voiced(double f) { return f > 0.0 && f <= DBL_MAX; }
-
 __global__ __launch_bounds__(64) void feat_lf0_kernel(const FtUtt *__restrict__ utt, const double *__restrict__ f0, double lf0_fill,
 													  double *__restrict__ lf0, int *__restrict__ right) {
 	const FtUtt u = utt[blockIdx.x];
