@@ -19,17 +19,13 @@
 #include <mutex>
 
 #include "../../include/world_class_features.h"
+#include "wc_features_batch.hpp"
 #include "wc_features_rows.hpp"
 #include "wc_internal.hpp"
 
 using namespace wc;
 
 namespace {
-
-struct FtUtt {
-	long long f_off;  // first frame in the packed arrays
-	int n, pad;
-};
 
 constexpr int kPackFrames = 8;  // frames of one block of feat_pack_kernel
 constexpr long long kMaxFrames = 4294967295ll;
@@ -318,8 +314,14 @@ long long width_of(int nd, int n_ap, int orders) {
 	return w > 0x7fffffffll ? -1 : w;
 }
 
+size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+}  // namespace
+
+namespace wc {
+
 // the shape arguments every call shares; *total: the frames of the batch
-int check_shape(const char *who, int n_utt, const int *lengths, int nd, int n_ap, int orders, int orders_min, int format, long long *total) {
+int ft_check_shape(const char *who, int n_utt, const int *lengths, int nd, int n_ap, int orders, int orders_min, int format, long long *total) {
 	const std::string w(who);
 	if (nd < 1 || n_ap < 0) return fail(WC_ERR_INVALID, w + ": nd must be at least 1 and n_ap not negative");
 	if (orders < orders_min || orders > 3) return fail(WC_ERR_INVALID, w + ": orders out of range");
@@ -338,7 +340,7 @@ int check_shape(const char *who, int n_utt, const int *lengths, int nd, int n_ap
 }
 
 // the descriptors on the device and the scratch reserved, both handed to stream s
-int prepare(Device *dev, hipStream_t s, int n_utt, const int *lengths, size_t scratch_bytes, const FtUtt **d_utt) {
+int ft_prepare(Device *dev, hipStream_t s, int n_utt, const int *lengths, size_t scratch_bytes, const FtUtt **d_utt) {
 	Staging *st;
 	{
 		std::lock_guard<std::mutex> g(g_stage_mu);
@@ -370,15 +372,13 @@ int prepare(Device *dev, hipStream_t s, int n_utt, const int *lengths, size_t sc
 	return WC_OK;
 }
 
-int finish(Device *dev, hipStream_t s) {
+int ft_finish(Device *dev, hipStream_t s) {
 	WC_HIP(hipEventRecord(dev->features_done, s));
 	dev->features_last = s;
 	return WC_OK;
 }
 
-size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-}  // namespace
+}  // namespace wc
 
 extern "C" {
 
@@ -388,7 +388,7 @@ int wc_pack_model_features_device(int n_utt, const int *lengths, int nd, int n_a
 								  const double *d_coded_ap, double lf0_fill, int out_format, void *d_rows) {
 	long long total = 0;
 	int rc;
-	if ((rc = check_shape("pack model features", n_utt, lengths, nd, n_ap, orders, 1, out_format, &total))) return rc;
+	if ((rc = ft_check_shape("pack model features", n_utt, lengths, nd, n_ap, orders, 1, out_format, &total))) return rc;
 	if (lf0_fill != lf0_fill) return fail(WC_ERR_INVALID, "pack model features: lf0_fill is NaN");
 	if (total == 0) return WC_OK;
 	if ((n_ap == 0) != (d_coded_ap == nullptr)) return fail(WC_ERR_INVALID, "pack model features: d_coded_ap is NULL exactly where n_ap is 0");
@@ -404,7 +404,7 @@ int wc_pack_model_features_device(int n_utt, const int *lengths, int nd, int n_a
 	hipStream_t s = dev->active();
 	const size_t lf0_bytes = round_up((size_t)total * sizeof(double), 16);
 	const FtUtt *d_utt = nullptr;
-	if ((rc = prepare(dev, s, n_utt, lengths, lf0_bytes + (size_t)total * sizeof(int), &d_utt))) return rc;
+	if ((rc = ft_prepare(dev, s, n_utt, lengths, lf0_bytes + (size_t)total * sizeof(int), &d_utt))) return rc;
 	double *lf0 = dev->features_scratch.as<double>();
 	int *right = reinterpret_cast<int *>(dev->features_scratch.as<char>() + lf0_bytes);
 	if ((rc = dev->time_begin("feat_lf0_kernel", s))) return rc;
@@ -421,14 +421,14 @@ int wc_pack_model_features_device(int n_utt, const int *lengths, int nd, int n_a
 						   d_coded_ap, (const double *)lf0, static_cast<double *>(d_rows));
 	WC_HIP(hipGetLastError());
 	if ((rc = dev->time_end("feat_pack_kernel", s))) return rc;
-	return finish(dev, s);
+	return ft_finish(dev, s);
 }
 
 int wc_mlpg_device(int n_utt, const int *lengths, int nd, int n_ap, int orders, int in_format, const void *d_mean, const void *d_var,
 				   int var_per_frame, double *d_static) {
 	long long total = 0;
 	int rc;
-	if ((rc = check_shape("mlpg", n_utt, lengths, nd, n_ap, orders, 2, in_format, &total))) return rc;
+	if ((rc = ft_check_shape("mlpg", n_utt, lengths, nd, n_ap, orders, 2, in_format, &total))) return rc;
 	if (var_per_frame != 0 && var_per_frame != 1) return fail(WC_ERR_INVALID, "mlpg: var_per_frame is 0 or 1");
 	if (total == 0) return WC_OK;
 	if (!d_mean || !d_var || !d_static) return fail(WC_ERR_INVALID, "mlpg: null array");
@@ -442,7 +442,7 @@ int wc_mlpg_device(int n_utt, const int *lengths, int nd, int n_ap, int orders, 
 	DeviceLock lock(dev);
 	hipStream_t s = dev->active();
 	const FtUtt *d_utt = nullptr;
-	if ((rc = prepare(dev, s, n_utt, lengths, (size_t)total * 3 * S * sizeof(double), &d_utt))) return rc;
+	if ((rc = ft_prepare(dev, s, n_utt, lengths, (size_t)total * 3 * S * sizeof(double), &d_utt))) return rc;
 	double *park = dev->features_scratch.as<double>();
 	const int groups = (int)((S + 1 + 63) / 64);
 	const long long blocks = (long long)n_utt * groups, per_launch = 1ll << 30;
@@ -458,7 +458,7 @@ int wc_mlpg_device(int n_utt, const int *lengths, int nd, int n_ap, int orders, 
 		WC_HIP(hipGetLastError());
 	}
 	if ((rc = dev->time_end("mlpg_kernel", s))) return rc;
-	return finish(dev, s);
+	return ft_finish(dev, s);
 }
 
 int wc_unpack_model_features_device(long long n_frames, int nd, int n_ap, int orders, int in_format, const void *d_rows, double vuv_threshold,
