@@ -104,6 +104,12 @@ def test_header_and_translation_unit_are_part_of_the_build():
     for unit in ("wc_features.hip", "wc_feature_stream.hip"):
         src = open(os.path.join(ROOT, "world_class_amd", "csrc", unit)).read()
         assert '#include "wc_features_rows.hpp"' in src and "bool ft_voiced(" not in src and "void ft_column(" not in src
+    # and so is the lagged ledger of the two streams: neither unit defines emitted_of itself
+    assert os.path.join(ROOT, "world_class_amd", "csrc", "wc_lag_stream.hpp") in build.headers()
+    assert "long long emitted_of(long long rows, int lag)" in open(os.path.join(ROOT, "world_class_amd", "csrc", "wc_lag_stream.hpp")).read()
+    for unit in ("wc_mlpg_stream.hip", "wc_feature_stream.hip"):
+        src = open(os.path.join(ROOT, "world_class_amd", "csrc", unit)).read()
+        assert '#include "wc_lag_stream.hpp"' in src and "long long emitted_of(" not in src
 
 
 def test_mirror_exists_with_its_parameter_names():

@@ -85,6 +85,7 @@ def test_header_and_translation_unit_are_part_of_the_build():
     assert os.path.join(ROOT, "include", HEADER) in build.headers()
     assert os.path.join(ROOT, "include", "world_class_features.h") in build.headers()
     assert "wc_mlpg_stream.hip" in build.sources() and "wc_features.hip" in build.sources()
+    assert os.path.join(ROOT, "world_class_amd", "csrc", "wc_lag_stream.hpp") in build.headers()
 
 
 def test_mirror_exists_with_its_parameter_names():

@@ -438,9 +438,7 @@ struct wc_align_stream {
 	int max_lag = 0, ring_cap = 0;  // 0: no reservation
 	// the descriptors of a push: AlPair, then AsWork per plain stream with rows | AwWork per windowed stream with rows | SeWork per
 	// stream with rows of a settled push; of a tail: SeWork per wanted stream
-	DevBuf drec;
-	HostBuf h_rec[2];          // their page-locked staging: a pair, so that a push waits for the copy of the push before the last only
-	int parity = 0;
+	RecPair rec;
 };
 
 namespace {
@@ -482,8 +480,7 @@ wc_align_stream *wc_align_stream_create(int dims, int dim_begin, int dim_end, in
 	h->track_m.assign(n_tracks, 0);
 	const size_t rec = (std::max(sizeof(AlPair) + sizeof(AsWork), sizeof(AwWork)) + sizeof(SeWork)) * (size_t)n_streams;
 	if (h->wrec.reserve(sizeof(AwRec) * (size_t)n_streams) || h->tracks.reserve(sizeof(double) * (size_t)track_rows * dims) || h->d.reserve(sizeof(double) * (size_t)sr * max_track_frames) ||
-		h->state.reserve(sizeof(double) * (size_t)2 * n_streams * max_track_frames) || h->drec.reserve(rec) || h->h_rec[0].reserve(rec) ||
-		h->h_rec[1].reserve(rec)) {
+		h->state.reserve(sizeof(double) * (size_t)2 * n_streams * max_track_frames) || h->rec.reserve(rec)) {
 		wc_align_stream_destroy(h);
 		return nullptr;
 	}
@@ -493,7 +490,7 @@ wc_align_stream *wc_align_stream_create(int dims, int dim_begin, int dim_end, in
 void wc_align_stream_destroy(wc_align_stream *h) {
 	if (!h) return;
 	h->dev->quiesce();
-	h->tracks.release(); h->d.release(); h->state.release(); h->wrec.release(); h->ring.release(); h->lastpos.release(); h->drec.release(); h->h_rec[0].release(); h->h_rec[1].release();
+	h->tracks.release(); h->d.release(); h->state.release(); h->wrec.release(); h->ring.release(); h->lastpos.release(); h->rec.release();
 	delete h;
 }
 
@@ -546,8 +543,8 @@ int as_push(wc_align_stream *h, const int *n_rows, const double *d_feat_a, doubl
 	if (total == 0) return WC_OK;
 	if (!d_feat_a || !d_position || !d_cost || (settle && !d_settled)) return fail(WC_ERR_INVALID, "align stream push: null array");
 	// ---- the descriptors (no refusal is left) ----
-	if (h->h_rec[h->parity].reserve(0)) return WC_ERR_DEVICE;  // (the copy of the push before the last has read this staging)
-	AlPair *pairs = h->h_rec[h->parity].as<AlPair>();
+	AlPair *pairs = h->rec.begin<AlPair>();
+	if (!pairs) return WC_ERR_DEVICE;
 	AsWork *work = reinterpret_cast<AsWork *>(pairs + plain);
 	AwWork *wwork = reinterpret_cast<AwWork *>(work + plain);
 	SeWork *swork = reinterpret_cast<SeWork *>(wwork + windowed);
@@ -598,9 +595,8 @@ int as_push(wc_align_stream *h, const int *n_rows, const double *d_feat_a, doubl
 	hipStream_t hs = h->dev->active();
 	int rc;
 	const size_t bytes = (sizeof(AlPair) + sizeof(AsWork)) * (size_t)plain + sizeof(AwWork) * (size_t)windowed + sizeof(SeWork) * (size_t)settled;
-	WC_HIP(hipMemcpyAsync(h->drec.p, pairs, bytes, hipMemcpyHostToDevice, hs));
-	if ((rc = h->h_rec[h->parity].mark(hs))) return rc;
-	const AlPair *d_pairs = h->drec.as<AlPair>();
+	const AlPair *d_pairs;
+	if ((rc = h->rec.upload(hs, bytes, &d_pairs))) return rc;
 	const AsWork *d_work = reinterpret_cast<const AsWork *>(d_pairs + plain);
 	if (plain > 0) {
 		AlArgs a = {};
@@ -655,7 +651,6 @@ int as_push(wc_align_stream *h, const int *n_rows, const double *d_feat_a, doubl
 		s.rows += n_rows[u];
 		s.parity ^= (int)(passes & 1);
 	}
-	h->parity = 1 - h->parity;
 	return WC_OK;
 }
 
@@ -717,8 +712,8 @@ int wc_align_stream_tail_device(wc_align_stream *h, const int *want, double *d_t
 		++count;
 	}
 	if (count == 0) return WC_OK;
-	if (h->h_rec[h->parity].reserve(0)) return WC_ERR_DEVICE;
-	SeWork *work = h->h_rec[h->parity].as<SeWork>();
+	SeWork *work = h->rec.begin<SeWork>();
+	if (!work) return WC_ERR_DEVICE;
 	long long off = 0;
 	int k = 0;
 	for (int u = 0; u < h->n_streams; ++u) {
@@ -733,17 +728,14 @@ int wc_align_stream_tail_device(wc_align_stream *h, const int *want, double *d_t
 	WC_HIP(hipSetDevice(h->dev->id));
 	hipStream_t hs = h->dev->active();
 	int rc;
-	WC_HIP(hipMemcpyAsync(h->drec.p, work, sizeof(SeWork) * (size_t)count, hipMemcpyHostToDevice, hs));
-	if ((rc = h->h_rec[h->parity].mark(hs))) return rc;
 	SeArgs x = {};
-	x.work = h->drec.as<SeWork>();
+	if ((rc = h->rec.upload(hs, sizeof(SeWork) * (size_t)count, &x.work))) return rc;
 	x.n_work = count; x.max_m = h->max_m; x.ring_cap = h->ring_cap;
 	x.lastpos = h->lastpos.as<int>(); x.out = d_tail;
 	if ((rc = h->dev->time_begin("align_stream_tail_kernel", hs))) return rc;
 	hipLaunchKernelGGL(align_stream_tail_kernel, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, hs, x);
 	WC_HIP(hipGetLastError());
 	if ((rc = h->dev->time_end("align_stream_tail_kernel", hs))) return rc;
-	h->parity = 1 - h->parity;
 	return WC_OK;
 }
 

@@ -23,6 +23,7 @@
 #include "../../include/world_class_feature_stream.h"
 #include "wc_features_rows.hpp"
 #include "wc_internal.hpp"
+#include "wc_lag_stream.hpp"
 
 using namespace wc;
 
@@ -203,11 +204,8 @@ __global__ __launch_bounds__(256) void feat_stream_pack_kernel(const FsDesc *__r
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
-struct FsState {
-	int lag = -1;  // -1: never reset
-	bool ended = false;
+struct FsState : LagState {
 	double fill = 0.0;
-	long long rows = 0, emitted = 0;
 };
 
 constexpr char kName[] = "feature stream";
@@ -215,31 +213,21 @@ int refuse(const std::string &what) { return fail(WC_ERR_INVALID, std::string(kN
 
 }  // namespace
 
-struct wc_feature_stream {
+struct wc_feature_stream : LagLedger<FsState> {
 	Device *dev = nullptr;
-	int n_streams = 0, nd = 0, n_ap = 0, orders = 0, max_rows = 0, max_lag = 0;
+	int nd = 0, n_ap = 0, orders = 0;
 	// Ring slots are the absolute row index modulo cap = max_lag + max_rows_per_push + 1.  A push from T0 to T1 rows at lag L scans
 	// rows T0 - L - 1 .. T1 - 1, the row before its first emitted frame up to its newest: at most max_lag + max_rows_per_push + 1 of
 	// them, none of which shares a slot with the rows T0 .. T1 - 1 it writes.  A flush scans rows n - L - 1 .. n - 1.
-	int cap = 0;
-	std::vector<FsState> st;
 	DevBuf ring;     // n_streams x cap x S doubles: the coded envelope, the parked log of F0 (NaN: unvoiced), the coded aperiodicity
 	DevBuf carried;  // n_streams records
 	DevBuf right;    // n_streams x cap ints: the suffix min-scan of a call, read back by the lane that wrote it
 	DevBuf triples;  // n_streams x max(max_rows_per_push, max_lag) x 3 doubles: the continuous log-F0 of an emitted frame and its neighbours
-	DevBuf drec;     // the descriptors of a call
-	HostBuf h_rec[2];  // a pair: a call waits for the copy of the call before the last only
-	int parity = 0;
-	void release_all() {
-		ring.release(); carried.release(); right.release(); triples.release(); drec.release(); h_rec[0].release(); h_rec[1].release();
-	}
+	RecPair rec;     // the descriptors of a call
+	void release_all() { ring.release(); carried.release(); right.release(); triples.release(); rec.release(); }
 };
 
 namespace {
-
-bool stream_ok(const wc_feature_stream *h, int stream) { return h && stream >= 0 && stream < h->n_streams; }
-
-long long emitted_of(long long rows, int lag) { return rows < 0 || lag < 0 ? -1 : (rows > lag ? rows - lag : 0); }
 
 // what both calls fill of a descriptor: the window and the frames of a stream that stands at `rows` rows behind this call
 void window(const wc_feature_stream *h, const FsState &s, long long rows, int n_out, FsDesc *d) {
@@ -254,16 +242,14 @@ void window(const wc_feature_stream *h, const FsState &s, long long rows, int n_
 }
 
 // the descriptors up in one copy, then the two kernels
-int enqueue(wc_feature_stream *h, HostBuf &hb, size_t n_desc, long long total_out, const double *d_f0, const double *d_sp, const double *d_ap,
+int enqueue(wc_feature_stream *h, size_t n_desc, long long total_out, const double *d_f0, const double *d_sp, const double *d_ap,
 			int out_format, void *d_rows) {
 	Device *dev = h->dev;
 	WC_HIP(hipSetDevice(dev->id));
 	hipStream_t s = dev->active();
-	WC_HIP(hipMemcpyAsync(h->drec.p, hb.p, sizeof(FsDesc) * n_desc, hipMemcpyHostToDevice, s));
+	const FsDesc *d_desc;
 	int rc;
-	if ((rc = hb.mark(s))) return rc;
-	h->parity = 1 - h->parity;
-	const FsDesc *d_desc = h->drec.as<FsDesc>();
+	if ((rc = h->rec.upload(s, sizeof(FsDesc) * n_desc, &d_desc))) return rc;
 	if ((rc = dev->time_begin("feat_stream_scan_kernel", s))) return rc;
 	hipLaunchKernelGGL(feat_stream_scan_kernel, dim3((unsigned)n_desc), dim3(64), 0, s, d_desc, h->nd, h->n_ap, h->cap, d_f0, d_sp, d_ap,
 					   h->ring.as<double>(), h->carried.as<FsCarry>(), h->right.as<int>(), h->triples.as<double>());
@@ -292,28 +278,23 @@ long long wc_feature_stream_emitted(long long rows, int lag) { return emitted_of
 
 wc_feature_stream *wc_feature_stream_create(int n_streams, int nd, int n_ap, int orders, int max_rows_per_push, int max_lag) {
 	const auto no = [](const char *why) { set_error(std::string(kName) + why); return (wc_feature_stream *)nullptr; };
-	if (nd < 1 || n_ap < 0) return no(": nd must be at least 1 and n_ap not negative");
+	const unsigned long long S = (unsigned long long)nd + 1 + n_ap;  // doubles of a ring row
+	if (const char *why = lag_check_dims(nd, n_ap)) return no(why);
 	if (orders < 1 || orders > 3) return no(": orders is 1, 2 or 3");
-	if (wc_model_feature_width(nd, n_ap, orders) < 0) return no(": the row width leaves 31 bits");
-	if (n_streams < 1 || max_rows_per_push < 1) return no(": n_streams and max_rows_per_push must be at least 1");
-	if (max_lag < 0) return no(": max_lag must not be negative");
-	// in 64 bits; under the bound the items of a take (max_rows_per_push x S), the triples and the block counts stay far below 2^31
-	const unsigned long long S = (unsigned long long)nd + 1 + n_ap, cap = (unsigned long long)max_lag + max_rows_per_push + 1;
-	const unsigned long long ring_bytes = 8ull * S * cap;  // of one stream; within 64 bits for S and cap up to 2^27 each, which are looked at first
-	if (S > (1ull << 27) || cap > (1ull << 27) || ring_bytes > (1ull << 30) || ring_bytes * (unsigned long long)n_streams > (1ull << 30))
-		return no(": the ring exceeds 2^30 bytes");
+	// (under the ring's bound the items of a take (max_rows_per_push x S), the triples and the block counts stay far below 2^31)
+	if (const char *why = lag_check_create(wc_model_feature_width(nd, n_ap, orders), n_streams, max_rows_per_push, max_lag, S)) return no(why);
 	Device *dev = current_device();
 	if (!dev) return nullptr;
 	DeviceLock lock(dev);
 	wc_feature_stream *h = new wc_feature_stream();
 	h->dev = dev;
-	h->n_streams = n_streams; h->nd = nd; h->n_ap = n_ap; h->orders = orders; h->max_rows = max_rows_per_push; h->max_lag = max_lag;
-	h->cap = (int)cap;
-	h->st.resize((size_t)n_streams);
+	h->init(n_streams, max_rows_per_push, max_lag);
+	h->nd = nd; h->n_ap = n_ap; h->orders = orders;
+	const size_t cap = (size_t)h->cap, ring_bytes = sizeof(double) * (size_t)S * cap;  // of one stream
 	const size_t rec = sizeof(FsDesc) * (size_t)n_streams, most = (size_t)std::max(max_rows_per_push, max_lag);
 	if (h->ring.reserve((size_t)ring_bytes * (size_t)n_streams) || h->carried.reserve(sizeof(FsCarry) * (size_t)n_streams) ||
 		h->right.reserve(sizeof(int) * (size_t)cap * (size_t)n_streams) || h->triples.reserve(sizeof(double) * 3 * most * (size_t)n_streams) ||
-		h->drec.reserve(rec) || h->h_rec[0].reserve(rec) || h->h_rec[1].reserve(rec)) {
+		h->rec.reserve(rec)) {
 		h->release_all();
 		delete h;
 		return nullptr;
@@ -344,8 +325,7 @@ void wc_feature_stream_destroy(wc_feature_stream *h) {
 }
 
 int wc_feature_stream_reset(wc_feature_stream *h, int stream, int lag, double lf0_fill) {
-	if (!stream_ok(h, stream)) return refuse(" reset: bad stream index");
-	if (lag < 0 || lag > h->max_lag) return refuse(" reset: a lag outside 0 .. max_lag");
+	if (const char *why = lag_check_reset(h, stream, lag)) return refuse(why);
 	if (lf0_fill != lf0_fill) return refuse(" reset: lf0_fill is NaN");
 	DeviceLock lock(h->dev);
 	FsState &s = h->st[stream];
@@ -361,14 +341,8 @@ int wc_feature_stream_push_device(wc_feature_stream *h, const int *n_rows, const
 	if (out_format != WC_FEAT_F64 && out_format != WC_FEAT_F32) return refuse(" push: the format is 0 (double) or 1 (float)");
 	DeviceLock lock(h->dev);
 	const int n = h->n_streams;
-	long long total_rows = 0, total_out = 0;
-	for (int u = 0; u < n; ++u) {
-		const FsState &s = h->st[u];
-		if (n_rows[u] < 0 || n_rows[u] > h->max_rows) return refuse(" push: a count outside 0 .. max_rows_per_push");
-		if (n_rows[u] > 0 && (s.lag < 0 || s.ended)) return refuse(" push: rows for a stream that was never reset or has ended (reset it first)");
-		total_rows += n_rows[u];
-		if (n_rows[u] > 0) total_out += emitted_of(s.rows + n_rows[u], s.lag) - s.emitted;
-	}
+	long long total_rows, total_out;
+	if (const char *why = h->scan_push(n_rows, &total_rows, &total_out)) return refuse(why);
 	if (total_rows > 0 && (h->n_ap == 0) != (d_coded_ap == nullptr)) return refuse(" push: d_coded_ap is NULL exactly where n_ap is 0");
 	if (total_rows > 0 && (!d_f0 || !d_coded_sp)) return refuse(" push: null array");
 	if (total_out > 0 && !d_rows) return refuse(" push: null array");
@@ -378,18 +352,16 @@ int wc_feature_stream_push_device(wc_feature_stream *h, const int *n_rows, const
 		overlap(d_rows, out_bytes, d_coded_ap, 8ull * rows_in * h->n_ap))
 		return refuse(" push: d_rows overlaps an input");
 	// ---- no refusal is left: the descriptors ----
-	HostBuf &hb = h->h_rec[h->parity];
-	if (total_rows > 0 && hb.reserve(0)) return WC_ERR_DEVICE;  // (the copy of the call before the last has read this staging)
-	FsDesc *desc = hb.as<FsDesc>();
+	FsDesc *desc = total_rows > 0 ? h->rec.begin<FsDesc>() : nullptr;  // (an empty call waits for nothing)
+	if (total_rows > 0 && !desc) return WC_ERR_DEVICE;
 	size_t n_desc = 0;
 	long long in_off = 0, out_off = 0;
 	for (int u = 0; u < n; ++u) {
 		const FsState &s = h->st[u];
 		const int k = n_rows[u];
-		frames_out[u] = 0;
+		frames_out[u] = h->push_frames(u, k);
 		if (k == 0) continue;
 		const long long rows = s.rows + k;
-		frames_out[u] = (int)(emitted_of(rows, s.lag) - s.emitted);
 		FsDesc &d = desc[n_desc++];
 		window(h, s, rows, frames_out[u], &d);
 		d.in_off = in_off; d.out_off = out_off;
@@ -402,12 +374,8 @@ int wc_feature_stream_push_device(wc_feature_stream *h, const int *n_rows, const
 	}
 	if (n_desc == 0) return WC_OK;
 	int rc;
-	if ((rc = enqueue(h, hb, n_desc, total_out, d_f0, d_coded_sp, d_coded_ap, out_format, d_rows))) return rc;
-	for (int u = 0; u < n; ++u) {
-		FsState &s = h->st[u];
-		s.rows += n_rows[u];
-		s.emitted += frames_out[u];
-	}
+	if ((rc = enqueue(h, n_desc, total_out, d_f0, d_coded_sp, d_coded_ap, out_format, d_rows))) return rc;
+	h->commit_push(n_rows, frames_out);
 	return WC_OK;
 }
 
@@ -416,23 +384,17 @@ int wc_feature_stream_flush_device(wc_feature_stream *h, const int *want, int ou
 	if (out_format != WC_FEAT_F64 && out_format != WC_FEAT_F32) return refuse(" flush: the format is 0 (double) or 1 (float)");
 	DeviceLock lock(h->dev);
 	const int n = h->n_streams;
-	long long total_out = 0;
-	for (int u = 0; u < n; ++u) {
-		const FsState &s = h->st[u];
-		if (!want[u]) continue;
-		if (s.lag < 0 || s.ended) return refuse(" flush: a wanted stream was never reset or has ended");
-		total_out += s.rows - s.emitted;
-	}
+	long long total_out;
+	if (const char *why = h->scan_flush(want, &total_out)) return refuse(why);
 	if (total_out > 0 && !d_rows) return refuse(" flush: null array");
 	// ---- no refusal is left: the same two kernels, nothing taken, every frame's prefix ending at the last row ----
-	HostBuf &hb = h->h_rec[h->parity];
-	if (total_out > 0 && hb.reserve(0)) return WC_ERR_DEVICE;
-	FsDesc *desc = hb.as<FsDesc>();
+	FsDesc *desc = total_out > 0 ? h->rec.begin<FsDesc>() : nullptr;
+	if (total_out > 0 && !desc) return WC_ERR_DEVICE;
 	size_t n_desc = 0;
 	long long out_off = 0;
 	for (int u = 0; u < n; ++u) {
 		const FsState &s = h->st[u];
-		frames_out[u] = want[u] ? (int)(s.rows - s.emitted) : 0;  // min(lag, rows)
+		frames_out[u] = h->flush_frames(u, want[u]);
 		if (frames_out[u] == 0) continue;
 		FsDesc &d = desc[n_desc++];
 		window(h, s, s.rows, frames_out[u], &d);
@@ -443,21 +405,17 @@ int wc_feature_stream_flush_device(wc_feature_stream *h, const int *want, int ou
 	}
 	if (n_desc) {
 		int rc;
-		if ((rc = enqueue(h, hb, n_desc, total_out, nullptr, nullptr, nullptr, out_format, d_rows))) return rc;
+		if ((rc = enqueue(h, n_desc, total_out, nullptr, nullptr, nullptr, out_format, d_rows))) return rc;
 	}
-	for (int u = 0; u < n; ++u) {
-		if (!want[u]) continue;
-		h->st[u].emitted += frames_out[u];
-		h->st[u].ended = true;
-	}
+	h->commit_flush(want, frames_out);
 	return WC_OK;
 }
 
-int wc_feature_stream_max_frames_per_push(const wc_feature_stream *h) { return h ? h->max_rows : WC_ERR_INVALID; }
-int wc_feature_stream_max_frames_per_flush(const wc_feature_stream *h) { return h ? h->max_lag : WC_ERR_INVALID; }
+int wc_feature_stream_max_frames_per_push(const wc_feature_stream *h) { return lag_max_frames_per_push(h, WC_ERR_INVALID); }
+int wc_feature_stream_max_frames_per_flush(const wc_feature_stream *h) { return lag_max_frames_per_flush(h, WC_ERR_INVALID); }
 
-long long wc_feature_stream_rows_received(const wc_feature_stream *h, int stream) { return stream_ok(h, stream) ? h->st[stream].rows : -1; }
-long long wc_feature_stream_frames_emitted(const wc_feature_stream *h, int stream) { return stream_ok(h, stream) ? h->st[stream].emitted : -1; }
-int wc_feature_stream_get_lag(const wc_feature_stream *h, int stream) { return stream_ok(h, stream) ? h->st[stream].lag : -1; }
+long long wc_feature_stream_rows_received(const wc_feature_stream *h, int stream) { return lag_rows_received(h, stream); }
+long long wc_feature_stream_frames_emitted(const wc_feature_stream *h, int stream) { return lag_frames_emitted(h, stream); }
+int wc_feature_stream_get_lag(const wc_feature_stream *h, int stream) { return lag_get_lag(h, stream); }
 
 }  // extern "C"

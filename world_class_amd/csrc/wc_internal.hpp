@@ -43,6 +43,29 @@ struct HostBuf {
 	template <class T> T *as() const { return static_cast<T *>(p); }
 };
 
+// The records of a stream handle's call and their way to the device: one device buffer and two page-locked stagings that take turns --
+// a pair, so that a call waits for the copy of the call before the last only.  A call that has something to upload waits for the
+// staging whose turn it is and takes its pointer (begin), writes its records there, and sends the used prefix up with one asynchronous
+// copy (upload), which records the staging's event and hands the turn to the other one.  Nothing reads "the staging of this call"
+// through the pair behind upload: the caller keeps the pointer begin gave it.
+struct RecPair {
+	DevBuf d;
+	HostBuf h[2];
+	int parity = 0;  // whose turn it is
+	int reserve(size_t bytes) { return d.reserve(bytes) || h[0].reserve(bytes) || h[1].reserve(bytes); }  // 0 on success
+	void release() { d.release(); h[0].release(); h[1].release(); }
+	// nullptr on failure (the error is set); with a byte count, this call's staging and the device buffer grow to it first
+	template <class T> T *begin(size_t bytes = 0) { return h[parity].reserve(bytes) || d.reserve(bytes) ? nullptr : h[parity].as<T>(); }
+	template <class T> int upload(hipStream_t s, size_t bytes, const T **on_device) {
+		HostBuf &hb = h[parity];
+		WC_HIP(hipMemcpyAsync(d.p, hb.p, bytes, hipMemcpyHostToDevice, s));
+		if (int rc = hb.mark(s)) return rc;
+		parity = 1 - parity;
+		*on_device = d.as<T>();
+		return WC_OK;
+	}
+};
+
 // host arrays <-> one packed device array: page-locked staging and its device twin (wc_batch.hip)
 struct Staging {
 	HostBuf h;

@@ -20,6 +20,7 @@
 #include "../../include/world_class_mlpg_stream.h"
 #include "wc_features_rows.hpp"
 #include "wc_internal.hpp"
+#include "wc_lag_stream.hpp"
 
 using namespace wc;
 
@@ -237,11 +238,8 @@ __global__ __launch_bounds__(64) void mlpg_stream_back_kernel(const MsBack *__re
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
-struct MsState {
-	int lag = -1;  // -1: never reset
+struct MsState : LagState {
 	int half = 0;  // where of its pair the carried state stands
-	bool ended = false;
-	long long rows = 0, emitted = 0;
 };
 
 constexpr char kName[] = "mlpg stream";
@@ -249,41 +247,32 @@ int refuse(const std::string &what) { return fail(WC_ERR_INVALID, std::string(kN
 
 }  // namespace
 
-struct wc_mlpg_stream {
+struct wc_mlpg_stream : LagLedger<MsState> {
 	Device *dev = nullptr;
-	int n_streams = 0, nd = 0, n_ap = 0, orders = 0, max_rows = 0, max_lag = 0;
+	int nd = 0, n_ap = 0, orders = 0;
 	// Ring slots are the absolute row index modulo cap = max_lag + max_rows_per_push + 1.  A push from T0 to T1 rows at lag L reads
 	// rows T0 - L .. T1 - 1 in its walks, at most max_lag + max_rows_per_push of them, and its forward kernel writes the final z / d of
 	// the carried row T0 - 1, which lies below that range when L is 0: the one slot of margin keeps row T0 - 1 apart from row T1 - 1
 	// then.  A flush reads rows n - L .. n - 1.
-	int cap = 0;
-	std::vector<MsState> st;
 	DevBuf state;  // n_streams x 2 halves x kFields x S doubles
 	DevBuf ring;   // n_streams x cap x (4 S + 1) doubles: l1, l2, z / d, z_end / d_end of every static column, vuv
-	DevBuf drec;   // the forward descriptors of a push, then its walks
-	HostBuf h_rec[2];  // a pair: a call waits for the copy of the call before the last only
-	int parity = 0;
+	RecPair rec;   // the forward descriptors of a push, then its walks
+	void release_all() { state.release(); ring.release(); rec.release(); }
 };
 
 namespace {
 
-bool stream_ok(const wc_mlpg_stream *h, int stream) { return h && stream >= 0 && stream < h->n_streams; }
-
-long long emitted_of(long long rows, int lag) { return rows < 0 || lag < 0 ? -1 : (rows > lag ? rows - lag : 0); }
-
 // the descriptors up in one copy, then the kernels: the forward kernel where rows were pushed, the back kernel where frames come out
-int enqueue(wc_mlpg_stream *h, HostBuf &hb, size_t n_fwd, size_t n_back, int in_format, const void *d_mean, const void *d_var, int var_per_frame,
+int enqueue(wc_mlpg_stream *h, size_t n_fwd, size_t n_back, int in_format, const void *d_mean, const void *d_var, int var_per_frame,
 			double *d_static) {
 	Device *dev = h->dev;
 	WC_HIP(hipSetDevice(dev->id));
 	hipStream_t s = dev->active();
 	const size_t bytes = sizeof(MsFwd) * n_fwd + sizeof(MsBack) * n_back;
-	WC_HIP(hipMemcpyAsync(h->drec.p, hb.p, bytes, hipMemcpyHostToDevice, s));
+	const MsFwd *d_fwd;
 	int rc;
-	if ((rc = hb.mark(s))) return rc;
-	h->parity = 1 - h->parity;
+	if ((rc = h->rec.upload(s, bytes, &d_fwd))) return rc;
 	const int S = h->nd + 1 + h->n_ap, groups = (S + 1 + 63) / 64;
-	const MsFwd *d_fwd = h->drec.as<MsFwd>();
 	const MsBack *d_back = reinterpret_cast<const MsBack *>(d_fwd + n_fwd);
 	if (n_fwd) {
 		if ((rc = dev->time_begin("mlpg_stream_forward_kernel", s))) return rc;
@@ -316,29 +305,22 @@ long long wc_mlpg_stream_emitted(long long rows, int lag) { return emitted_of(ro
 
 wc_mlpg_stream *wc_mlpg_stream_create(int n_streams, int nd, int n_ap, int orders, int max_rows_per_push, int max_lag) {
 	const auto no = [](const char *why) { set_error(std::string(kName) + why); return (wc_mlpg_stream *)nullptr; };
-	if (nd < 1 || n_ap < 0) return no(": nd must be at least 1 and n_ap not negative");
+	const unsigned long long S = (unsigned long long)nd + 1 + n_ap, row = 4 * S + 1;  // doubles of a ring row
+	if (const char *why = lag_check_dims(nd, n_ap)) return no(why);
 	if (orders < 2 || orders > 3) return no(": orders is 2 or 3");
-	if (wc_model_feature_width(nd, n_ap, orders) < 0) return no(": the row width leaves 31 bits");
-	if (n_streams < 1 || max_rows_per_push < 1) return no(": n_streams and max_rows_per_push must be at least 1");
-	if (max_lag < 0) return no(": max_lag must not be negative");
-	// in 64 bits; under the bound the descriptor and block counts of a push (n_streams x max_rows_per_push walks, each over
-	// (S + 1 + 63) / 64 blocks) stay far below 2^31 as well
-	const unsigned long long S = (unsigned long long)nd + 1 + n_ap, cap = (unsigned long long)max_lag + max_rows_per_push + 1;
-	const unsigned long long ring_bytes = 8ull * (4 * S + 1) * cap;  // of one stream; within 64 bits for S and cap up to 2^27 each, which are looked at first
-	if (S > (1ull << 27) || cap > (1ull << 27) || ring_bytes > (1ull << 30) || ring_bytes * (unsigned long long)n_streams > (1ull << 30))
-		return no(": the ring exceeds 2^30 bytes");
+	// (under the ring's bound a push's n_streams x max_rows_per_push walks, each over (S + 1 + 63) / 64 blocks, stay far below 2^31)
+	if (const char *why = lag_check_create(wc_model_feature_width(nd, n_ap, orders), n_streams, max_rows_per_push, max_lag, row)) return no(why);
 	Device *dev = current_device();
 	if (!dev) return nullptr;
 	DeviceLock lock(dev);
 	wc_mlpg_stream *h = new wc_mlpg_stream();
 	h->dev = dev;
-	h->n_streams = n_streams; h->nd = nd; h->n_ap = n_ap; h->orders = orders; h->max_rows = max_rows_per_push; h->max_lag = max_lag;
-	h->cap = (int)cap;
-	h->st.resize((size_t)n_streams);
+	h->init(n_streams, max_rows_per_push, max_lag);
+	h->nd = nd; h->n_ap = n_ap; h->orders = orders;
 	const size_t rec = (size_t)n_streams * (sizeof(MsFwd) + sizeof(MsBack) * (size_t)max_rows_per_push);
-	if (h->state.reserve(sizeof(double) * 2 * kFields * (size_t)S * (size_t)n_streams) || h->ring.reserve((size_t)ring_bytes * (size_t)n_streams) ||
-		h->drec.reserve(rec) || h->h_rec[0].reserve(rec) || h->h_rec[1].reserve(rec)) {
-		h->state.release(); h->ring.release(); h->drec.release(); h->h_rec[0].release(); h->h_rec[1].release();
+	if (h->state.reserve(sizeof(double) * 2 * kFields * (size_t)S * (size_t)n_streams) || h->ring.reserve(sizeof(double) * (size_t)row * (size_t)h->cap * (size_t)n_streams) ||
+		h->rec.reserve(rec)) {
+		h->release_all();
 		delete h;
 		return nullptr;
 	}
@@ -348,13 +330,12 @@ wc_mlpg_stream *wc_mlpg_stream_create(int n_streams, int nd, int n_ap, int order
 void wc_mlpg_stream_destroy(wc_mlpg_stream *h) {
 	if (!h) return;
 	h->dev->quiesce();
-	h->state.release(); h->ring.release(); h->drec.release(); h->h_rec[0].release(); h->h_rec[1].release();
+	h->release_all();
 	delete h;
 }
 
 int wc_mlpg_stream_reset(wc_mlpg_stream *h, int stream, int lag) {
-	if (!stream_ok(h, stream)) return refuse(" reset: bad stream index");
-	if (lag < 0 || lag > h->max_lag) return refuse(" reset: a lag outside 0 .. max_lag");
+	if (const char *why = lag_check_reset(h, stream, lag)) return refuse(why);
 	DeviceLock lock(h->dev);
 	MsState &s = h->st[stream];
 	const int half = s.half;  // (neither the state nor the ring is cleared: a stream with no rows reads neither, and no walk goes below row 0)
@@ -371,14 +352,8 @@ int wc_mlpg_stream_push_device(wc_mlpg_stream *h, const int *n_rows, int in_form
 	if (var_per_frame != 0 && var_per_frame != 1) return refuse(" push: var_per_frame is 0 or 1");
 	DeviceLock lock(h->dev);
 	const int n = h->n_streams;
-	long long total_rows = 0, total_out = 0;
-	for (int u = 0; u < n; ++u) {
-		const MsState &s = h->st[u];
-		if (n_rows[u] < 0 || n_rows[u] > h->max_rows) return refuse(" push: a count outside 0 .. max_rows_per_push");
-		if (n_rows[u] > 0 && (s.lag < 0 || s.ended)) return refuse(" push: rows for a stream that was never reset or has ended (reset it first)");
-		total_rows += n_rows[u];
-		if (n_rows[u] > 0) total_out += emitted_of(s.rows + n_rows[u], s.lag) - s.emitted;
-	}
+	long long total_rows, total_out;
+	if (const char *why = h->scan_push(n_rows, &total_rows, &total_out)) return refuse(why);
 	if (total_rows > 0 && (!d_mean || !d_var)) return refuse(" push: null array");
 	if (total_out > 0 && !d_static) return refuse(" push: null array");
 	const unsigned long long W = (unsigned long long)wc_model_feature_width(h->nd, h->n_ap, h->orders), esz = in_format == WC_FEAT_F32 ? 4 : 8;
@@ -387,10 +362,9 @@ int wc_mlpg_stream_push_device(wc_mlpg_stream *h, const int *n_rows, int in_form
 		overlap(d_static, out_bytes, d_var, (var_per_frame ? (unsigned long long)total_rows : (total_rows ? 1ull : 0ull)) * W * esz))
 		return refuse(" push: d_static overlaps an input");
 	// ---- no refusal is left: the descriptors ----
-	HostBuf &hb = h->h_rec[h->parity];
-	if (total_rows > 0 && hb.reserve(0)) return WC_ERR_DEVICE;  // (the copy of the call before the last has read this staging)
+	MsFwd *fwd = total_rows > 0 ? h->rec.begin<MsFwd>() : nullptr;  // (an empty call waits for nothing)
+	if (total_rows > 0 && !fwd) return WC_ERR_DEVICE;
 	std::vector<MsBack> walks;
-	MsFwd *fwd = hb.as<MsFwd>();
 	size_t n_fwd = 0;
 	long long in_off = 0, out_off = 0;
 	for (int u = 0; u < n; ++u) {
@@ -418,14 +392,10 @@ int wc_mlpg_stream_push_device(wc_mlpg_stream *h, const int *n_rows, int in_form
 	if (n_fwd == 0) return WC_OK;
 	std::copy(walks.begin(), walks.end(), reinterpret_cast<MsBack *>(fwd + n_fwd));
 	int rc;
-	if ((rc = enqueue(h, hb, n_fwd, walks.size(), in_format, d_mean, d_var, var_per_frame, d_static))) return rc;
-	for (int u = 0; u < n; ++u) {
-		MsState &s = h->st[u];
-		if (n_rows[u] == 0) continue;
-		s.rows += n_rows[u];
-		s.emitted += frames_out[u];
-		s.half = 1 - s.half;
-	}
+	if ((rc = enqueue(h, n_fwd, walks.size(), in_format, d_mean, d_var, var_per_frame, d_static))) return rc;
+	h->commit_push(n_rows, frames_out);
+	for (int u = 0; u < n; ++u)
+		if (n_rows[u] > 0) h->st[u].half = 1 - h->st[u].half;
 	return WC_OK;
 }
 
@@ -433,23 +403,17 @@ int wc_mlpg_stream_flush_device(wc_mlpg_stream *h, const int *want, double *d_st
 	if (!h || !want || !frames_out) return refuse(" flush: null argument");
 	DeviceLock lock(h->dev);
 	const int n = h->n_streams;
-	long long total_out = 0;
-	for (int u = 0; u < n; ++u) {
-		const MsState &s = h->st[u];
-		if (!want[u]) continue;
-		if (s.lag < 0 || s.ended) return refuse(" flush: a wanted stream was never reset or has ended");
-		total_out += s.rows - s.emitted;
-	}
+	long long total_out;
+	if (const char *why = h->scan_flush(want, &total_out)) return refuse(why);
 	if (total_out > 0 && !d_static) return refuse(" flush: null array");
 	// ---- no refusal is left: a walk per stream with rows that wait ----
-	HostBuf &hb = h->h_rec[h->parity];
-	if (total_out > 0 && hb.reserve(0)) return WC_ERR_DEVICE;
-	MsBack *walks = hb.as<MsBack>();
+	MsBack *walks = total_out > 0 ? h->rec.begin<MsBack>() : nullptr;
+	if (total_out > 0 && !walks) return WC_ERR_DEVICE;
 	size_t n_back = 0;
 	long long out_off = 0;
 	for (int u = 0; u < n; ++u) {
 		const MsState &s = h->st[u];
-		frames_out[u] = want[u] ? (int)(s.rows - s.emitted) : 0;  // min(lag, rows)
+		frames_out[u] = h->flush_frames(u, want[u]);
 		if (frames_out[u] == 0) continue;
 		MsBack &b = walks[n_back++];
 		b.out_off = out_off;
@@ -459,21 +423,17 @@ int wc_mlpg_stream_flush_device(wc_mlpg_stream *h, const int *want, double *d_st
 	}
 	if (n_back) {
 		int rc;
-		if ((rc = enqueue(h, hb, 0, n_back, WC_FEAT_F64, nullptr, nullptr, 0, d_static))) return rc;
+		if ((rc = enqueue(h, 0, n_back, WC_FEAT_F64, nullptr, nullptr, 0, d_static))) return rc;
 	}
-	for (int u = 0; u < n; ++u) {
-		if (!want[u]) continue;
-		h->st[u].emitted += frames_out[u];
-		h->st[u].ended = true;
-	}
+	h->commit_flush(want, frames_out);
 	return WC_OK;
 }
 
-int wc_mlpg_stream_max_frames_per_push(const wc_mlpg_stream *h) { return h ? h->max_rows : WC_ERR_INVALID; }
-int wc_mlpg_stream_max_frames_per_flush(const wc_mlpg_stream *h) { return h ? h->max_lag : WC_ERR_INVALID; }
+int wc_mlpg_stream_max_frames_per_push(const wc_mlpg_stream *h) { return lag_max_frames_per_push(h, WC_ERR_INVALID); }
+int wc_mlpg_stream_max_frames_per_flush(const wc_mlpg_stream *h) { return lag_max_frames_per_flush(h, WC_ERR_INVALID); }
 
-long long wc_mlpg_stream_rows_received(const wc_mlpg_stream *h, int stream) { return stream_ok(h, stream) ? h->st[stream].rows : -1; }
-long long wc_mlpg_stream_frames_emitted(const wc_mlpg_stream *h, int stream) { return stream_ok(h, stream) ? h->st[stream].emitted : -1; }
-int wc_mlpg_stream_get_lag(const wc_mlpg_stream *h, int stream) { return stream_ok(h, stream) ? h->st[stream].lag : -1; }
+long long wc_mlpg_stream_rows_received(const wc_mlpg_stream *h, int stream) { return lag_rows_received(h, stream); }
+long long wc_mlpg_stream_frames_emitted(const wc_mlpg_stream *h, int stream) { return lag_frames_emitted(h, stream); }
+int wc_mlpg_stream_get_lag(const wc_mlpg_stream *h, int stream) { return lag_get_lag(h, stream); }
 
 }  // extern "C"

@@ -143,9 +143,7 @@ struct wc_morph_stream {
 	std::vector<double> pos;
 	std::vector<int> cnt;
 	DevBuf bf0, bsp, bap;    // the backlog: 2 voices x n_streams x cap slots
-	DevBuf drec;             // the frame and keep records of a push
-	HostBuf h_rec[2];        // their page-locked staging: a pair, so that a push waits for the copy of the push before the last only
-	int parity = 0;
+	RecPair rec;             // the frame and keep records of a push
 	DevBuf dsp[2], dap[2];   // wc_morph_stream_push_coded_device: the pushed frames' decoded rows per voice (on first use)
 	size_t frames_cap() const { return (size_t)n_streams * max_frames; }
 	size_t keeps_cap() const { return (size_t)2 * n_streams * std::min(max_backlog, max_frames); }
@@ -174,8 +172,8 @@ int ms_push(wc_morph_stream *m, const int *n_a, const double *d_f0_a, const doub
 	if ((in[0] > 0 && !(d_f0_a && d_a_a && d_b_a)) || (in[1] > 0 && !(d_f0_b && d_a_b && d_b_b)))
 		return fail(WC_ERR_INVALID, "morph stream push: null input array");
 	// ---- the plan: host arithmetic on a copy of the states, every refusal in front of the first enqueue ----
-	if (m->h_rec[m->parity].reserve(0)) return WC_ERR_DEVICE;  // (the copy of the push before the last has read this staging)
-	MsSet *set = m->h_rec[m->parity].as<MsSet>();
+	MsSet *set = m->rec.begin<MsSet>();
+	if (!set) return WC_ERR_DEVICE;
 	MsFrame *fr = reinterpret_cast<MsFrame *>(set + n);
 	MsKeep *kp = reinterpret_cast<MsKeep *>(fr + m->frames_cap());  // (moved up behind the frames once their number is known)
 	m->next = m->st;
@@ -251,10 +249,8 @@ int ms_push(wc_morph_stream *m, const int *n_a, const double *d_f0_a, const doub
 	// the keep records follow the frame records of this push in the staging and on the device
 	std::memmove(fr + total_out, kp, sizeof(MsKeep) * (size_t)n_keep);
 	const size_t bytes = sizeof(MsSet) * (size_t)n + sizeof(MsFrame) * (size_t)total_out + sizeof(MsKeep) * (size_t)n_keep;
-	WC_HIP(hipMemcpyAsync(m->drec.p, set, bytes, hipMemcpyHostToDevice, hs));
-	if ((rc = m->h_rec[m->parity].mark(hs))) return rc;
 	MsArgs a;
-	a.sets = m->drec.as<MsSet>();
+	if ((rc = m->rec.upload(hs, bytes, &a.sets))) return rc;
 	a.frames = reinterpret_cast<const MsFrame *>(a.sets + n);
 	a.keeps = reinterpret_cast<const MsKeep *>(a.frames + total_out);
 	a.total_out = total_out; a.fs = m->fs; a.fft_size = m->fft_size;
@@ -268,7 +264,6 @@ int ms_push(wc_morph_stream *m, const int *n_a, const double *d_f0_a, const doub
 	WC_HIP(hipGetLastError());
 	if ((rc = m->dev->time_end("morph_stream_kernel", hs))) return rc;
 	m->st.swap(m->next);
-	m->parity = 1 - m->parity;
 	return WC_OK;
 }
 
@@ -301,7 +296,7 @@ wc_morph_stream *wc_morph_stream_create(int fs, int fft_size, int n_streams, int
 	const size_t slots = (size_t)2 * n_streams * m->cap, bins = fft_size / 2 + 1;
 	const size_t rec = m->rec_bytes();
 	if (m->bf0.reserve(sizeof(double) * slots) || m->bsp.reserve(sizeof(double) * slots * bins) || m->bap.reserve(sizeof(double) * slots * bins) ||
-		m->drec.reserve(rec) || m->h_rec[0].reserve(rec) || m->h_rec[1].reserve(rec)) {
+		m->rec.reserve(rec)) {
 		wc_morph_stream_destroy(m);
 		return nullptr;
 	}
@@ -311,7 +306,7 @@ wc_morph_stream *wc_morph_stream_create(int fs, int fft_size, int n_streams, int
 void wc_morph_stream_destroy(wc_morph_stream *m) {
 	if (!m) return;
 	m->dev->quiesce();
-	m->bf0.release(); m->bsp.release(); m->bap.release(); m->drec.release(); m->h_rec[0].release(); m->h_rec[1].release();
+	m->bf0.release(); m->bsp.release(); m->bap.release(); m->rec.release();
 	for (int x = 0; x < 2; ++x) { m->dsp[x].release(); m->dap[x].release(); }
 	delete m;
 }

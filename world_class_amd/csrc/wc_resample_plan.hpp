@@ -13,8 +13,8 @@
 //   sample received - 2K + b.
 //
 //   A call plans on the host with every refusal in front of the first enqueue, so a refused call moves nothing; its records go up
-//   with one asynchronous copy out of h_rec[parity], a page-locked pair, so that a call waits for the copy of the call before the
-//   last only; then the kernels are enqueued and the plan becomes the state.
+//   with one asynchronous copy through the handle's record pair (RecPair, wc_internal.hpp); then the kernels are enqueued and the
+//   plan becomes the state.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -215,9 +215,7 @@ int rs_refuse(const char *name, const char *what) { return fail(WC_ERR_INVALID, 
 // ---- the batch handle -----------------------------------------------------------------------------------------------------------------
 template <class Core> struct RsBatch {
 	Core *c = nullptr;
-	DevBuf drec;
-	HostBuf h_rec[2];  // a pair: a call waits for the copy of the call before the last only
-	int parity = 0;
+	RecPair rec;  // grown to the call's records by every call
 };
 
 template <class H, class Core> H *rs_batch_create(Core *c) {
@@ -230,7 +228,7 @@ template <class H, class Core> H *rs_batch_create(Core *c) {
 template <class H> void rs_batch_destroy(H *r) {
 	if (!r) return;
 	r->c->dev->quiesce();
-	r->drec.release(); r->h_rec[0].release(); r->h_rec[1].release();
+	r->rec.release();
 	rs_core_destroy(r->c);
 	delete r;
 }
@@ -264,14 +262,12 @@ int rs_batch_run(const char *name, H *r, bool arrays_ok, int n_utt, int in_forma
 	const size_t bytes = sizeof(Rec) * (size_t)n_utt;
 	WC_HIP(hipSetDevice(c.dev->id));
 	hipStream_t hs = c.dev->active();
-	HostBuf &hb = r->h_rec[r->parity];
-	if (hb.reserve(bytes) || r->drec.reserve(bytes)) return WC_ERR_DEVICE;
-	const RsSorted s = rs_sort_records(c, recs, hb.template as<Rec>());
-	WC_HIP(hipMemcpyAsync(r->drec.p, hb.p, bytes, hipMemcpyHostToDevice, hs));
-	int rc;
-	if ((rc = hb.mark(hs))) return rc;
-	r->parity = 1 - r->parity;
-	return enqueue(hs, r->drec.template as<Rec>(), s);
+	Rec *staged = r->rec.template begin<Rec>(bytes);
+	if (!staged) return WC_ERR_DEVICE;
+	const RsSorted s = rs_sort_records(c, recs, staged);
+	const Rec *d_rec;
+	if (int rc = r->rec.upload(hs, bytes, &d_rec)) return rc;
+	return enqueue(hs, d_rec, s);
 }
 
 // ---- the stream handle ----------------------------------------------------------------------------------------------------------------
@@ -290,9 +286,7 @@ template <class Core, class State> struct RsStreams {
 	long long cap = 0;  // doubles per buffer: 2K + max_new
 	std::vector<State> st;
 	DevBuf buf;   // n_streams x 2 x cap
-	DevBuf drec;  // RsPush per stream with samples, then the converter's record per stream with outputs
-	HostBuf h_rec[2];
-	int parity = 0;
+	RecPair rec;  // RsPush per stream with samples, then the converter's record per stream with outputs
 };
 
 bool rs_stream_counts_ok(const char *name, int n_streams, int max_samples_per_push) {
@@ -304,7 +298,7 @@ bool rs_stream_counts_ok(const char *name, int n_streams, int max_samples_per_pu
 template <class H> void rs_stream_destroy(H *h) {
 	if (!h) return;
 	h->c->dev->quiesce();
-	h->buf.release(); h->drec.release(); h->h_rec[0].release(); h->h_rec[1].release();
+	h->buf.release(); h->rec.release();
 	rs_core_destroy(h->c);
 	delete h;
 }
@@ -319,7 +313,7 @@ template <class H, class Rec, class Core> H *rs_stream_create(Core *c, int n_str
 	h->cap = 2ll * c->p.K + max_samples_per_push;
 	h->st.resize((size_t)n_streams);
 	const size_t rec = (sizeof(RsPush) + sizeof(Rec)) * (size_t)n_streams;
-	if (h->buf.reserve(sizeof(double) * (size_t)n_streams * 2 * (size_t)h->cap) || h->drec.reserve(rec) || h->h_rec[0].reserve(rec) || h->h_rec[1].reserve(rec)) {
+	if (h->buf.reserve(sizeof(double) * (size_t)n_streams * 2 * (size_t)h->cap) || h->rec.reserve(rec)) {
 		rs_stream_destroy(h);
 		return nullptr;
 	}
@@ -365,9 +359,8 @@ int rs_stream_push(const char *name, const char *count_refusal, H *h, const void
 	}
 	if ((total_in > 0 && !d_chunk) || (total_out > 0 && !d_y)) return rs_refuse(name, " stream push: null array");
 	// ---- no refusal is left: the records ----
-	HostBuf &hb = h->h_rec[h->parity];
-	if (hb.reserve(0)) return WC_ERR_DEVICE;  // (the copy of the push before the last has read this staging)
-	RsPush *push = hb.template as<RsPush>();
+	RsPush *push = h->rec.template begin<RsPush>();
+	if (!push) return WC_ERR_DEVICE;
 	std::vector<Rec> recs;
 	long long c_off = 0, y_off = 0;
 	int kp = 0, widen_blocks = 0;
@@ -398,11 +391,9 @@ int rs_stream_push(const char *name, const char *count_refusal, H *h, const void
 	if (n_push > 0 || !recs.empty()) {
 		const RsSorted so = rs_sort_records(c, recs, reinterpret_cast<Rec *>(push + n_push));
 		const size_t bytes = sizeof(RsPush) * (size_t)n_push + sizeof(Rec) * recs.size();
-		WC_HIP(hipMemcpyAsync(h->drec.p, hb.p, bytes, hipMemcpyHostToDevice, hs));
+		const RsPush *d_push;
 		int rc;
-		if ((rc = hb.mark(hs))) return rc;
-		h->parity = 1 - h->parity;
-		const RsPush *d_push = h->drec.template as<RsPush>();
+		if ((rc = h->rec.upload(hs, bytes, &d_push))) return rc;
 		if (n_push > 0) {
 			double *buf = h->buf.template as<double>();
 			rs_with_format(in_format, [&](auto format) {

@@ -149,7 +149,7 @@ wc_track_morph *wc_track_morph_create(int fs, int fft_size, int n_streams, int n
 	const size_t rec = h->rec_bytes();
 	if (h->tf0.reserve(sizeof(double) * rows) || h->tsp.reserve(sizeof(double) * rows * bins) || h->tap.reserve(sizeof(double) * rows * bins) ||
 		(slots > 0 && (h->rf0.reserve(sizeof(double) * slots) || h->rsp.reserve(sizeof(double) * slots * bins) || h->rap.reserve(sizeof(double) * slots * bins))) ||
-		h->drec.reserve(rec) || h->h_rec[0].reserve(rec) || h->h_rec[1].reserve(rec)) {
+		h->rec.reserve(rec)) {
 		wc_track_morph_destroy(h);
 		return nullptr;
 	}
@@ -160,7 +160,7 @@ void wc_track_morph_destroy(wc_track_morph *h) {
 	if (!h) return;
 	h->dev->quiesce();
 	h->tf0.release(); h->tsp.release(); h->tap.release(); h->rf0.release(); h->rsp.release(); h->rap.release();
-	h->release_records();
+	h->rec.release();
 	delete h;
 }
 

@@ -205,7 +205,7 @@ wc_track_morph_coded *wc_track_morph_coded_create(int fs, int fft_size, int numb
 	if (hipSetDevice(dev->id) != hipSuccess || tc_alloc(h, h->tf0, d * rows) || tc_alloc(h, h->tcsp, d * rows * nd) || tc_alloc(h, h->tcap, d * rows * n_ap) ||
 		tc_alloc(h, h->rf0, d * slots) || tc_alloc(h, h->rcsp, d * slots * nd) || tc_alloc(h, h->rcap, d * slots * n_ap) ||
 		tc_alloc(h, h->scsp, d * scr * nd) || tc_alloc(h, h->scap, d * scr * n_ap) || tc_alloc(h, h->ssp, d * scr * bins) ||
-		tc_alloc(h, h->sap, d * scr * bins) || tc_alloc(h, h->drec, rec) || h->h_rec[0].reserve(rec) || h->h_rec[1].reserve(rec)) {
+		tc_alloc(h, h->sap, d * scr * bins) || tc_alloc(h, h->rec.d, rec) || h->rec.reserve(rec)) {  // (the device half is accounted; reserve finds it there)
 		wc_track_morph_coded_destroy(h);
 		return nullptr;
 	}
@@ -217,7 +217,7 @@ void wc_track_morph_coded_destroy(wc_track_morph_coded *h) {
 	h->dev->quiesce();
 	h->tf0.release(); h->tcsp.release(); h->tcap.release(); h->rf0.release(); h->rcsp.release(); h->rcap.release();
 	h->scsp.release(); h->scap.release(); h->ssp.release(); h->sap.release();
-	h->release_records();
+	h->rec.release();
 	delete h;
 }
 

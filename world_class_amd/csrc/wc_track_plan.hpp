@@ -11,8 +11,8 @@
 //   so the new rows never land on a slot the state before the push still needs and a push that fails on the device leaves the rows
 //   of the last good push.
 //
-//   A call plans in h_rec[parity] and `next` (plan_push / plan_flush: host arithmetic, every refusal in front of the first enqueue),
-//   uploads the records with one asynchronous copy (upload), enqueues its kernels, and the plan becomes the state (commit).
+//   A call plans in the record pair's staging and `next` (plan_push / plan_flush: host arithmetic, every refusal in front of the first
+//   enqueue), uploads the records with one asynchronous copy (upload), enqueues its kernels, and the plan becomes the state (commit).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -67,9 +67,8 @@ struct TrackPlan {
 	Device *dev;
 	std::vector<TrackState> st, next;  // next: the states a call plans, kept if it succeeds
 	std::vector<int> track_m, cnt;
-	DevBuf drec;       // the records of a call (allocated by the handle)
-	HostBuf h_rec[2];  // their page-locked staging: a pair, so that a call waits for the copy of the call before the last only
-	int parity = 0;
+	RecPair rec;                 // the records of a call (reserved by the handle)
+	TrackSet *staged = nullptr;  // the staging the call's plan took
 
 	size_t frames_cap() const { return (size_t)n_streams * std::max(max_frames, max_delay); }
 	size_t keeps_cap() const { return (size_t)n_streams * std::min(max_delay, max_frames); }
@@ -103,9 +102,7 @@ struct TrackPlan {
 		track_m.assign(n_tracks, 0);
 		cnt.assign(n_streams, 0);
 	}
-	void release_records() { drec.release(); h_rec[0].release(); h_rec[1].release(); }
-
-	TrackSet *sets() const { return h_rec[parity].as<TrackSet>(); }
+	TrackSet *sets() const { return staged; }
 	TrackFrame *frames() const { return reinterpret_cast<TrackFrame *>(sets() + n_streams); }
 	TrackKeep *keeps() const { return reinterpret_cast<TrackKeep *>(frames() + frames_cap()); }  // (moved up behind the frames by upload)
 	void set(const TrackState &q, TrackSet &s) const {
@@ -128,7 +125,7 @@ struct TrackPlan {
 			in += n_a[u];
 		}
 		if (in > 0 && !in_ok) return refuse(" push: null input array");
-		if (h_rec[parity].reserve(0)) return WC_ERR_DEVICE;  // (the copy of the call before the last has read this staging)
+		if (!(staged = rec.begin<TrackSet>())) return WC_ERR_DEVICE;
 		TrackSet *sp = sets();
 		TrackFrame *fr = frames();
 		TrackKeep *kp = keeps();
@@ -180,7 +177,7 @@ struct TrackPlan {
 			if (s.track < 0 || s.ended) return refuse(" flush: a wanted stream is not attached or has ended");
 			if (s.delay == 0 || s.n == 0) return refuse(" flush: a wanted stream has no delay or no rows");
 		}
-		if (h_rec[parity].reserve(0)) return WC_ERR_DEVICE;
+		if (!(staged = rec.begin<TrackSet>())) return WC_ERR_DEVICE;
 		TrackSet *sp = sets();
 		TrackFrame *fr = frames();
 		next = st;
@@ -215,22 +212,15 @@ struct TrackPlan {
 
 	// the planned records to the device on hs: the keep records follow the frame records of this call in the staging and on the device
 	int upload(hipStream_t hs, const TrackCall &c, TrackRecs *r) {
-		TrackSet *sp = sets();
-		TrackFrame *fr = frames();
-		std::memmove(fr + c.total_out, keeps(), sizeof(TrackKeep) * (size_t)c.n_keep);
+		std::memmove(frames() + c.total_out, keeps(), sizeof(TrackKeep) * (size_t)c.n_keep);
 		const size_t bytes = sizeof(TrackSet) * (size_t)n_streams + sizeof(TrackFrame) * (size_t)c.total_out + sizeof(TrackKeep) * (size_t)c.n_keep;
-		WC_HIP(hipMemcpyAsync(drec.p, sp, bytes, hipMemcpyHostToDevice, hs));
-		if (int rc = h_rec[parity].mark(hs)) return rc;
-		r->sets = drec.as<TrackSet>();
+		if (int rc = rec.upload(hs, bytes, &r->sets)) return rc;
 		r->frames = reinterpret_cast<const TrackFrame *>(r->sets + n_streams);
 		r->keeps = reinterpret_cast<const TrackKeep *>(r->frames + c.total_out);
 		return WC_OK;
 	}
 	// everything of the call is enqueued: the plan becomes the state
-	void commit() {
-		st.swap(next);
-		parity = 1 - parity;
-	}
+	void commit() { st.swap(next); }
 };
 
 // ---- the bodies of the entry points that differ in nothing but the handle's name; h may be null, so the name comes with the call ----

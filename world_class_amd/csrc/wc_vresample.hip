@@ -735,9 +735,7 @@ struct wc_warp_stream {
 	std::vector<int> track_len;  // 0: the slot has not been set
 	DevBuf tracks;               // n_tracks x max_track samples of track_format
 	DevBuf carry;                // n_streams x 2 doubles
-	DevBuf drec;                 // a record per stream with outputs, then a WsKeep per stream with entries
-	HostBuf h_rec[2];
-	int parity = 0;
+	RecPair rec;                 // a record per stream with outputs, then a WsKeep per stream with entries
 };
 
 namespace {
@@ -785,8 +783,8 @@ int ws_push(wc_warp_stream *h, bool flush, const int *counts, const double *d_en
 	}
 	if ((total_read > 0 && !d_entries) || (total_out > 0 && !d_y)) return refuse(": null array");
 	// ---- no refusal is left: the records ----
-	HostBuf &hb = h->h_rec[h->parity];
-	if (hb.reserve(0)) return WC_ERR_DEVICE;  // (the copy of the push before the last has read this staging)
+	WmRec *rec = h->rec.begin<WmRec>();
+	if (!rec) return WC_ERR_DEVICE;
 	std::vector<WmRec> recs;
 	std::vector<WsKeep> keeps;
 	long long e_off = 0, y_off = 0;
@@ -816,16 +814,13 @@ int ws_push(wc_warp_stream *h, bool flush, const int *counts, const double *d_en
 	if (!recs.empty() || !keeps.empty()) {
 		WC_HIP(hipSetDevice(c.dev->id));
 		hipStream_t hs = c.dev->active();
-		WmRec *rec = hb.as<WmRec>();
 		const RsSorted so = rs_sort_records(c, recs, rec);
 		WsKeep *keep = reinterpret_cast<WsKeep *>(rec + recs.size());
 		std::copy(keeps.begin(), keeps.end(), keep);
 		const size_t bytes = sizeof(WmRec) * recs.size() + sizeof(WsKeep) * keeps.size();
-		WC_HIP(hipMemcpyAsync(h->drec.p, hb.p, bytes, hipMemcpyHostToDevice, hs));
+		const WmRec *d_rec;
 		int rc;
-		if ((rc = hb.mark(hs))) return rc;
-		h->parity = 1 - h->parity;
-		const WmRec *d_rec = h->drec.as<WmRec>();
+		if ((rc = h->rec.upload(hs, bytes, &d_rec))) return rc;
 		if ((rc = ws_enqueue(c, hs, d_rec, so, h->tracks.p, h->track_format, d_entries, h->carry.as<double>(),
 							 reinterpret_cast<const WsKeep *>(d_rec + recs.size()), (int)keeps.size(), d_y, out_format)))
 			return rc;
@@ -1098,7 +1093,7 @@ wc_warp_stream *wc_warp_stream_create(unsigned long long step_min, unsigned long
 	h->track_len.assign((size_t)n_tracks, 0);
 	const size_t rec = (sizeof(WmRec) + sizeof(WsKeep)) * (size_t)n_streams;
 	if (h->tracks.reserve((size_t)ws_bytes_of(track_format) * (size_t)n_tracks * (size_t)max_track_samples) ||
-		h->carry.reserve(sizeof(double) * 2 * (size_t)n_streams) || h->drec.reserve(rec) || h->h_rec[0].reserve(rec) || h->h_rec[1].reserve(rec)) {
+		h->carry.reserve(sizeof(double) * 2 * (size_t)n_streams) || h->rec.reserve(rec)) {
 		wc_warp_stream_destroy(h);
 		return nullptr;
 	}
@@ -1108,7 +1103,7 @@ wc_warp_stream *wc_warp_stream_create(unsigned long long step_min, unsigned long
 void wc_warp_stream_destroy(wc_warp_stream *h) {
 	if (!h) return;
 	h->c->dev->quiesce();
-	h->tracks.release(); h->carry.release(); h->drec.release(); h->h_rec[0].release(); h->h_rec[1].release();
+	h->tracks.release(); h->carry.release(); h->rec.release();
 	rs_core_destroy(h->c);
 	delete h;
 }

@@ -6,7 +6,7 @@ import ctypes as C
 
 from . import DeviceArray, _check, _ints, _opt  # noqa: F401  (_ints: for raw calls through _L(), as the tests make them)
 from .features import FORMATS
-from .resample import _binder, _Handle
+from .resample import _binder, _lag_emitted, _LagStream
 
 _ip = C.POINTER(C.c_int)
 _vp = C.c_void_p
@@ -28,42 +28,24 @@ FEATURE_STREAM_SIGNATURES = {
 _L = _binder(FEATURE_STREAM_SIGNATURES)
 
 
-def emitted(rows, lag):
-    """E(rows) = max(rows - lag, 0): the rows a stream that has not ended has emitted after so many rows"""
-    n = int(_L().wc_feature_stream_emitted(int(rows), int(lag)))
-    if n < 0:
-        raise ValueError("rows and lag must not be negative")
-    return n
+emitted = _lag_emitted(_L, "wc_feature_stream_emitted",
+                       "E(rows) = max(rows - lag, 0): the rows a stream that has not ended has emitted after so many rows")
 
 
-class FeatureStream(_Handle):
+class FeatureStream(_LagStream):
     """n_streams concurrent streams of rows of one F0, nd coded envelope and n_ap coded aperiodicity values, at most
     max_rows_per_push rows per stream and push, each stream with a lag of at most max_lag rows and an lf0_fill given at its reset.
     Emitted rows have orders * (nd + 1 + n_ap) + 1 columns (orders 1, 2 or 3)"""
     _lib = staticmethod(_L)
     _sym = "wc_feature"
-    _kind = "_stream"
 
     def __init__(self, n_streams, nd, n_ap, orders, max_rows_per_push, max_lag):
         self.n_streams, self.nd, self.n_ap, self.orders = int(n_streams), int(nd), int(n_ap), int(orders)
         self._create(self.n_streams, self.nd, self.n_ap, self.orders, int(max_rows_per_push), int(max_lag))
 
-    @property
-    def max_frames_per_push(self):
-        return int(self._fn("_stream_max_frames_per_push")(self._h))
-
-    @property
-    def max_frames_per_flush(self):
-        return int(self._fn("_stream_max_frames_per_flush")(self._h))
-
     def reset(self, stream, lag, lf0_fill=0.0):
         """the stream forgets everything and takes rows again, emitting `lag` rows behind the newest"""
         _check(self._fn("_stream_reset")(self._h, int(stream), int(lag), float(lf0_fill)))
-
-    def _counts(self, counts):
-        if len(counts) != self.n_streams:
-            raise ValueError("one entry per stream")
-        return _ints(counts), (C.c_int * self.n_streams)()
 
     def push_device(self, n_rows, d_f0, d_coded_sp, d_coded_ap, d_rows, out_format="f64"):
         """n_rows[u] rows per stream packed in d_f0, d_coded_sp and d_coded_ap (None where n_ap is 0), the emitted rows packed by
@@ -78,12 +60,3 @@ class FeatureStream(_Handle):
         counts, got = self._counts([1 if w else 0 for w in want])
         _check(self._fn("_stream_flush_device")(self._h, counts, FORMATS[out_format][0], _opt(d_rows), got))
         return list(got)
-
-    def rows_received(self, stream):
-        return int(self._fn("_stream_rows_received")(self._h, int(stream)))
-
-    def frames_emitted(self, stream):
-        return int(self._fn("_stream_frames_emitted")(self._h, int(stream)))
-
-    def get_lag(self, stream):
-        return int(self._fn("_stream_get_lag")(self._h, int(stream)))

@@ -5,7 +5,7 @@ import ctypes as C
 
 from . import DeviceArray, _check, _ints, _opt  # noqa: F401  (_ints: for raw calls through _L(), as the tests make them)
 from .features import FORMATS
-from .resample import _binder, _Handle
+from .resample import _binder, _lag_emitted, _LagStream
 
 _ip = C.POINTER(C.c_int)
 _vp = C.c_void_p
@@ -27,41 +27,23 @@ MLPG_STREAM_SIGNATURES = {
 _L = _binder(MLPG_STREAM_SIGNATURES)
 
 
-def emitted(rows, lag):
-    """E(rows) = max(rows - lag, 0): the frames a stream that has not ended has emitted after so many rows"""
-    n = int(_L().wc_mlpg_stream_emitted(int(rows), int(lag)))
-    if n < 0:
-        raise ValueError("rows and lag must not be negative")
-    return n
+emitted = _lag_emitted(_L, "wc_mlpg_stream_emitted",
+                       "E(rows) = max(rows - lag, 0): the frames a stream that has not ended has emitted after so many rows")
 
 
-class MlpgStream(_Handle):
+class MlpgStream(_LagStream):
     """n_streams concurrent streams of rows of width orders * (nd + 1 + n_ap) + 1 (orders 2 or 3), at most max_rows_per_push rows per
     stream and push, each stream with a lag of at most max_lag rows given at its reset.  Emitted rows have nd + 2 + n_ap doubles"""
     _lib = staticmethod(_L)
     _sym = "wc_mlpg"
-    _kind = "_stream"
 
     def __init__(self, n_streams, nd, n_ap, orders, max_rows_per_push, max_lag):
         self.n_streams, self.nd, self.n_ap, self.orders = int(n_streams), int(nd), int(n_ap), int(orders)
         self._create(self.n_streams, self.nd, self.n_ap, self.orders, int(max_rows_per_push), int(max_lag))
 
-    @property
-    def max_frames_per_push(self):
-        return int(self._fn("_stream_max_frames_per_push")(self._h))
-
-    @property
-    def max_frames_per_flush(self):
-        return int(self._fn("_stream_max_frames_per_flush")(self._h))
-
     def reset(self, stream, lag):
         """the stream forgets everything and takes rows again, emitting `lag` rows behind the newest"""
         _check(self._fn("_stream_reset")(self._h, int(stream), int(lag)))
-
-    def _counts(self, counts):
-        if len(counts) != self.n_streams:
-            raise ValueError("one entry per stream")
-        return _ints(counts), (C.c_int * self.n_streams)()
 
     def push_device(self, n_rows, d_mean, d_var, d_static, var_per_frame=False, in_format="f64"):
         """n_rows[u] rows per stream packed in d_mean (and in d_var, or one row of variances for the push), the emitted static rows
@@ -76,12 +58,3 @@ class MlpgStream(_Handle):
         counts, got = self._counts([1 if w else 0 for w in want])
         _check(self._fn("_stream_flush_device")(self._h, counts, _opt(d_static), got))
         return list(got)
-
-    def rows_received(self, stream):
-        return int(self._fn("_stream_rows_received")(self._h, int(stream)))
-
-    def frames_emitted(self, stream):
-        return int(self._fn("_stream_frames_emitted")(self._h, int(stream)))
-
-    def get_lag(self, stream):
-        return int(self._fn("_stream_get_lag")(self._h, int(stream)))

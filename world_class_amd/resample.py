@@ -127,6 +127,46 @@ class _Handle:
             pass
 
 
+class _LagStream(_Handle):
+    """what the two lagged row streams share (csrc/wc_lag_stream.hpp): MlpgStream and FeatureStream"""
+    _kind = "_stream"
+    n_streams = 0
+
+    @property
+    def max_frames_per_push(self):
+        return int(self._fn("_stream_max_frames_per_push")(self._h))
+
+    @property
+    def max_frames_per_flush(self):
+        return int(self._fn("_stream_max_frames_per_flush")(self._h))
+
+    def _counts(self, counts):
+        if len(counts) != self.n_streams:
+            raise ValueError("one entry per stream")
+        return _ints(counts), (C.c_int * self.n_streams)()
+
+    def rows_received(self, stream):
+        return int(self._fn("_stream_rows_received")(self._h, int(stream)))
+
+    def frames_emitted(self, stream):
+        return int(self._fn("_stream_frames_emitted")(self._h, int(stream)))
+
+    def get_lag(self, stream):
+        return int(self._fn("_stream_get_lag")(self._h, int(stream)))
+
+
+def _lag_emitted(binder, symbol, doc):
+    """a module's emitted(rows, lag), bound to its library symbol"""
+    def emitted(rows, lag):
+        n = int(getattr(binder(), symbol)(int(rows), int(lag)))
+        if n < 0:
+            raise ValueError("rows and lag must not be negative")
+        return n
+
+    emitted.__doc__ = doc
+    return emitted
+
+
 class _Batch(_Handle):
     """the batch handle of either converter: the packing of host arrays around its run_device"""
     _kind = "r"
