@@ -168,6 +168,24 @@ class Port:
                               smooth_sections=h[14])
         return r
 
+    def harvest_refine(self, y, fs_d, cand0, f0_floor=71.0, f0_ceil=800.0, use_cos_table=False, decisions=False):
+        """Harvest's refinement alone (overlap of the neighbouring frames' candidates, refinement by instantaneous frequency,
+        thresholds) on the decimated signal y at the internal rate fs_d and the raw candidate rows cand0 [1 ms frames][S]
+        (0 = empty slot).  Returns (refined candidates, scores), each [frames][7 S]; with decisions also the integers every live
+        candidate was cut into, [frames][7 S][10]: hw, N, basic, nh and the six bins (0 beyond nh)."""
+        y, cand0 = _c(y), _c(cand0)
+        L, S = cand0.shape
+        c1, s1 = np.zeros((L, 7 * S)), np.zeros((L, 7 * S))
+        fn = self.lib.wco_harvest_refine
+        fn.restype = C.c_int
+        fn.argtypes = [_dp, C.c_int, C.c_double, C.c_int, C.c_int, _dp, C.c_double, C.c_double, C.c_int, _dp, _dp, _ip]
+        dec = np.zeros((L, 7 * S, 10), dtype=np.int32)
+        got = fn(_p(y), len(y), float(fs_d), L, S, _p(cand0), f0_floor, f0_ceil, int(use_cos_table), _p(c1), _p(s1),
+                 dec.ctypes.data_as(_ip) if decisions else None)
+        if got != 7 * S:
+            raise ValueError("harvest_refine: bad arguments (%d)" % got)
+        return (c1, s1, dec) if decisions else (c1, s1)
+
     def cheaptrick_fft_size(self, fs, f0_floor=71.0):
         return self.lib.wco_cheaptrick_fft_size(fs, f0_floor)
 

@@ -803,6 +803,9 @@ struct HvTrace {
 	int smooth_sections = 0;
 };
 static HvTrace *g_hv_trace = nullptr;
+// the integer decisions of hv_refine_one per (frame, candidate) -- hw, N, basic, nh and the six bins (0 beyond nh) -- for
+// wco_harvest_refine; written only while this points at [L][n_cand][WCO_HV_REFINE_DECISIONS] ints
+static int *g_hv_refine_trace = nullptr;
 static int get_samples(int fs, int x_length, double fp) {  // :173-181
 	return static_cast<int>(1000.0 * x_length / fs / fp) + 1;
 }
@@ -923,7 +926,7 @@ static void hv_overlap(Harvest &H, int nc) {
 		}
 }
 // :883-927 with :750-878
-static void hv_refine_one(const Harvest &H, double pos, double f, double *rf, double *rs) {
+static void hv_refine_one(const Harvest &H, double pos, double f, double *rf, double *rs, int *trace = nullptr) {
 	double fs = H.fs_d;
 	int hw = static_cast<int>(1.5 * fs / f + 1.0);
 	double wlt = (2.0 * hw + 1.0) / fs;
@@ -960,9 +963,11 @@ static void hv_refine_one(const Harvest &H, double pos, double f, double *rf, do
 	for (int i = 0; i < bt; ++i) wave[i] = dw[i] * H.y[clampi(basic + i - 1, 0, H.y_length - 1)];
 	r2c(wave.data(), N, ds.data());
 	int nh = std::min(static_cast<int>(fs / 2.0 / f), 6);
+	if (trace) { trace[0] = hw; trace[1] = N; trace[2] = basic; trace[3] = nh; }
 	double num = 0, den = 0, sc = 0;
 	for (int i = 0; i < nh; ++i) {
 		int idx = mround(f * N / fs * (i + 1));
+		if (trace) trace[4 + i] = idx;
 		cd m = std::conj(ms[idx]), d = std::conj(ds[idx]);  // explicit sign flip (:831,:840)
 		double pw = m.real() * m.real() + m.imag() * m.imag();
 		double ni = m.real() * d.imag() - m.imag() * d.real();
@@ -983,7 +988,8 @@ static void hv_refine(Harvest &H) {
 			double f = H.cand[i][j];
 			if (f <= 0.0) { H.cand[i][j] = 0.0; H.score[i][j] = 0.0; continue; }
 			double rf, rs;
-			hv_refine_one(H, H.tpos[i], f, &rf, &rs);
+			hv_refine_one(H, H.tpos[i], f, &rf, &rs,
+						  g_hv_refine_trace ? g_hv_refine_trace + (static_cast<size_t>(i) * H.n_cand + j) * WCO_HV_REFINE_DECISIONS : nullptr);
 			if (rf < H.floor_ || rf > H.ceil_ || rs < 2.5) { rf = 0.0; rs = 0.0; }
 			H.cand[i][j] = rf;
 			H.score[i][j] = rs;
@@ -1441,5 +1447,35 @@ int wco_harvest_tail(const double *cand, const double *score, int L, int n_cand,
 		std::copy(t.begin(), t.end(), trace);
 	}
 	return get_samples(fs, x_length, frame_period);
+}
+int wco_harvest_refine(const double *y, int y_length, double fs_d, int L, int S, const double *cand0, double f0_floor,
+					   double f0_ceil, int use_cos_table, double *cand1, double *score1, int *decisions) {
+	if (!y || !cand0 || !cand1 || !score1 || y_length < 1 || L < 1 || S < 1 || !(fs_d > 0.0)) return -1;
+	Harvest H;
+	H.fs_d = fs_d;
+	H.floor_ = f0_floor;
+	H.ceil_ = f0_ceil;
+	H.y.assign(y, y + y_length);
+	H.y_length = y_length;
+	H.L = L;
+	H.max_cand = H.n_cand = 7 * S;
+	H.tpos.resize(L);
+	for (int i = 0; i < L; ++i) H.tpos[i] = i * 1 / 1000.0;
+	H.cand.assign(L, vd(H.max_cand, 0.0));
+	H.score.assign(L, vd(H.max_cand, 0.0));
+	for (int i = 0; i < L; ++i) std::copy(cand0 + static_cast<size_t>(i) * S, cand0 + static_cast<size_t>(i + 1) * S, H.cand[i].begin());
+	const int table_before = g_hv_use_cos_table;
+	g_hv_use_cos_table = use_cos_table;
+	if (decisions) std::fill(decisions, decisions + static_cast<size_t>(L) * H.n_cand * WCO_HV_REFINE_DECISIONS, 0);
+	g_hv_refine_trace = decisions;
+	hv_overlap(H, S);
+	hv_refine(H);
+	g_hv_refine_trace = nullptr;
+	g_hv_use_cos_table = table_before;
+	for (int i = 0; i < L; ++i) {
+		std::copy(H.cand[i].begin(), H.cand[i].end(), cand1 + static_cast<size_t>(i) * H.n_cand);
+		std::copy(H.score[i].begin(), H.score[i].end(), score1 + static_cast<size_t>(i) * H.n_cand);
+	}
+	return H.n_cand;
 }
 }  // extern "C"

@@ -90,6 +90,16 @@ int wco_harvest_debug(const double *x, int x_length, int fs, double f0_floor, do
 int wco_harvest_tail(const double *cand, const double *score, int L, int n_cand, double frame_period, int fs, int x_length,
                      double *cand_out, double *score_out, double *f0_base, double *s1, double *s2, double *s3,
                      double *f0_fixed, double *f0_1ms, double *tpos, double *f0, int *trace, int trace_capacity);
+
+/* Harvest's refinement alone on candidate rows given by the caller: overlapF0Candidates and refineF0Candidates (the hv_overlap
+ * and hv_refine every wco_harvest call runs) on the decimated signal y[y_length] at the internal rate fs_d, over L 1 ms frames
+ * with cand0 [L][S] raw candidates (0 = empty slot).  use_cos_table: HarvestOption::use_cos_table for this call only.
+ * Out: cand1 / score1 [L][7 S], block b of a row holding the slots of frame i, i-1, i-2, i-3, i+1, i+2, i+3; candidates the
+ * thresholds reject are 0 in both; decisions (may be NULL) [L][7 S][WCO_HV_REFINE_DECISIONS]: the integers every live candidate
+ * was cut into -- hw, N, basic, nh and the six bins (0 beyond nh; all 0 for an empty position).  Returns 7 S, < 0 on bad arguments. */
+#define WCO_HV_REFINE_DECISIONS 10
+int wco_harvest_refine(const double *y, int y_length, double fs_d, int L, int S, const double *cand0, double f0_floor,
+                       double f0_ceil, int use_cos_table, double *cand1, double *score1, int *decisions);
 #ifdef __cplusplus
 }
 #endif

@@ -56,8 +56,13 @@ class Harvest:
         return out
 
     def debug_refine(self, cand0, by_slots=False):
-        """Development hook: the refinement kernel alone on the candidate rows `cand0` ([1 ms frames of the most recent call][S],
-        0 = empty slot); returns (refined candidates, scores), each [frames][7 S].  by_slots: the slot layout instead of the packed one."""
+        """Development hook: the refinement kernel alone on the candidate rows `cand0` ([1 ms frames of the most recent call, utterance
+        after utterance][S], 0 = empty slot, anything else a frequency the detector could emit: within [f0_floor, f0_ceil]), over
+        the decimated signals of that call (debug_fetch("y", u)).  Returns (refined candidates, scores), each [frames][7 S]: position
+        j + S b of frame i holds slot j of frame i, i-1, i-2, i-3, i+1, i+2, i+3 for b = 0 .. 6, refined at frame i; 0 in both where
+        the source frame lies outside the utterance, the slot is empty or the thresholds reject the result.  The rows replace the
+        call's own raw candidates (debug_fetch("cand0")).  by_slots: 0 the default dispatch (frames in groups; rows wider than 128
+        positions the packed kernel), 1 one wavefront per slot, 2 the packed kernel (one wavefront per frame)."""
         fn = lib().wc_harvest_debug_refine
         fn.restype = C.c_int
         fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
