@@ -6,7 +6,7 @@ import sys
 import numpy as np
 a = np.fromfile(sys.argv[1], dtype=np.uint64).reshape(-1, 16)[:, :11].astype(np.int64)
 a = a[(a[:, 10] > a[:, 0]) & (a[:, 0] > 0)]
-# (windows of at most 2048 samples, the usual case: job-major; the longer ones stamp half-major: "rest of the even half", "odd half")
+# (job-major, as both launches stamp; under WC_D4C_LONG=halves the longer windows stamp half-major: "rest of the even half", "odd half")
 names = ["set-up, window of job 0, parked", "job 0 even: master read + transform", "job 0 even: weighted read + transform + products + park", "job 0 odd half", "jobs 1 and 2", "reload parked",
          "dc corrections", "power smoothing (order-faithful)", "division + two signed smoothings", "store"]
 d = np.diff(a, axis=1)

@@ -1,5 +1,6 @@
 """Per-kernel timings of the device pipeline on one GPU (development aid; the graded number is bench.py).
-usage: python tools/microbench.py [--fs 48000] [--utts 64] [--seconds 10] [--iters 3] [--stages hcds]"""
+usage: python tools/microbench.py [--fs 48000] [--utts 64] [--seconds 10] [--iters 3] [--stages hcds] [--f0 HZ]
+--f0 HZ puts every voiced frame of the given contours at HZ (80: every gated frame of D4C has windows longer than 2048 samples at 48 kHz)."""
 import argparse
 import os
 import sys
@@ -22,12 +23,15 @@ def main():
     ap.add_argument("--seconds", type=float, default=10.0)
     ap.add_argument("--iters", type=int, default=3)
     ap.add_argument("--stages", default="hcds")
+    ap.add_argument("--f0", type=float, default=0.0, help="every voiced frame's F0 in the contours handed to the stages (0: as generated)")
     a = ap.parse_args()
     L = w.lib()
     fs = a.fs
     nd = min(a.utts, 8)
     base = [make_utterance(fs, a.seconds, 3000 + u) for u in range(nd)]
     tf = [true_f0(fs, a.seconds, 3000 + u) for u in range(nd)]
+    if a.f0 > 0.0:
+        tf = [(t, np.where(f > 0.0, a.f0, 0.0)) for t, f in tf]
     xs = [base[u % nd] for u in range(a.utts)]
     xl = [len(x) for x in xs]
     fl = [w.get_samples(fs, n, 5.0) for n in xl]
@@ -72,7 +76,7 @@ def main():
     print(f"fs={fs} utts={a.utts} frames={frames} stages={a.stages}: wall {t*1e3:.1f} ms -> {frames/t/1e6:.3f} Mframes/s")
     for k in KERNELS:
         if k in best:
-            print(f"  {k:20s} {best[k]:8.2f} ms")
+            print(f"  {k:20s} {best[k]:8.3f} ms")
     print(f"  {'sum of kernels':20s} {sum(best.values()):8.2f} ms")
 
 

@@ -52,6 +52,7 @@ struct D4cArgs {
 	double threshold;
 	long long sgd_stride;  // doubles per frame in sgd
 	int *long_list, *long_cnt;  // gated frames whose windows exceed 2048 samples: left by d4c2_frames_kernel<false>, done by <true>
+	double *long_park;  // [grid of d4c2_frames_kernel<true>][kD4Park]: the mean-removed window of the long frame a block is at
 	const int *uidx;  // [total_frames] utterance of every frame (d4c_lt_count_kernel): the one-wavefront kernels read it instead of bisecting
 	int rare_only;  // (unused)
 	int *rare_list;  // [0]: count, then the gated frames the one-wavefront kernels leave to the block kernel
@@ -747,10 +748,13 @@ __global__ __launch_bounds__(256) void d4c_rows_kernel(D4cArgs a) {
 // LDS: 18.5 KB per frame wavefront (exchange buffer = mirrored segment of the smoothings), 9.8 KB per band wavefront,
 // instead of 64 KB / 36 KB per 8-wavefront workgroup.  Deviations from the kernels above, all at the 1e-15 level: the
 // halving of the real-transform unpacking is folded into scale factors; the smoothings' two interpolation abscissae are
-// k + c_lo, k + c_hi with one pair per frame; (hi - lo) * (1 / width).  The window is generated once per half (the
-// wavefront cannot hold a frame's 4096 samples next to a transform in flight): 6 instead of 3 window generations per frame.
+// k + c_lo, k + c_hi with one pair per frame; (hi - lo) * (1 / width).  The wavefront cannot hold a window's samples next to a
+// transform in flight: a window is formed once, parked (frame's row and LDS; a block's row of long_park for windows beyond 2048
+// samples) and read back for each half and transform: 3 window generations per frame.
 constexpr long long kD4Row = 4160;  // doubles per frame of the group-delay array when d4c2_frames_kernel parks its halves in it
 constexpr int kD4Lds = 2304;  // doubles: the smoothings' 2049 + 2 b + 1 terms, b <= 120 (d4c2_can); the exchange buffer is its head
+constexpr long long kD4Park = 4096;  // doubles per block of d4c2_frames_kernel<true>: a window's even samples (32 slots x 64 lanes), then its odd ones
+constexpr long long kD4LongGrid = 4096;  // blocks of the launch that walks the list of long-window frames, at most
 
 // F0-adaptive window of reference src/d4c.cpp:246-303 as the strided packed input of one half of the transform: slot q
 // holds z[n] +- z[n + 1024] for n = lane + 64 q, z[m] = (sample 2 m, sample 2 m + 1) of the mean-removed windowed signal
@@ -759,10 +763,16 @@ constexpr int kD4Lds = 2304;  // doubles: the smoothings' 2049 + 2 b + 1 terms, 
 // transform of the centroid).  Returns the window length; sumsq = sum of squares of the (unweighted) samples.
 // SLOTS = 16: the window is known to be at most 2048 samples long (every lane's 16 slots hold all of it, z[n + 1024] = 0, `odd`
 // plays no part: the caller forms both halves' inputs from the one result); SLOTS = 32: any length.
-template <int SLOTS>
+// With a `park` of the caller's (SLOTS = 32) nothing is folded or weighted: park(q, ve, vo) receives the mean-removed sample pair
+// of every slot of the live groups of four, q = 0 .. 31, and re / im come back without meaning; only sumsq and the length count.
+struct D4NoPark {
+	__device__ __forceinline__ void operator()(int, double, double) const {}
+};
+template <int SLOTS, class Park = D4NoPark>
 __device__ __forceinline__ int d4c2_windowed(int type, const double *__restrict__ x, int x_last, int fs, double f0, double pos, double ratio,
 											 const uint32_t *__restrict__ rng, int odd, bool weighted, double (&re)[16],
-											 double (&im)[16], double &sumsq, int lane) {
+											 double (&im)[16], double &sumsq, int lane, Park park = Park()) {
+	constexpr bool PARKED = !std::is_same<Park, D4NoPark>::value;
 	WC_FRESH(lane);
 	const int hw = __builtin_amdgcn_readfirstlane(mround(ratio * fs / f0 / 2.0));
 	const int wl = 2 * hw + 1;
@@ -831,10 +841,14 @@ __device__ __forceinline__ int d4c2_windowed(int type, const double *__restrict_
 		ve = fma(-We, wc, ve);
 		vo = fma(-Wo, wc, vo);
 		sumsq = fma(vo, vo, fma(ve, ve, sumsq));
-		if (weighted) { ve *= i0 + 1.0; vo *= i0 + 2.0; }
-		if (q < 16) { re[q] = ve; im[q] = vo; }
-		else if (odd) { re[q & 15] -= ve; im[q & 15] -= vo; }
-		else { re[q & 15] += ve; im[q & 15] += vo; }
+		if constexpr (PARKED) {
+			park(q, ve, vo);
+		} else {
+			if (weighted) { ve *= i0 + 1.0; vo *= i0 + 2.0; }
+			if (q < 16) { re[q] = ve; im[q] = vo; }
+			else if (odd) { re[q & 15] -= ve; im[q & 15] -= vo; }
+			else { re[q & 15] += ve; im[q & 15] += vo; }
+		}
 	});
 	sumsq = wave_sum_all(sumsq);
 	return wl;
@@ -1039,9 +1053,16 @@ __device__ __forceinline__ void d4c2_smooth(D4Bins &s, double width, int fs, dou
 #define D4_STAMP(i) do { } while (0)
 #endif
 // gated frames up to the static group delay (reference :308-460), which the band kernel reads back
-// LONG = false: frames whose windows fit 2048 samples (F0 of 94 Hz and above at 48 kHz): a window is formed once per position,
-// parked in the frame's row and read back by both halves and both transforms; LONG = true: the others, window formed per half
-// and transform.  Every gated frame is done by exactly one of the two launches.
+// kD4Short: frames whose windows fit 2048 samples (F0 of 94 Hz and above at 48 kHz): a window is formed once per position,
+// parked in the frame's row and read back by both halves and both transforms.  The others (the second launch):
+// kD4Long: a window is formed once per position too; the mean-removed sample pairs of all 32 slots are parked in a row that
+// belongs to the block (D4cArgs::long_park: the frame's own row has no room for 4096 samples next to the products that wait in
+// it), and the four inputs of a position's transforms are formed from them: (v[q] +- v[q + 16]) * pw, the weighted one
+// (v[q] * w(q) +- v[q + 16] * w(q + 16)) * pw -- the operations, operands and order of
+// kD4LongHalves (WC_D4C_LONG=halves, the twin of rounds 3-6): the window formed again for every half and transform, ten times
+// per frame, each time with the same mean, the same sum of squares and the same samples.  The same bits.
+// Every gated frame is done by exactly one of the two launches.
+constexpr int kD4Short = 0, kD4Long = 1, kD4LongHalves = 2;
 // The frame's row of the group-delay array through a buffer resource: an access is one 32-bit offset register (shared by all
 // the accesses of a lane), an immediate and a scalar offset -- as plain pointers the parked layouts' offsets (up to 33 KB, beyond
 // the 4 KB immediate of a global access) made the compiler form a 64-bit vector address per access and keep dozens of them, half
@@ -1052,9 +1073,9 @@ __device__ __forceinline__ void d4c2_smooth(D4Bins &s, double width, int fs, dou
 #if WC_D4C2_BUFFER
 typedef unsigned int d4_u2 __attribute__((ext_vector_type(2)));
 struct D4Row { __amdgpu_buffer_rsrc_t r; };
-__device__ __forceinline__ D4Row d4_row(double *p) {
+__device__ __forceinline__ D4Row d4_row(double *p, long long n = kD4Row) {
 	D4Row w;
-	w.r = __builtin_amdgcn_make_buffer_rsrc(p, 0, (int)(kD4Row * 8), 0x00020000);
+	w.r = __builtin_amdgcn_make_buffer_rsrc(p, 0, (int)(n * 8), 0x00020000);
 	return w;
 }
 __device__ __forceinline__ double d4_ld(const D4Row &w, int idx) {
@@ -1069,13 +1090,14 @@ __device__ __forceinline__ void d4_st(const D4Row &w, int idx, double d) {
 }
 #else
 struct D4Row { double *p; };
-__device__ __forceinline__ D4Row d4_row(double *p) { D4Row w; w.p = p; asm volatile("" : "+s"(w.p)); return w; }
+__device__ __forceinline__ D4Row d4_row(double *p, long long = kD4Row) { D4Row w; w.p = p; asm volatile("" : "+s"(w.p)); return w; }
 __device__ __forceinline__ double d4_ld(const D4Row &w, int idx) { return w.p[idx]; }
 __device__ __forceinline__ void d4_st(const D4Row &w, int idx, double d) { w.p[idx] = d; }
 #endif
-template <bool LONG>
+template <int FORM>
 __device__ __forceinline__ void d4c2_frame(const D4cArgs &a, const long long g, double *L, const int lane) {
 	constexpr int M = 2048;
+	constexpr bool LONG = FORM != kD4Short;
 	const double f0v = a.f0[g];
 	if (f0v == 0.0 || a.ap0[g] <= a.threshold) return;  // reference :147
 	const int fs = a.fs;
@@ -1208,6 +1230,109 @@ __device__ __forceinline__ void d4c2_frame(const D4cArgs &a, const long long g, 
 			}
 			if (job == 0) D4_STAMP(4);
 		}
+	} else if constexpr (FORM == kD4Long) {
+		// (wl > 2048: all sixteen lower slots are live, ng = 4; of the upper ones the groups of four below the window's end)
+		const D4Row win = d4_row(a.long_park + (long long)blockIdx.x * kD4Park, kD4Park);
+#pragma unroll 1
+		for (int job = 0; job < 3; ++job) {
+			int ln = lane;
+			WC_FRESH(ln);
+			const double p = (job == 0) ? pos - 0.25 / f0 : (job == 1) ? pos + 0.25 / f0 : pos;
+			double pw;
+			{
+				double mr[16], mi[16], sumsq;
+				d4c2_windowed<32>(job == 2 ? 1 : 2, x, x_last, fs, f0, p, 4.0, rng + (long long)job * wl, 0, false, mr, mi, sumsq, ln,
+								  [&](int q, double ve, double vo) {
+									  d4_st(win, 64 * q + ln, ve);
+									  d4_st(win, 2048 + 64 * q + ln, vo);
+								  });
+				// (see the short form for the scale)
+				pw = (job == 2) ? 1.0 : 0.5 * (1.0 / sqrt(sumsq));
+				if (job == 0) D4_STAMP(1);
+			}
+			// (what a lane parks it reads back itself: program order is all the ordering the round trip needs)
+			auto master = [&](double (&re)[16], double (&im)[16], bool weighted, int odd) {
+				int ln = lane;
+				WC_FRESH(ln);  // (the weights below must not be hoisted out of the loop over the halves and spilled)
+#pragma unroll
+				for (int q = 0; q < 16; ++q) {
+					re[q] = d4_ld(win, 64 * q + ln);
+					im[q] = d4_ld(win, 2048 + 64 * q + ln);
+				}
+				WF_SCHED_FENCE();
+				if (weighted) {
+#pragma unroll
+					for (int q = 0; q < 16; ++q) {
+						const int i0 = 2 * ln + 128 * q;
+						re[q] *= i0 + 1.0;
+						im[q] *= i0 + 2.0;
+					}
+				}
+				// the samples folded in from 1024 packed points on: a group the window does not reach was not parked and adds nothing
+#pragma unroll
+				for (int qg = 16; qg < 32; qg += 8) {
+					if (qg * 128 >= wl) break;
+					const bool two = (qg + 4) * 128 < wl;
+					double ur[8], ui[8];
+#pragma unroll
+					for (int k = 0; k < 8; ++k) {
+						ur[k] = ui[k] = 0.0;
+						if (k < 4 || two) {
+							ur[k] = d4_ld(win, 64 * (qg + k) + ln);
+							ui[k] = d4_ld(win, 2048 + 64 * (qg + k) + ln);
+						}
+					}
+					WF_SCHED_FENCE();
+#pragma unroll
+					for (int k = 0; k < 8; ++k) {
+						if (k < 4 || two) {
+							const int q = qg + k, i0 = 2 * ln + 128 * q;
+							double ve = ur[k], vo = ui[k];
+							if (weighted) { ve *= i0 + 1.0; vo *= i0 + 2.0; }
+							if (odd) { re[q & 15] -= ve; im[q & 15] -= vo; }
+							else { re[q & 15] += ve; im[q & 15] += vo; }
+						}
+					}
+				}
+#pragma unroll
+				for (int q = 0; q < 16; ++q) {
+					re[q] *= pw;
+					im[q] *= pw;
+				}
+			};
+#pragma unroll 1
+			for (int odd = 0; odd < 2; ++odd) {
+				double re[16], im[16], nyq1;
+				master(re, im, false, odd);
+				wf_r2c4096_half(re, im, nyq1, 4, L, a.tw, ln, odd);
+				if (job == 0 && odd == 0) D4_STAMP(2);
+				if (job == 2) {
+#pragma unroll
+					for (int s = 0; s < 16; ++s) d4_st(row, 2048 + 1024 * odd + 64 * s + ln, 0.25 * fma(re[s], re[s], im[s] * im[s]));
+					if (odd == 0) spsM = 0.25 * (nyq1 * nyq1);
+				} else {
+					double ar[16], ai[16], nyq2;
+					master(ar, ai, true, odd);
+					wf_r2c4096_half(ar, ai, nyq2, 4, L, a.tw, ln, odd);
+					// job 0's products wait in the frame's own row for job 1's; the sum starts from 0.0 as the twin's does
+					double acc[16];
+#pragma unroll
+					for (int s = 0; s < 16; ++s) acc[s] = 0.0;
+					if (job == 1) {
+#pragma unroll
+						for (int s = 0; s < 16; ++s) acc[s] = d4_ld(row, 1024 * odd + 64 * s + ln);
+						WF_SCHED_FENCE();
+					}
+#pragma unroll
+					for (int s = 0; s < 16; ++s) acc[s] += fma(re[s], ar[s], im[s] * ai[s]);
+#pragma unroll
+					for (int s = 0; s < 16; ++s) d4_st(row, 1024 * odd + 64 * s + ln, acc[s]);
+					if (odd == 0) cenM += nyq1 * nyq2;
+					if (job == 0 && odd == 0) D4_STAMP(3);
+				}
+			}
+			if (job == 0) D4_STAMP(4);
+		}
 	} else
 #pragma unroll 1
 	for (int odd = 0; odd < 2; ++odd) {
@@ -1315,14 +1440,26 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WC_D4C2_OCC,
 	if constexpr (!LONG) {
 		const long long g = xcd_frame(blockIdx.x, a.total_frames);
 		if (g >= a.total_frames) return;
-		d4c2_frame<false>(a, g, L, lane);
+		d4c2_frame<kD4Short>(a, g, L, lane);
 	} else {
+		// (the fence between a block's frames also orders the reuse of its row of long_park)
 		const int n_long = *a.long_cnt;
 #pragma unroll 1
 		for (int i = blockIdx.x; i < n_long; i += gridDim.x) {
-			d4c2_frame<true>(a, a.long_list[1 + i], L, lane);
+			d4c2_frame<kD4Long>(a, a.long_list[1 + i], L, lane);
 			wf_fence();
 		}
+	}
+}
+// WC_D4C_LONG=halves: the list of d4c2_frames_kernel<true> in the per-half form, its A/B and bit-identity twin
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WC_D4C2_OCC, WC_D4C2_OCC))) void d4c2_frames_halves_kernel(D4cArgs a) {
+	__shared__ __attribute__((aligned(16))) double L[kD4Lds];
+	const int lane = threadIdx.x;
+	const int n_long = *a.long_cnt;
+#pragma unroll 1
+	for (int i = blockIdx.x; i < n_long; i += gridDim.x) {
+		d4c2_frame<kD4LongHalves>(a, a.long_list[1 + i], L, lane);
+		wf_fence();
 	}
 }
 
@@ -1954,12 +2091,13 @@ struct wc_d4c {
 	bool select64 = false;  // WC_D4C_SELECT=64 (D4cArgs::select64)
 	int band_waves = 3;  // N = 4096 band stage: d4c2_band_kernel<3> at three wavefronts per SIMD (default), WC_D4C_BAND_WAVES=2: <2>, its twin (select64 always takes the twin)
 	bool lt_listed = true;  // d4c2_lovetrain_kernel<true> walks a list of its frames (default); WC_D4C_LT_LIST=0: a grid of every frame (the A/B and bit-identity twin)
+	bool long_halves = false;  // WC_D4C_LONG=halves: the long-window frames in the per-half form (d4c2_frames_halves_kernel, the A/B and bit-identity twin of d4c2_frames_kernel<true>)
 	bool count_tails = false;  // WC_D4C_BAND_TAILS=1: count the band wavefronts that enter the 64-bit tail of the search (wc_debug_d4c_band_tails)
 	bool split;  // band loop and row output as separate kernels (default; WC_D4C_SPLIT=0: one fused kernel)
 	bool wave2;  // 4096-point transforms by two wavefronts per frame (d4c2_*; default where they apply, WC_D4C_IMPL=block: never)
 	Device *dev;
 	double f0_bound = 0.0;  // (a caller's promise about the contour's highest F0: no longer relied on -- the frames the wavefront kernels leave out are listed on the device)
-	DevBuf nuttall, utts, cnt, uidx, long_list, rare_list, lt_list, tails, off, endpos, endpos2, ap0, sgd, coarse, d_x, d_tpos, d_f0, d_ap;
+	DevBuf nuttall, utts, cnt, uidx, long_list, long_park, rare_list, lt_list, tails, off, endpos, endpos2, ap0, sgd, coarse, d_x, d_tpos, d_f0, d_ap;
 	HostBuf h_stage, h_rows, h_x;
 };
 
@@ -2028,6 +2166,10 @@ int d4c_enqueue(wc_d4c *d, hipStream_t s, int n_utt, const double *d_x, const in
 		if ((rc = d->sgd.reserve(sizeof(double) * (size_t)total * (main2 ? (size_t)row2 : (size_t)(d->fft_size_d4c / 2 + 1))))) return rc;
 		if ((rc = d->coarse.reserve(sizeof(double) * (size_t)total * kMaxBands))) return rc;
 	}
+	// the launch over the long-window frames: a fixed grid, a row of kD4Park doubles per block for the window it is at
+	const long long long_grid = std::min<long long>(((total + 7) / 8) * 8, kD4LongGrid);
+	const bool long_parked = main2 && d->fft_size_d4c == 4096 && !d->long_halves;
+	if (long_parked && (rc = d->long_park.reserve(sizeof(double) * (size_t)(long_grid * kD4Park)))) return rc;
 	if ((rc = d->endpos.reserve(sizeof(uint64_t) * n_utt))) return rc;
 	if ((rc = d->endpos2.reserve(sizeof(uint64_t) * n_utt))) return rc;
 	if ((rc = d->h_stage.reserve(sizeof(UttDesc) * n_utt + sizeof(uint64_t) * n_utt))) return rc;
@@ -2053,7 +2195,7 @@ int d4c_enqueue(wc_d4c *d, hipStream_t s, int n_utt, const double *d_x, const in
 	a.x = d_x; a.utts = d->utts.as<UttDesc>(); a.n_utt = n_utt; a.tpos = d_tpos; a.f0 = d_f0;
 	a.rng_off = d->off.as<unsigned long long>(); a.rng_table = dev->rng_table.as<uint32_t>(); a.rng_base = dev->rng_base;
 	a.tw = dev->twiddle; a.ap = d_ap; a.ap0 = d->ap0.as<double>(); a.cnt = d->cnt.as<uint32_t>(); a.uidx = d->uidx.as<int>(); a.long_cnt = d->long_list.as<int>(); a.long_list = d->long_list.as<int>();
-	a.sgd = d->sgd.as<double>(); a.coarse = d->coarse.as<double>();
+	a.sgd = d->sgd.as<double>(); a.coarse = d->coarse.as<double>(); a.long_park = long_parked ? d->long_park.as<double>() : nullptr;
 	a.nuttall = d->nuttall.as<double>(); a.total_frames = total; a.fs = d->fs; a.fft_size_out = fft_size;
 	a.n_ap = d->n_ap; a.window_length = d->window_length; a.threshold = d->threshold; a.select64 = d->select64 ? 1 : 0;
 	a.rare_only = 0;
@@ -2090,7 +2232,8 @@ int d4c_enqueue(wc_d4c *d, hipStream_t s, int n_utt, const double *d_x, const in
 			a.rare_only = 1;
 			if (d->fft_size_d4c == 4096) {
 				hipLaunchKernelGGL(d4c2_frames_kernel<false>, dim3((unsigned)blocks8), dim3(64), 0, s, a);
-				hipLaunchKernelGGL(d4c2_frames_kernel<true>, dim3((unsigned)std::min<long long>(blocks8, 4096)), dim3(64), 0, s, a);
+				if (long_parked) hipLaunchKernelGGL(d4c2_frames_kernel<true>, dim3((unsigned)long_grid), dim3(64), 0, s, a);
+				else hipLaunchKernelGGL(d4c2_frames_halves_kernel, dim3((unsigned)long_grid), dim3(64), 0, s, a);
 				hipLaunchKernelGGL((d4c_frames_kernel<4096, 512, true, true>), dim3(256), dim3(512), 0, s, a);
 			} else {
 				hipLaunchKernelGGL(d4c1_frames_kernel, dim3((unsigned)blocks8), dim3(64), 0, s, a);
@@ -2138,6 +2281,19 @@ extern "C" int wc_debug_d4c_band_tails(wc_d4c *d, unsigned int *tails) {
 	DeviceLock lock(d->dev);
 	WC_HIP(hipStreamSynchronize(d->dev->active()));
 	WC_HIP(hipMemcpy(tails, d->tails.p, sizeof(unsigned int), hipMemcpyDeviceToHost));
+	return WC_OK;
+}
+
+// the number of gated frames with windows longer than 2048 samples that the handle's last call listed for the second launch of
+// its frames stage (d4c2_frames_kernel<true>, or its twin under WC_D4C_LONG=halves); -1: a handle whose frames stage lists none
+extern "C" int wc_debug_d4c_long_count(wc_d4c *d, int *n) {
+	if (!d || !n) return fail(WC_ERR_INVALID, "d4c: null argument");
+	*n = -1;
+	if (!(d->wave2 && d->split && d->fft_size_d4c == 4096 && d->window_length <= 1023) || !d->long_list.p) return WC_OK;
+	WC_HIP(hipSetDevice(d->dev->id));
+	DeviceLock lock(d->dev);
+	WC_HIP(hipStreamSynchronize(d->dev->active()));
+	WC_HIP(hipMemcpy(n, d->long_list.p, sizeof(int), hipMemcpyDeviceToHost));
 	return WC_OK;
 }
 
@@ -2248,6 +2404,8 @@ wc_d4c *wc_d4c_create(int fs, double threshold) {
 		if (bw && (std::strcmp(bw, "2") == 0 || std::strcmp(bw, "3") == 0)) d->band_waves = bw[0] - '0';
 		const char *ll = getenv("WC_D4C_LT_LIST");
 		d->lt_listed = !(ll && ll[0] == '0');
+		const char *lw = getenv("WC_D4C_LONG");
+		d->long_halves = lw && std::strcmp(lw, "halves") == 0;
 		const char *ct = getenv("WC_D4C_BAND_TAILS");
 		d->count_tails = ct && ct[0] == '1';
 		const char *impl = getenv("WC_D4C_IMPL");
@@ -2284,7 +2442,7 @@ void wc_d4c_destroy(wc_d4c *d) {
 	if (!d) return;
 	d->dev->quiesce();
 	d->dev->handle_gone();
-	d->nuttall.release(); d->utts.release(); d->cnt.release(); d->uidx.release(); d->long_list.release(); d->rare_list.release(); d->lt_list.release(); d->tails.release(); d->off.release(); d->endpos.release(); d->endpos2.release();
+	d->nuttall.release(); d->utts.release(); d->cnt.release(); d->uidx.release(); d->long_list.release(); d->long_park.release(); d->rare_list.release(); d->lt_list.release(); d->tails.release(); d->off.release(); d->endpos.release(); d->endpos2.release();
 	d->ap0.release(); d->sgd.release(); d->coarse.release(); d->d_x.release(); d->d_tpos.release(); d->d_f0.release(); d->d_ap.release(); d->h_stage.release(); d->h_rows.release(); d->h_x.release();
 	delete d;
 }
