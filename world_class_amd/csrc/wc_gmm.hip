@@ -1,6 +1,6 @@
 // Joint-density GMM conversion (include/world_class_gmm.h).
 //
-//   gmm_ll_kernel    ll(t, m) of THE rule of convert.  A block of eight wavefronts takes a tile of 64 frames: the tile's source vectors
+//   gmm_ll_kernel    (wc_gmm_ll.hpp, shared with the training) ll(t, m) of THE rule of convert.  A block of eight wavefronts takes a tile of 64 frames: the tile's source vectors
 //                    are read along the rows (neighbouring threads on neighbouring columns), widened, and parked in LDS transposed,
 //                    65 doubles from column to column, so that both the writes and the reads (lane = frame) miss each other's banks.
 //                    Each wavefront then walks mixtures of its own: m = first + wave, + 8, ... inside the block's share of them
@@ -25,6 +25,7 @@
 #include "../../include/world_class_gmm.h"
 #include "wc_features_batch.hpp"
 #include "wc_features_rows.hpp"
+#include "wc_gmm_ll.hpp"
 #include "wc_gmm_plan.hpp"
 #include "wc_internal.hpp"
 
@@ -39,85 +40,8 @@ struct wc_gmm {
 
 namespace {
 
-constexpr int kTile = 64, kPitch = kTile + 1, kRows = 16, kWaves = 8;
-static_assert(kRows == 16, "gmm_q cuts the rest of the rows into blocks of 16, 8 and 4");
 constexpr size_t kTableBytes = (size_t)256 << 20;  // the most scratch one launch's table of ll takes
 constexpr long long kChunkMax = 1ll << 24;         // frames of one launch at the most
-
-struct GmmDev {
-	const double *Wt;   // [m][k][i]: W_m(i,k), 0.0 where i < k
-	const double *Bt;   // [m][k][j]: B_m(j,k)
-	const double *mux, *muy, *c, *cvar;
-	int n_mix, dx, dy;
-};
-
-// rows i0 .. i0 + R - 1 of z for this lane's frame, and their squares added to q in ascending i; xl: the lane's column of the tile
-// (x(k) at xl[k * kPitch])
-template <int R>
-__device__ __forceinline__ double gmm_rows(const double *__restrict__ Wm, const double *__restrict__ mu, const double *xl, int dx, int i0, double q) {
-	double z[R];
-	const double *w = Wm + i0;
-	double dk = xl[0] - mu[0];
-#pragma unroll
-	for (int r = 0; r < R; ++r) z[r] = w[r] * dk;
-#pragma unroll 2
-	for (int k = 1; k <= i0; ++k) {  // columns 1 .. i0 reach all R rows
-		w += dx;
-		dk = xl[k * kPitch] - mu[k];
-#pragma unroll
-		for (int r = 0; r < R; ++r) z[r] = z[r] + w[r] * dk;
-	}
-	// the triangle: column i0 + j reaches rows i0 + j .. i0 + R - 1.  (Rows at and past dx read what lies behind them and are dropped.)
-#pragma unroll
-	for (int j = 1; j < R; ++j) {
-		if (i0 + j < dx) {
-			w = Wm + (size_t)(i0 + j) * dx + i0;
-			dk = xl[(i0 + j) * kPitch] - mu[i0 + j];
-#pragma unroll
-			for (int r = j; r < R; ++r) z[r] = z[r] + w[r] * dk;
-		}
-	}
-#pragma unroll
-	for (int r = 0; r < R; ++r)
-		if (i0 + r < dx) q = i0 + r == 0 ? z[r] * z[r] : q + z[r] * z[r];
-	return q;
-}
-
-// q of one mixture: blocks of kRows rows, the rest in the narrowest block that holds it
-__device__ __forceinline__ double gmm_q(const double *__restrict__ Wm, const double *__restrict__ mu, const double *xl, int dx) {
-	double q = 0.0;
-	int i0 = 0;
-	for (; i0 + kRows <= dx; i0 += kRows) q = gmm_rows<kRows>(Wm, mu, xl, dx, i0, q);
-	const int rest = dx - i0;
-	if (rest > 8) q = gmm_rows<kRows>(Wm, mu, xl, dx, i0, q);
-	else if (rest > 4) q = gmm_rows<8>(Wm, mu, xl, dx, i0, q);
-	else if (rest > 0) q = gmm_rows<4>(Wm, mu, xl, dx, i0, q);
-	return q;
-}
-
-// table: ll of frame t0 at its start
-template <class T>
-__global__ __launch_bounds__(kTile * kWaves) void gmm_ll_kernel(GmmDev g, long long t0, long long n_end, const T *__restrict__ rows, int ld_in,
-																  int col_in, int per, double *__restrict__ table) {
-	extern __shared__ __attribute__((aligned(16))) double gmm_x[];  // dx * kPitch
-	const int tid = threadIdx.x, dx = g.dx;
-	const long long tbase = t0 + (long long)blockIdx.x * kTile;
-	for (int idx = tid; idx < kTile * dx; idx += kTile * kWaves) {
-		const int ff = idx / dx, col = idx - ff * dx;
-		const long long t = tbase + ff;
-		gmm_x[col * kPitch + ff] = t < n_end ? (double)rows[(size_t)t * ld_in + col_in + col] : 0.0;
-	}
-	__syncthreads();
-	const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-	const int m_begin = blockIdx.y * per, m_end = m_begin + per < g.n_mix ? m_begin + per : g.n_mix;
-	const long long t = tbase + lane;
-	const double *xl = gmm_x + lane;
-	for (int m = m_begin + wave; m < m_end; m += kWaves) {
-		const double q = gmm_q(g.Wt + (size_t)m * dx * dx, g.mux + (size_t)m * dx, xl, dx);
-		const double ll = g.c[m] - 0.5 * q;
-		if (t < n_end) table[(size_t)(t - t0) * g.n_mix + m] = ll;
-	}
-}
 
 template <class T, class O>
 __global__ __launch_bounds__(64) void gmm_pick_kernel(GmmDev g, long long t0, const T *__restrict__ rows, int ld_in, int col_in,
@@ -175,7 +99,7 @@ __global__ __launch_bounds__(64) void gmm_pick_kernel(GmmDev g, long long t0, co
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
-size_t lds_bytes_of(int dx) { return (size_t)dx * kPitch * sizeof(double); }
+size_t lds_bytes_of(int dx) { return gmm_lds_bytes_of(dx); }
 
 int refuse(const char *why) { return fail(WC_ERR_INVALID, std::string("gmm convert: ") + why); }
 
@@ -307,24 +231,12 @@ int wc_gmm_convert_device(const wc_gmm *g, long long n_frames, int in_format, co
 	dv.c = dv.muy + M * Y;
 	dv.cvar = dv.c + M;
 	dv.n_mix = n_mix; dv.dx = dx; dv.dy = dy;
-	const size_t lds = lds_bytes_of(dx);
 	for (long long t0 = 0; t0 < n_frames; t0 += chunk) {
 		const long long nc = n_frames - t0 < chunk ? n_frames - t0 : chunk;
 		double *table = d_loglik ? d_loglik + (size_t)t0 * n_mix : dev->features_scratch.as<double>();
-		// the mixtures are cut into shares of whole eights (a wavefront each) where the tiles alone leave compute units idle
-		const long long tiles = (nc + kTile - 1) / kTile, want = 4ll * g->cus;
-		long long split = (want + tiles - 1) / tiles;
-		const long long most = (n_mix + kWaves - 1) / kWaves;
-		split = split < 1 ? 1 : (split > most ? most : split);
-		const int per = (int)(((n_mix + split - 1) / split + kWaves - 1) / kWaves * kWaves);
-		const dim3 grid((unsigned)tiles, (unsigned)((n_mix + per - 1) / per));
 		if ((rc = dev->time_begin("gmm_ll_kernel", s))) return rc;
-		if (in_format == WC_FEAT_F32)
-			hipLaunchKernelGGL(gmm_ll_kernel<float>, grid, dim3(kTile * kWaves), lds, s, dv, t0, n_frames, static_cast<const float *>(d_rows_in), ld_in,
-							   col_in, per, table);
-		else
-			hipLaunchKernelGGL(gmm_ll_kernel<double>, grid, dim3(kTile * kWaves), lds, s, dv, t0, n_frames, static_cast<const double *>(d_rows_in), ld_in,
-							   col_in, per, table);
+		if (in_format == WC_FEAT_F32) gmm_ll_launch(dv, g->cus, s, t0, nc, n_frames, static_cast<const float *>(d_rows_in), ld_in, col_in, table);
+		else gmm_ll_launch(dv, g->cus, s, t0, nc, n_frames, static_cast<const double *>(d_rows_in), ld_in, col_in, table);
 		WC_HIP(hipGetLastError());
 		if ((rc = dev->time_end("gmm_ll_kernel", s))) return rc;
 		if (!pick) continue;

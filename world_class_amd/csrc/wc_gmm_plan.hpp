@@ -17,6 +17,39 @@ struct GmmPlan {
 
 inline bool gmm_finite(double v) { return std::fabs(v) <= 1.7976931348623157e308; }  // not NaN, not infinite
 
+// THE rule's Cholesky and W = L^-1 on the n x n matrix whose lower triangle stands in S (row i at S + i * ld): L and W are n x n
+// row-major, and only their lower triangles are written.  -> the row whose diagonal s is not > 0 or not finite (L and W are then
+// unfinished), or -1.  The conversion applies it to Sxx, the training (wc_gmm_train_plan.hpp) to the whole joint matrix.
+inline long gmm_factor(size_t n, const double *S, size_t ld, double *L, double *W) {
+	for (size_t i = 0; i < n; ++i)
+		for (size_t j = 0; j <= i; ++j) {
+			double s = S[i * ld + j];
+			for (size_t k = 0; k < j; ++k) s = s - L[i * n + k] * L[j * n + k];
+			if (j < i) {
+				L[i * n + j] = s / L[j * n + j];
+			} else {
+				if (!(s > 0.0) || !gmm_finite(s)) return (long)i;
+				L[i * n + i] = std::sqrt(s);
+			}
+		}
+	for (size_t j = 0; j < n; ++j) {
+		W[j * n + j] = 1.0 / L[j * n + j];
+		for (size_t i = j + 1; i < n; ++i) {
+			double s = L[i * n + j] * W[j * n + j];
+			for (size_t k = j + 1; k < i; ++k) s = s + L[i * n + k] * W[k * n + j];
+			W[i * n + j] = -s / L[i * n + i];
+		}
+	}
+	return -1;
+}
+
+// c of THE rule for a factor of n rows: (log(w) - ld) - (0.5 * (double)n) * log(2 pi), ld the sum of log L(i,i) ascending
+inline double gmm_constant(size_t n, double w, const double *L) {
+	double ld = std::log(L[0]);
+	for (size_t i = 1; i < n; ++i) ld = ld + std::log(L[i * n + i]);
+	return (std::log(w) - ld) - (0.5 * (double)n) * 1.8378770664093453;
+}
+
 // fills *p; a refusal leaves its text in *why and returns false
 inline bool gmm_prepare(int n_mix, int dx, int dy, const double *weight, const double *mean, const double *cov, GmmPlan *p, std::string *why) {
 	const auto no = [&](const std::string &text) { *why = text; return false; };
@@ -46,25 +79,8 @@ inline bool gmm_prepare(int n_mix, int dx, int dy, const double *weight, const d
 		double *L = Lbuf.data(), *W = p->W.data() + (size_t)m * X * X, *B = p->B.data() + (size_t)m * Y * X;
 		for (size_t i = 0; i < X; ++i) p->mux[m * X + i] = mean[m * D + i];
 		for (size_t j = 0; j < Y; ++j) p->muy[m * Y + j] = mean[m * D + X + j];
-		for (size_t i = 0; i < X; ++i)
-			for (size_t j = 0; j <= i; ++j) {
-				double s = S[i * D + j];
-				for (size_t k = 0; k < j; ++k) s = s - L[i * X + k] * L[j * X + k];
-				if (j < i) {
-					L[i * X + j] = s / L[j * X + j];
-				} else {
-					if (!(s > 0.0) || !gmm_finite(s)) return no(at(m, i) + ": the source covariance is not positive definite (a Cholesky diagonal that is not > 0 or not finite)");
-					L[i * X + i] = std::sqrt(s);
-				}
-			}
-		for (size_t j = 0; j < X; ++j) {
-			W[j * X + j] = 1.0 / L[j * X + j];
-			for (size_t i = j + 1; i < X; ++i) {
-				double s = L[i * X + j] * W[j * X + j];
-				for (size_t k = j + 1; k < i; ++k) s = s + L[i * X + k] * W[k * X + j];
-				W[i * X + j] = -s / L[i * X + i];
-			}
-		}
+		const long bad = gmm_factor(X, S, D, L, W);
+		if (bad >= 0) return no(at(m, (size_t)bad) + ": the source covariance is not positive definite (a Cholesky diagonal that is not > 0 or not finite)");
 		for (size_t j = 0; j < Y; ++j) {
 			const double *Syx = S + (X + j) * D;
 			for (size_t k = 0; k < X; ++k) {
@@ -77,9 +93,7 @@ inline bool gmm_prepare(int n_mix, int dx, int dy, const double *weight, const d
 			if (!(s > 0.0) || !gmm_finite(s)) return no(at(m, X + j) + ": a conditional variance that is not > 0 or not finite");
 			p->cvar[m * Y + j] = s;
 		}
-		double ld = std::log(L[0]);
-		for (size_t i = 1; i < X; ++i) ld = ld + std::log(L[i * X + i]);
-		p->c[m] = (std::log(weight[m]) - ld) - (0.5 * (double)dx) * 1.8378770664093453;
+		p->c[m] = gmm_constant(X, weight[m], L);
 	}
 	return true;
 }
