@@ -207,3 +207,27 @@ def test_cheaptrick_split_kernel_against_the_sixteen_points_kernel(wca, port, mo
     r1 = wca.Pipeline(fs).run_batch([x, x[:20000]])
     for u in range(2):
         assert np.array_equal(r1[u]["f0"], r2[u]["f0"]) and rel(r2[u]["sp"], r1[u]["sp"]) < 1e-10
+
+
+FAR = 2 ** 33 + 12345  # a noise position no draw table reaches from 0
+
+
+@pytest.mark.parametrize("order", [(0, 1), (1, 0)])
+def test_cheaptrick_utterance_without_frames_does_not_stretch_the_draw_table(wca, order):
+    """the device call with an utterance that has samples but no frames at position 0 next to one at FAR: the table is sized over the
+    utterances that draw, the empty one's position stands, the other one's rows and end position are those of the call with it alone"""
+    fs = 16000
+    x, other = make_utterance(fs, 0.3, 31), make_utterance(fs, 0.3, 32)
+    tpos, f0 = wca.Harvest(fs).compute(x)
+    c, DA = wca.CheapTrick(fs), wca.DeviceArray
+    n, bins = len(f0), c.bins
+    d_t, d_f, d_sp = DA.from_host(tpos), DA.from_host(f0), DA.from_host(np.zeros(n * bins))
+    end, = c.compute_device(DA.from_host(x), [len(x)], d_t, d_f, [n], d_sp, rng_pos=[FAR])
+    alone = d_sp.to_host((n, bins))
+    assert end > FAR and (alone > 0).all()
+    xs, f_len, pos = [other, x], [0, n], [0, FAR]
+    xs, f_len, pos = [[v[k] for k in order] for v in (xs, f_len, pos)]
+    d_sp2 = DA.from_host(np.zeros(n * bins))
+    got = c.compute_device(DA.from_host(np.concatenate(xs)), [len(v) for v in xs], d_t, d_f, f_len, d_sp2, rng_pos=pos)
+    assert got[order.index(0)] == 0 and got[order.index(1)] == end
+    assert np.array_equal(d_sp2.to_host((n, bins)), alone)

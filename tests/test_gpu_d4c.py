@@ -204,3 +204,27 @@ def test_d4c_one_transform_kernels_against_the_block_kernels_and_frames_they_lea
     port.rng_reset()
     assert np.abs(a - b).max() < AP_ABS
     assert np.abs(a - ref).max() < AP_ABS
+
+
+FAR = 2 ** 33 + 12345  # a noise position no draw table reaches from 0
+
+
+@pytest.mark.parametrize("order", [(0, 1), (1, 0)])
+def test_d4c_utterance_without_frames_does_not_stretch_the_draw_table(wca, order):
+    """the device call with an utterance that has samples but no frames at position 0 next to one at FAR: the table is sized over the
+    utterances that draw, the empty one's position stands, the other one's rows and end position are those of the call with it alone"""
+    fs, n_fft = 16000, 1024
+    x, other = make_utterance(fs, 0.3, 31), make_utterance(fs, 0.3, 32)
+    tpos, f0 = wca.Harvest(fs).compute(x)
+    n, bins = len(f0), n_fft // 2 + 1
+    d, DA = wca.D4C(fs), wca.DeviceArray
+    d_t, d_f, d_ap = DA.from_host(tpos), DA.from_host(f0), DA.from_host(np.zeros(n * bins))
+    end, = d.compute_device(DA.from_host(x), [len(x)], d_t, d_f, [n], n_fft, d_ap, rng_pos=[FAR])
+    alone = d_ap.to_host((n, bins))
+    assert end > FAR and (alone > 0).all()
+    xs, f_len, pos = [other, x], [0, n], [0, FAR]
+    xs, f_len, pos = [[v[k] for k in order] for v in (xs, f_len, pos)]
+    d_ap2 = DA.from_host(np.zeros(n * bins))
+    got = d.compute_device(DA.from_host(np.concatenate(xs)), [len(v) for v in xs], d_t, d_f, f_len, n_fft, d_ap2, rng_pos=pos)
+    assert got[order.index(0)] == 0 and got[order.index(1)] == end
+    assert np.array_equal(d_ap2.to_host((n, bins)), alone)

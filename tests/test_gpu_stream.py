@@ -274,3 +274,52 @@ def test_config5_shape_512_streams_frame_accounting_and_identical_streams(wca, p
         assert np.array_equal(res[u]["f0"], res[u % 4]["f0"]) and np.array_equal(res[u]["sp"], res[u % 4]["sp"]), u
     for u in range(4):
         compare_oracle(res[u], oracle_whole(port, xs[u], fs, 1.0), "stream %d vs oracle" % u)
+
+
+def test_a_stream_that_commits_nothing_next_to_one_far_away_in_the_noise(wca):
+    """Two analysis streams with aperiodicity, stream 1's noise positions 2^33 draws away.  In one push stream 0 commits no frames
+    (its look-ahead is not filled yet) while stream 1 commits some: the stages' call on both must size the draw table over the
+    stream that draws alone.  Utterances of 0.3 s end with their second push at chunk 200 / lookahead 400 ms, so no push there has a
+    stream without frames next to one with frames; the smallest settings the streams take with 5 ms frames and aperiodicity do:
+    chunk, lookback and lookahead of 40 ms (multiples of lcm(8 ms, frame period), at least 38 ms around a frame for D4C)."""
+    from world_class_amd.stream import StreamAnalyzer
+    fs, far = 16000, 2 ** 33 + 12345
+    x = make_utterance(fs, 0.3, 5310)
+    sa = StreamAnalyzer(fs, 2, frame_period=5.0, chunk_ms=40, lookback_ms=40, lookahead_ms=40, aperiodicity=True)
+    sa.set_rng_position(1, far)
+    sa.set_d4c_rng_position(1, far)
+    cs, none = sa.chunk_samples, np.zeros(0)
+    acc = [dict(tpos=[], f0=[], sp=[], ap=[]) for _ in range(2)]
+    at = [0, 0]  # samples fed per stream
+
+    def push(streams):
+        chunks = [x[at[u]:at[u] + cs] if u in streams else none for u in range(2)]
+        flush = [1 if u in streams and at[u] + cs >= len(x) else 0 for u in range(2)]
+        before = [sa.frames_committed(u) for u in range(2)]
+        for u, r in enumerate(sa.push(chunks, flush)):
+            for k in acc[u]:
+                acc[u][k].append(r[k])
+        for u in streams:
+            at[u] += cs
+        return [sa.frames_committed(u) - before[u] for u in range(2)]
+
+    while sa.frames_committed(1) == 0:  # stream 1 alone until it commits frames
+        push([1])
+    assert at[1] < len(x) - cs
+    got = push([0, 1])
+    assert got[0] == 0 and got[1] > 0, got
+    while at[0] < len(x):
+        push([u for u in range(2) if at[u] < len(x)])
+    res = [{k: np.concatenate(v) for k, v in a.items()} for a in acc]
+    assert np.array_equal(res[0]["f0"], res[1]["f0"]) and np.array_equal(res[0]["tpos"], res[1]["tpos"]) and (res[0]["f0"] > 0).any()
+    ends = []
+    for u, start in enumerate((0, far)):
+        wca.rng_set_position(start)
+        want = wca.D4C(fs).compute(x, res[u]["tpos"], res[u]["f0"], sa.fft_size)
+        ends.append(wca.rng_get_position())
+        unv = lambda a: (a > 1.0 - 1e-9).all(axis=1)  # LoveTrain's unvoiced frames
+        assert np.array_equal(unv(res[u]["ap"]), unv(want)), u
+        assert np.abs(res[u]["ap"] - want).max() <= 1e-7, (u, np.abs(res[u]["ap"] - want).max())
+    wca.rng_set_position(0)
+    assert sa.d4c_rng_position(1) == ends[1] and sa.d4c_rng_position(0) == ends[1] - far == ends[0]
+    assert sa.rng_position(1) - far == sa.rng_position(0) > 0

@@ -258,3 +258,28 @@ def test_stage_call_in_two_halves_equals_one_piece_and_retries_only_the_half_tha
     assert wca.lib().wc_release_scratch() == 0
     ys3 = s.compute_batch(*arg(cases[:3]), rng_pos=start[:3])[0]  # (the staging comes back on the next call)
     assert all(np.array_equal(a, b) for a, b in zip(ys3, ys[:3]))
+
+
+FAR = 2 ** 33 + 12345  # a noise position no draw table reaches from 0
+
+
+@pytest.mark.parametrize("order", [(0, 1), (1, 0)])
+def test_synthesis_utterance_without_output_does_not_stretch_the_draw_table(wca, order):
+    """the device call with an utterance of no output samples at position 0 next to one at FAR: the table is sized over the
+    utterances that draw, the empty one's position stands, the other one's samples and end position are those of the call with it alone"""
+    fs = 16000
+    x = make_utterance(fs, 0.3, 31)
+    tpos, f0 = wca.Harvest(fs).compute(x)
+    ct = wca.CheapTrick(fs)
+    sp, ap = ct.compute(x, tpos, f0), wca.D4C(fs).compute(x, tpos, f0, ct.fft_size)
+    sy, DA = wca.Synthesis(fs, ct.fft_size, 5.0), wca.DeviceArray
+    n, m = len(f0), sy.out_length(len(f0))
+    d_y = DA.from_host(np.zeros(m))
+    end, = sy.compute_device(DA.from_host(f0), [n], DA.from_host(sp), DA.from_host(ap), [m], d_y, rng_pos=[FAR])
+    alone = d_y.to_host()
+    assert end > FAR and np.abs(alone).max() > 1e-3
+    d_y2 = DA.from_host(np.zeros(m))
+    got = sy.compute_device(DA.from_host(np.concatenate([f0, f0])), [n, n], DA.from_host(np.concatenate([sp, sp])), DA.from_host(np.concatenate([ap, ap])),
+                            [[0, m][k] for k in order], d_y2, rng_pos=[[0, FAR][k] for k in order])
+    assert got[order.index(0)] == 0 and got[order.index(1)] == end
+    assert np.array_equal(d_y2.to_host(), alone)

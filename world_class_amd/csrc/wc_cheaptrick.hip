@@ -7,6 +7,8 @@
 // confined to summation order (block reductions / block scan instead of sequential loops), our own
 // FFT, and device libm; the noise draws come from the exact stream positions the reference's serial
 // order would use (see wc_core.hip).
+// The host half is shared with the other stages: descriptors, batch layout and the range of noise draws a call asks the table for
+// (wc_stage_plan.hpp), option readers (wc_options.hpp), descriptor upload, end positions and the host-pointer call (wc_hostcopy.hpp).
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -18,6 +20,7 @@
 #include "wc_frames.hpp"
 #include "wc_wavefft.hpp"
 #include "wc_hostcopy.hpp"
+#include "wc_options.hpp"
 #include "wc_stages.hpp"
 
 namespace wc {
@@ -1287,8 +1290,13 @@ struct wc_cheaptrick {
 	Device *dev;
 	DevBuf utts, cnt, uidx, rare, off, endpos, d_x, d_tpos, d_f0, d_sp;
 	HostBuf h_stage, h_rows, h_x;
-	double f0_bound = 0.0;  // (a caller's promise about the contour's highest F0: no longer relied on -- the frames the wavefront kernels leave out are listed on the device)
 };
+
+// the development options, read once when the handle is created
+static void ct_read_options(wc_cheaptrick *c) {
+	c->wave = !opt_is("WC_CT_IMPL", "block");
+	c->split = opt_is("WC_CT_IMPL", "split");  // N = 2048 on eight points per lane (ct_wave_split_kernel; A/B)
+}
 
 // Threads per frame: eight samples per thread up to N = 2048 (one radix-4 butterfly per thread and pass, nobody idle): 256
 // threads at N = 1024 / 512 left half / three quarters of them idle in every FFT pass while barriers, reductions and the
@@ -1309,40 +1317,21 @@ static void launch_ct(const CtArgs &a, hipStream_t s) {
 //   ct_prepare  descriptors upload, per-frame draw counts, per-utterance scan -> c->off, c->endpos (device)
 //   ct_frames   the per-frame kernel (may run on another stream once ct_prepare's work is done)
 int ct_prepare(wc_cheaptrick *c, hipStream_t s, int n_utt, const int *x_length, const double *d_f0, const int *f0_length,
-			   const uint64_t *rng_pos, long long *total_out, uint64_t *min_pos_out, uint64_t *max_end_out) {
+			   const uint64_t *rng_pos, long long *total_out) {
 	const int bins = c->fft_size / 2 + 1;
-	std::vector<UttDesc> utts(n_utt);
-	long long xo = 0, fo = 0;
-	uint64_t min_pos = ~0ull, max_end = 0;
-	const uint64_t per_frame_max = (uint64_t)(2 * (c->fft_size / 2) + 1 + bins);
-	for (int u = 0; u < n_utt; ++u) {
+	for (int u = 0; u < n_utt; ++u)
 		if (x_length[u] <= 0 || f0_length[u] < 0) return fail(WC_ERR_INVALID, "cheaptrick: non-positive length");
-		UttDesc &d = utts[u];
-		d.x_off = xo; d.f_off = fo; d.y_off = 0;
-		d.x_len = x_length[u]; d.f_len = f0_length[u]; d.y_len = 0; d.f_base = 0;
-		d.rng_pos = rng_pos ? rng_pos[u] : 0ull;
-		xo += x_length[u];
-		fo += f0_length[u];
-		if (d.rng_pos < min_pos) min_pos = d.rng_pos;
-		uint64_t e = d.rng_pos + per_frame_max * (uint64_t)d.f_len;
-		if (e > max_end) max_end = e;
-	}
-	const long long total = fo;
+	std::vector<UttDesc> utts(n_utt);
+	const long long total = batch_layout(n_utt, x_length, f0_length, nullptr, rng_pos, utts.data()).f;
 	*total_out = total;
-	*min_pos_out = min_pos;
-	*max_end_out = max_end;
 	if (total == 0) return WC_OK;
 	int rc;
-	if ((rc = c->utts.reserve(sizeof(UttDesc) * n_utt))) return rc;
 	if ((rc = c->cnt.reserve(sizeof(uint32_t) * total))) return rc;
 	if ((rc = c->uidx.reserve(sizeof(int) * total))) return rc;
 	if ((rc = c->rare.reserve(sizeof(int) * (total + 1)))) return rc;
 	if ((rc = c->off.reserve(sizeof(uint64_t) * total))) return rc;
 	if ((rc = c->endpos.reserve(sizeof(uint64_t) * n_utt))) return rc;
-	if ((rc = c->h_stage.reserve(sizeof(UttDesc) * n_utt + sizeof(uint64_t) * n_utt))) return rc;
-	std::memcpy(c->h_stage.p, utts.data(), sizeof(UttDesc) * n_utt);
-	WC_HIP(hipMemcpyAsync(c->utts.p, c->h_stage.p, sizeof(UttDesc) * n_utt, hipMemcpyHostToDevice, s));
-	if ((rc = c->h_stage.mark(s))) return rc;
+	if ((rc = utts_up(s, utts, c->h_stage, c->utts))) return rc;
 	hipLaunchKernelGGL(ct_count_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, d_f0, total, c->fs,
 					   c->f0_floor, bins, c->cnt.as<uint32_t>(), c->utts.as<UttDesc>(), n_utt, c->uidx.as<int>(), c->rare.as<int>());
 	hipLaunchKernelGGL(utt_scan_kernel, dim3(n_utt), dim3(256), 0, s, c->cnt.as<uint32_t>(), c->utts.as<UttDesc>(),
@@ -1393,7 +1382,6 @@ int ct_frames(wc_cheaptrick *c, hipStream_t s, int n_utt, const double *d_x, con
 	return dev->time_end("cheaptrick_frames", s);
 }
 
-void ct_set_f0_bound(wc_cheaptrick *c, double f0_bound) { c->f0_bound = f0_bound; }
 const unsigned long long *ct_end_positions(const wc_cheaptrick *c) { return c->endpos.as<unsigned long long>(); }
 
 static int ct_run_device(wc_cheaptrick *c, int n_utt, const double *d_x, const int *x_length, const double *d_tpos,
@@ -1401,32 +1389,15 @@ static int ct_run_device(wc_cheaptrick *c, int n_utt, const double *d_x, const i
 	Device *dev = c->dev;
 	hipStream_t s = dev->active();
 	long long total = 0;
-	uint64_t min_pos = 0, max_end = 0;
 	int rc;
 	// sizes first (the RNG table must exist before anything is enqueued that may outlive a reallocation)
-	{
-		const int bins = c->fft_size / 2 + 1;
-		const uint64_t per_frame_max = (uint64_t)(2 * (c->fft_size / 2) + 1 + bins);
-		uint64_t lo = ~0ull, hi = 0;
-		for (int u = 0; u < n_utt; ++u) {
-			if (f0_length[u] <= 0) continue;  // (no frames, no draws: its position -- a stream reset hours after the others -- must not stretch the table)
-			uint64_t p0 = rng_pos ? rng_pos[u] : 0ull;
-			lo = p0 < lo ? p0 : lo;
-			uint64_t e = p0 + per_frame_max * (uint64_t)f0_length[u];
-			hi = e > hi ? e : hi;
-		}
-		if (hi > lo && (rc = dev->ensure_rng(lo, hi))) return rc;
-	}
-	if ((rc = ct_prepare(c, s, n_utt, x_length, d_f0, f0_length, rng_pos, &total, &min_pos, &max_end))) return rc;
+	DrawRange draws;
+	for (int u = 0; u < n_utt; ++u) draws.add(rng_pos ? rng_pos[u] : 0ull, cheaptrick_draws(c->fft_size, f0_length[u]));
+	if (!draws.empty() && (rc = dev->ensure_rng(draws.lo, draws.hi))) return rc;
+	if ((rc = ct_prepare(c, s, n_utt, x_length, d_f0, f0_length, rng_pos, &total))) return rc;
 	if (total == 0) return WC_OK;
 	if ((rc = ct_frames(c, s, n_utt, d_x, d_tpos, d_f0, d_sp, total, nullptr))) return rc;
-	if (rng_pos) {
-		std::vector<uint64_t> h_end(n_utt);
-		WC_HIP(hipMemcpyAsync(h_end.data(), c->endpos.p, sizeof(uint64_t) * n_utt, hipMemcpyDeviceToHost, s));
-		WC_HIP(hipStreamSynchronize(s));
-		for (int u = 0; u < n_utt; ++u) rng_pos[u] = h_end[u];
-	}
-	return WC_OK;
+	return rng_pos ? end_positions_down(s, c->endpos, n_utt, rng_pos) : WC_OK;
 }
 
 wc::Device *ct_device(const wc_cheaptrick *c) { return c->dev; }
@@ -1447,11 +1418,7 @@ wc_cheaptrick *wc_cheaptrick_create(int fs, double q1, double f0_floor, int fft_
 	c->fft_size = fft_size ? fft_size : wc_cheaptrick_fft_size(fs, f0_floor);  // reference :36-41
 	c->f0_floor = wc_cheaptrick_f0_floor(fs, c->fft_size);                      // reference :44
 	c->dev = dev;
-	{
-		const char *impl = getenv("WC_CT_IMPL");
-		c->wave = !(impl && std::strcmp(impl, "block") == 0);
-		c->split = impl && std::strcmp(impl, "split") == 0;  // N = 2048 on eight points per lane (ct_wave_split_kernel; A/B)
-	}
+	ct_read_options(c);
 	if (!fft_size_supported(c->fft_size)) {
 		set_error("cheaptrick: fft_size must be 512, 1024, 2048 or 4096 (fs between 8 kHz and 96 kHz)");
 		delete c;
@@ -1489,28 +1456,10 @@ int wc_cheaptrick_compute(wc_cheaptrick *c, const double *x, int x_length, const
 	if (!c || !x || !temporal_positions || !f0 || !spectrogram) return fail(WC_ERR_INVALID, "cheaptrick: null argument");
 	if (x_length <= 0 || f0_length < 0) return fail(WC_ERR_INVALID, "cheaptrick: bad length");
 	if (f0_length == 0) return WC_OK;
-	WC_HIP(hipSetDevice(c->dev->id));
-	DeviceLock lock(c->dev);
-	hipStream_t s = c->dev->active();
-	const int bins = c->fft_size / 2 + 1;
-	int rc;
-	if ((rc = c->d_x.reserve(sizeof(double) * x_length))) return rc;
-	if ((rc = c->d_tpos.reserve(sizeof(double) * f0_length))) return rc;
-	if ((rc = c->d_f0.reserve(sizeof(double) * f0_length))) return rc;
-	if ((rc = c->d_sp.reserve(sizeof(double) * (size_t)f0_length * bins))) return rc;
-	if ((rc = array_up(s, x, (size_t)x_length, c->h_x, c->d_x.as<double>()))) return rc;
-	WC_HIP(hipMemcpyAsync(c->d_tpos.p, temporal_positions, sizeof(double) * f0_length, hipMemcpyHostToDevice, s));
-	WC_HIP(hipMemcpyAsync(c->d_f0.p, f0, sizeof(double) * f0_length, hipMemcpyHostToDevice, s));
-	uint64_t pos = global_rng_position();
-	rc = ct_run_device(c, 1, c->d_x.as<double>(), &x_length, c->d_tpos.as<double>(), c->d_f0.as<double>(), &f0_length,
-					   c->d_sp.as<double>(), &pos);
-	if (rc) return rc;
-	set_global_rng_position(pos);
-	// the rows come down into page-locked staging (a pageable destination takes the copy engine's slow path, and a fresh 16 MB
-	// vector per call is 4096 page faults) and go to the caller's rows by a few threads
-	const size_t n_sp = (size_t)f0_length * bins;
-	if ((rc = c->h_rows.reserve(sizeof(double) * n_sp))) return rc;
-	return rows_down(s, spectrogram, f0_length, bins, c->d_sp.as<double>(), c->h_rows.as<double>());
+	return rows_call(c->dev, {c->d_x, c->d_tpos, c->d_f0, c->d_sp, c->h_x, c->h_rows}, x, x_length, temporal_positions, f0, f0_length,
+					 c->fft_size / 2 + 1, spectrogram, [&](const double *d_x, const double *d_tpos, const double *d_f0, double *d_sp, uint64_t *pos) {
+						 return ct_run_device(c, 1, d_x, &x_length, d_tpos, d_f0, &f0_length, d_sp, pos);
+					 });
 }
 
 }  // extern "C"

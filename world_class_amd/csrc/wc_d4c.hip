@@ -13,6 +13,8 @@
 //   (WC_D4C_SPLIT=0 runs the last three in one fused d4c_frames_kernel.)
 // The noise draws come from the exact stream positions of the reference's serial order: all
 // LoveTrain frames first, then the gated frames (RNG draw-count contract).
+// The host half is shared with the other stages: descriptors, batch layout, a frame's draw bound and the range a call asks the table
+// for (wc_stage_plan.hpp), option readers (wc_options.hpp), descriptor upload, end positions and the host-pointer call (wc_hostcopy.hpp).
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -25,6 +27,7 @@
 #include "wc_frames.hpp"
 #include "wc_wavefft.hpp"
 #include "wc_hostcopy.hpp"
+#include "wc_options.hpp"
 
 namespace wc {
 
@@ -2096,10 +2099,20 @@ struct wc_d4c {
 	bool split;  // band loop and row output as separate kernels (default; WC_D4C_SPLIT=0: one fused kernel)
 	bool wave2;  // 4096-point transforms by two wavefronts per frame (d4c2_*; default where they apply, WC_D4C_IMPL=block: never)
 	Device *dev;
-	double f0_bound = 0.0;  // (a caller's promise about the contour's highest F0: no longer relied on -- the frames the wavefront kernels leave out are listed on the device)
 	DevBuf nuttall, utts, cnt, uidx, long_list, long_park, rare_list, lt_list, tails, off, endpos, endpos2, ap0, sgd, coarse, d_x, d_tpos, d_f0, d_ap;
 	HostBuf h_stage, h_rows, h_x;
 };
+
+// the development options, read once when the handle is created
+static void d4c_read_options(wc_d4c *d) {
+	d->split = !opt_off("WC_D4C_SPLIT");  // default: split schedule; WC_D4C_SPLIT=0 runs the single fused kernel
+	d->select64 = opt_is("WC_D4C_SELECT", "64");
+	if (opt_is("WC_D4C_BAND_WAVES", "2")) d->band_waves = 2;  // ("2" or "3" and nothing else; 3 is the default)
+	d->lt_listed = !opt_off("WC_D4C_LT_LIST");
+	d->long_halves = opt_is("WC_D4C_LONG", "halves");
+	d->count_tails = opt_on("WC_D4C_BAND_TAILS");
+	d->wave2 = !opt_is("WC_D4C_IMPL", "block");
+}
 
 template <int N>
 static void launch_lt(const D4cArgs &a, hipStream_t s) {
@@ -2130,28 +2143,12 @@ int d4c_enqueue(wc_d4c *d, hipStream_t s, int n_utt, const double *d_x, const in
 				const unsigned long long *d_start) {
 	Device *dev = d->dev;
 	if (fft_size < 2 || (fft_size & 1)) return fail(WC_ERR_INVALID, "d4c: fft_size must be even and positive");
-	std::vector<UttDesc> utts(n_utt);
-	long long xo = 0, fo = 0;
-	uint64_t min_pos = ~0ull, max_end = 0;
-	const uint64_t lt_max = (uint64_t)(2 * (int)(3.0 * d->fs / 40.0 / 2.0 + 1.0) + 1);
-	const uint64_t main_max = 3ull * (uint64_t)(2 * (int)(4.0 * d->fs / 47.0 / 2.0 + 1.0) + 1);
-	for (int u = 0; u < n_utt; ++u) {
+	for (int u = 0; u < n_utt; ++u)
 		if (x_length[u] <= 0 || f0_length[u] < 0) return fail(WC_ERR_INVALID, "d4c: non-positive length");
-		UttDesc &t = utts[u];
-		t.x_off = xo; t.f_off = fo; t.y_off = 0;
-		t.x_len = x_length[u]; t.f_len = f0_length[u]; t.y_len = 0; t.f_base = 0;
-		t.rng_pos = rng_pos ? rng_pos[u] : 0ull;
-		xo += x_length[u];
-		fo += f0_length[u];
-		if (t.rng_pos < min_pos) min_pos = t.rng_pos;
-		uint64_t e = t.rng_pos + (lt_max + main_max) * (uint64_t)t.f_len;
-		if (e > max_end) max_end = e;
-	}
-	const long long total = fo;
-	(void)min_pos; (void)max_end;
+	std::vector<UttDesc> utts(n_utt);
+	const long long total = batch_layout(n_utt, x_length, f0_length, nullptr, rng_pos, utts.data()).f;
 	if (total == 0) return WC_OK;
 	int rc;
-	if ((rc = d->utts.reserve(sizeof(UttDesc) * n_utt))) return rc;
 	if ((rc = d->cnt.reserve(sizeof(uint32_t) * total))) return rc;
 	if ((rc = d->uidx.reserve(sizeof(int) * total))) return rc;
 	if ((rc = d->long_list.reserve(sizeof(int) * (total + 1)))) return rc;  // [0]: the count
@@ -2172,10 +2169,7 @@ int d4c_enqueue(wc_d4c *d, hipStream_t s, int n_utt, const double *d_x, const in
 	if (long_parked && (rc = d->long_park.reserve(sizeof(double) * (size_t)(long_grid * kD4Park)))) return rc;
 	if ((rc = d->endpos.reserve(sizeof(uint64_t) * n_utt))) return rc;
 	if ((rc = d->endpos2.reserve(sizeof(uint64_t) * n_utt))) return rc;
-	if ((rc = d->h_stage.reserve(sizeof(UttDesc) * n_utt + sizeof(uint64_t) * n_utt))) return rc;
-	std::memcpy(d->h_stage.p, utts.data(), sizeof(UttDesc) * n_utt);
-	WC_HIP(hipMemcpyAsync(d->utts.p, d->h_stage.p, sizeof(UttDesc) * n_utt, hipMemcpyHostToDevice, s));
-	if ((rc = d->h_stage.mark(s))) return rc;
+	if ((rc = utts_up(s, utts, d->h_stage, d->utts))) return rc;
 	const unsigned grid1 = (unsigned)((total + 255) / 256);
 	// LoveTrain's long-window frames are listed by the count kernel itself: the list's count is zeroed here, in front of it
 	const bool lt_listed = d->lt_listed && d->wave2 && d->fft_size_lt == 4096;
@@ -2348,39 +2342,19 @@ extern "C" int wc_debug_d4c_bands(wc_d4c *d, int n_frames, const double *rows, d
 	return WC_OK;
 }
 
-void d4c_set_f0_bound(wc_d4c *d, double f0_bound) { d->f0_bound = f0_bound; }
 const unsigned long long *d4c_end_positions(const wc_d4c *d) { return d->endpos2.as<unsigned long long>(); }
-
-// upper bound of the stream positions one utterance can consume (LoveTrain + three windows per frame)
-uint64_t d4c_draw_bound(const wc_d4c *d, int f0_length) {
-	const uint64_t lt_max = (uint64_t)(2 * (int)(3.0 * d->fs / 40.0 / 2.0 + 1.0) + 1);
-	const uint64_t main_max = 3ull * (uint64_t)(2 * (int)(4.0 * d->fs / 47.0 / 2.0 + 1.0) + 1);
-	return (lt_max + main_max) * (uint64_t)(f0_length > 0 ? f0_length : 0);
-}
 
 static int d4c_run_device(wc_d4c *d, int n_utt, const double *d_x, const int *x_length, const double *d_tpos,
 						  const double *d_f0, const int *f0_length, int fft_size, double *d_ap, uint64_t *rng_pos) {
 	Device *dev = d->dev;
 	hipStream_t s = dev->active();
 	int rc;
-	uint64_t lo = ~0ull, hi = 0;
-	long long total = 0;
-	for (int u = 0; u < n_utt; ++u) {
-		uint64_t p0 = rng_pos ? rng_pos[u] : 0ull;
-		lo = p0 < lo ? p0 : lo;
-		uint64_t e = p0 + d4c_draw_bound(d, f0_length[u]);
-		hi = e > hi ? e : hi;
-		total += f0_length[u] > 0 ? f0_length[u] : 0;
-	}
-	if ((rc = dev->ensure_rng(lo, hi))) return rc;
+	DrawRange draws;
+	for (int u = 0; u < n_utt; ++u) draws.add(rng_pos ? rng_pos[u] : 0ull, d4c_draws(d->fs, f0_length[u]));
+	if (!draws.empty() && (rc = dev->ensure_rng(draws.lo, draws.hi))) return rc;
 	if ((rc = d4c_enqueue(d, s, n_utt, d_x, x_length, d_tpos, d_f0, f0_length, fft_size, d_ap, rng_pos, nullptr))) return rc;
-	if (rng_pos && total > 0) {
-		std::vector<uint64_t> h_end(n_utt);
-		WC_HIP(hipMemcpyAsync(h_end.data(), d->endpos2.p, sizeof(uint64_t) * n_utt, hipMemcpyDeviceToHost, s));
-		WC_HIP(hipStreamSynchronize(s));
-		for (int u = 0; u < n_utt; ++u) rng_pos[u] = h_end[u];
-	}
-	return WC_OK;
+	// (a batch without frames has enqueued nothing: the positions stand)
+	return rng_pos && !draws.empty() ? end_positions_down(s, d->endpos2, n_utt, rng_pos) : WC_OK;
 }
 
 wc::Device *d4c_device(const wc_d4c *d) { return d->dev; }
@@ -2395,22 +2369,7 @@ wc_d4c *wc_d4c_create(int fs, double threshold) {
 	d->fs = fs;
 	d->threshold = threshold;
 	d->dev = dev;
-	{
-		const char *sp = getenv("WC_D4C_SPLIT");  // default: split schedule; WC_D4C_SPLIT=0 runs the single fused kernel
-		d->split = !(sp && sp[0] == '0');
-		const char *sel = getenv("WC_D4C_SELECT");
-		d->select64 = sel && std::strcmp(sel, "64") == 0;
-		const char *bw = getenv("WC_D4C_BAND_WAVES");
-		if (bw && (std::strcmp(bw, "2") == 0 || std::strcmp(bw, "3") == 0)) d->band_waves = bw[0] - '0';
-		const char *ll = getenv("WC_D4C_LT_LIST");
-		d->lt_listed = !(ll && ll[0] == '0');
-		const char *lw = getenv("WC_D4C_LONG");
-		d->long_halves = lw && std::strcmp(lw, "halves") == 0;
-		const char *ct = getenv("WC_D4C_BAND_TAILS");
-		d->count_tails = ct && ct[0] == '1';
-		const char *impl = getenv("WC_D4C_IMPL");
-		d->wave2 = !(impl && std::strcmp(impl, "block") == 0);
-	}
+	d4c_read_options(d);
 	// reference src/d4c.cpp:60-111
 	d->fft_size_d4c = static_cast<int>(std::pow(2.0, 1.0 + static_cast<int>(std::log(4.0 * fs / 47.0 + 1) / 0.69314718055994529)));
 	d->n_ap = static_cast<int>(std::fmin(15000.0, fs / 2.0 - 3000.0) / 3000.0);
@@ -2461,26 +2420,10 @@ int wc_d4c_compute(wc_d4c *d, const double *x, int x_length, const double *tempo
 	if (!d || !x || !temporal_positions || !f0 || !aperiodicity) return fail(WC_ERR_INVALID, "d4c: null argument");
 	if (x_length <= 0 || f0_length < 0) return fail(WC_ERR_INVALID, "d4c: bad length");
 	if (f0_length == 0) return WC_OK;
-	WC_HIP(hipSetDevice(d->dev->id));
-	DeviceLock lock(d->dev);
-	hipStream_t s = d->dev->active();
-	const int bins = fft_size / 2 + 1;
-	int rc;
-	if ((rc = d->d_x.reserve(sizeof(double) * x_length))) return rc;
-	if ((rc = d->d_tpos.reserve(sizeof(double) * f0_length))) return rc;
-	if ((rc = d->d_f0.reserve(sizeof(double) * f0_length))) return rc;
-	if ((rc = d->d_ap.reserve(sizeof(double) * (size_t)f0_length * bins))) return rc;
-	if ((rc = array_up(s, x, (size_t)x_length, d->h_x, d->d_x.as<double>()))) return rc;
-	WC_HIP(hipMemcpyAsync(d->d_tpos.p, temporal_positions, sizeof(double) * f0_length, hipMemcpyHostToDevice, s));
-	WC_HIP(hipMemcpyAsync(d->d_f0.p, f0, sizeof(double) * f0_length, hipMemcpyHostToDevice, s));
-	uint64_t pos = global_rng_position();
-	rc = d4c_run_device(d, 1, d->d_x.as<double>(), &x_length, d->d_tpos.as<double>(), d->d_f0.as<double>(), &f0_length,
-						fft_size, d->d_ap.as<double>(), &pos);
-	if (rc) return rc;
-	set_global_rng_position(pos);
-	const size_t n_ap = (size_t)f0_length * bins;  // (page-locked staging, rows handed over by a few threads: see wc_cheaptrick_compute)
-	if ((rc = d->h_rows.reserve(sizeof(double) * n_ap))) return rc;
-	return rows_down(s, aperiodicity, f0_length, bins, d->d_ap.as<double>(), d->h_rows.as<double>());
+	return rows_call(d->dev, {d->d_x, d->d_tpos, d->d_f0, d->d_ap, d->h_x, d->h_rows}, x, x_length, temporal_positions, f0, f0_length,
+					 fft_size / 2 + 1, aperiodicity, [&](const double *d_x, const double *d_tpos, const double *d_f0, double *d_ap, uint64_t *pos) {
+						 return d4c_run_device(d, 1, d_x, &x_length, d_tpos, d_f0, &f0_length, fft_size, d_ap, pos);
+					 });
 }
 
 }  // extern "C"

@@ -30,6 +30,8 @@
 //                        the extension walks (<1>), which get a wavefront per (voiced section, direction)
 //   hv_smooth_kernel     zero-lag Butterworth per voiced section, one lane per section (:639-703)
 //   hv_output_kernel     1 ms contour -> frame_period grid (:199-204)
+// The development options (the WC_HARVEST_* variables named above and at the fields of wc_harvest) are read once, in
+// hv_read_options at the top of wc_harvest_create, through the readers of wc_options.hpp.
 #include <atomic>
 #include <cmath>
 #include <cstdio>
@@ -45,6 +47,7 @@
 #include "wc_internal.hpp"
 #include "wc_frames.hpp"
 #include "wc_hostcopy.hpp"
+#include "wc_options.hpp"
 
 namespace wc {
 
@@ -4486,6 +4489,24 @@ static int hv_run_device(wc_harvest *h, int n_utt, const double *d_x, const int 
 	return fail(WC_ERR_DEVICE, "harvest: zero-crossing buffer overflow");
 }
 
+// the development options, read once when the handle is created (what each one selects: see the fields of wc_harvest)
+static void hv_read_options(wc_harvest *h) {
+	h->use_fir = opt_is("WC_HARVEST_BANDPASS", "fir");
+	h->ignore_ties = opt_is("WC_HARVEST_TIES", "ignore");
+	h->force_tie = (int)opt_int("WC_HARVEST_FORCE_TIE", -1);
+	h->no_quiet = opt_is("WC_HARVEST_QUIET", "sliding");
+	h->sdft_lanes = (int)opt_int("WC_HARVEST_SDFT_LANES", 0);
+	h->sdft8_max = opt_int("WC_HARVEST_SDFT8_MAX", 3072);
+	h->debug_small_caps = opt_set("WC_DEBUG_SMALL_CAPS");
+	h->direct_decimation = opt_is("WC_HARVEST_DECIMATE", "direct");
+	h->chunked_decimation = h->direct_decimation || opt_is("WC_HARVEST_DECIMATE", "chunks");
+	h->smooth_full_walk = opt_is("WC_HARVEST_SMOOTH", "full");
+	const char *refine = "WC_HARVEST_REFINE";
+	h->refine_mode = opt_is(refine, "slots") ? 1 : opt_is(refine, "packed") ? 2 : opt_is(refine, "group2") ? 3 : opt_is(refine, "group8") ? 4 : 0;
+	h->raw_from_lists = opt_is("WC_HARVEST_RAW", "lists");
+	h->raw_mode = opt_is("WC_HARVEST_RAW", "blocks") ? 1 : opt_is("WC_HARVEST_RAW", "four") ? 2 : 0;
+}
+
 wc::Device *hv_device(const wc_harvest *h) { return h->dev; }
 
 extern "C" {
@@ -4510,6 +4531,7 @@ wc_harvest *wc_harvest_create(int fs, double f0_floor, double f0_ceil, double fr
 	h->channels_in_octave = channels_in_octave; h->dev = dev;
 	h->use_cos_table_opt = use_cos_table;
 	h->use_cos_table = use_cos_table != 0;
+	hv_read_options(h);
 	// reference src/harvest.cpp:82-84, :1388-1397, :1418-1419
 	h->decim = std::max(std::min(h_mround(fs / target_fs), 12), 1);
 	h->fs_d = static_cast<double>(fs) / h->decim;
@@ -4578,22 +4600,7 @@ wc_harvest *wc_harvest_create(int fs, double f0_floor, double f0_ceil, double fr
 		ok = ok && h->d_sd_rot.reserve(sizeof(double2) * sd_rot.size()) == 0 && h->d_sd_p0.reserve(sizeof(double2) * sd_p0.size()) == 0 &&
 			 hipMemcpy(h->d_sd_rot.p, sd_rot.data(), sizeof(double2) * sd_rot.size(), hipMemcpyHostToDevice) == hipSuccess &&
 			 hipMemcpy(h->d_sd_p0.p, sd_p0.data(), sizeof(double2) * sd_p0.size(), hipMemcpyHostToDevice) == hipSuccess;
-		const char *bp = getenv("WC_HARVEST_BANDPASS");
-		h->use_fir = bp && std::strcmp(bp, "fir") == 0;
-		const char *ti = getenv("WC_HARVEST_TIES");
-		h->ignore_ties = ti && std::strcmp(ti, "ignore") == 0;
-		h->force_tie = getenv("WC_HARVEST_FORCE_TIE") ? atoi(getenv("WC_HARVEST_FORCE_TIE")) : -1;
-		const char *qu = getenv("WC_HARVEST_QUIET");
-		h->no_quiet = qu && std::strcmp(qu, "sliding") == 0;
-		const char *sl = getenv("WC_HARVEST_SDFT_LANES");
-		h->sdft_lanes = sl ? atoi(sl) : 0;
-		const char *sm8 = getenv("WC_HARVEST_SDFT8_MAX");
-		h->sdft8_max = sm8 ? atoll(sm8) : 3072;
 		h->tables_valid = false;
-		h->debug_small_caps = getenv("WC_DEBUG_SMALL_CAPS") != nullptr;
-		const char *dm = getenv("WC_HARVEST_DECIMATE");
-		h->direct_decimation = dm && std::strcmp(dm, "direct") == 0;
-		h->chunked_decimation = dm && (std::strcmp(dm, "direct") == 0 || std::strcmp(dm, "chunks") == 0);
 		{
 			// powers of the recursion's state matrix A = [a0 a1 a2; 1 0 0; 0 1 0] (state = the last three values of the recursion's
 			// inner sequence, newest first), in extended precision: A^(C 2^j) for the scan's levels, A^(C (l + 1)) for the carry
@@ -4624,13 +4631,6 @@ wc_harvest *wc_harvest_create(int fs, double f0_floor, double f0_ceil, double fr
 			ok = ok && h->d_dec_ptab.reserve(sizeof(double) * ptab.size()) == 0 &&
 				 hipMemcpy(h->d_dec_ptab.p, ptab.data(), sizeof(double) * ptab.size(), hipMemcpyHostToDevice) == hipSuccess;
 		}
-		const char *sm = getenv("WC_HARVEST_SMOOTH");
-		h->smooth_full_walk = sm && std::strcmp(sm, "full") == 0;
-		const char *rfm = getenv("WC_HARVEST_REFINE");
-		h->refine_mode = !rfm ? 0 : std::strcmp(rfm, "slots") == 0 ? 1 : std::strcmp(rfm, "packed") == 0 ? 2 : std::strcmp(rfm, "group2") == 0 ? 3 : std::strcmp(rfm, "group8") == 0 ? 4 : 0;
-		const char *rw = getenv("WC_HARVEST_RAW");
-		h->raw_from_lists = rw && std::strcmp(rw, "lists") == 0;
-		h->raw_mode = rw && std::strcmp(rw, "blocks") == 0 ? 1 : rw && std::strcmp(rw, "four") == 0 ? 2 : 0;
 	}
 	{
 		std::vector<double2> rot(2 * (RF_MAXHW + 1));

@@ -200,4 +200,54 @@ inline int rows_up(hipStream_t s, const double *const *rows, int n_rows, int bin
 	return WC_OK;
 }
 
+// The shared pieces of the CheapTrick and D4C handles' host side.
+// A call's descriptors -> device through the handle's page-locked staging (asynchronous; `stage` is marked busy until the stream has passed)
+inline int utts_up(hipStream_t s, const std::vector<UttDesc> &utts, HostBuf &stage, DevBuf &d_utts) {
+	const size_t bytes = sizeof(UttDesc) * utts.size();
+	int rc;
+	if ((rc = d_utts.reserve(bytes)) || (rc = stage.reserve(bytes))) return rc;
+	std::memcpy(stage.p, utts.data(), bytes);
+	WC_HIP(hipMemcpyAsync(d_utts.p, stage.p, bytes, hipMemcpyHostToDevice, s));
+	return stage.mark(s);
+}
+
+// the end positions behind a run -> the caller's array (the stream is drained)
+inline int end_positions_down(hipStream_t s, const DevBuf &d_end, int n_utt, uint64_t *rng_pos) {
+	std::vector<uint64_t> h_end(n_utt);
+	WC_HIP(hipMemcpyAsync(h_end.data(), d_end.p, sizeof(uint64_t) * n_utt, hipMemcpyDeviceToHost, s));
+	WC_HIP(hipStreamSynchronize(s));
+	std::copy(h_end.begin(), h_end.end(), rng_pos);
+	return WC_OK;
+}
+
+// The host-pointer, single-utterance call of a stage that turns samples, a time axis and a contour into rows of `bins` doubles
+// (arguments already checked, f0_length > 0): up through the handle's buffers, run(d_x, d_tpos, d_f0, d_rows, &position) at the
+// process-wide noise position, and the rows down into page-locked staging (a pageable destination takes the copy engine's slow
+// path, and a fresh 16 MB vector per call is 4096 page faults), from where a few threads hand them to the caller's rows.
+struct RowsCallBufs {
+	DevBuf &d_x, &d_tpos, &d_f0, &d_rows;
+	HostBuf &h_x, &h_rows;
+};
+template <class Run>
+inline int rows_call(Device *dev, RowsCallBufs b, const double *x, int x_length, const double *temporal_positions, const double *f0,
+					 int f0_length, int bins, double **rows, Run run) {
+	WC_HIP(hipSetDevice(dev->id));
+	DeviceLock lock(dev);
+	hipStream_t s = dev->active();
+	const size_t n_rows = (size_t)f0_length * bins;
+	int rc;
+	if ((rc = b.d_x.reserve(sizeof(double) * x_length))) return rc;
+	if ((rc = b.d_tpos.reserve(sizeof(double) * f0_length))) return rc;
+	if ((rc = b.d_f0.reserve(sizeof(double) * f0_length))) return rc;
+	if ((rc = b.d_rows.reserve(sizeof(double) * n_rows))) return rc;
+	if ((rc = array_up(s, x, (size_t)x_length, b.h_x, b.d_x.as<double>()))) return rc;
+	WC_HIP(hipMemcpyAsync(b.d_tpos.p, temporal_positions, sizeof(double) * f0_length, hipMemcpyHostToDevice, s));
+	WC_HIP(hipMemcpyAsync(b.d_f0.p, f0, sizeof(double) * f0_length, hipMemcpyHostToDevice, s));
+	uint64_t pos = global_rng_position();
+	if ((rc = run(b.d_x.as<double>(), b.d_tpos.as<double>(), b.d_f0.as<double>(), b.d_rows.as<double>(), &pos))) return rc;
+	set_global_rng_position(pos);
+	if ((rc = b.h_rows.reserve(sizeof(double) * n_rows))) return rc;
+	return rows_down(s, rows, f0_length, bins, b.d_rows.as<double>(), b.h_rows.as<double>());
+}
+
 }  // namespace wc

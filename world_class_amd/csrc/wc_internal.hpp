@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/world_class_c.h"
+#include "wc_stage_plan.hpp"  // UttDesc, the batch layout, the draw range
 
 namespace wc {
 
@@ -133,16 +134,6 @@ void set_global_rng_position(uint64_t position);
 struct DeviceLock {
 	std::unique_lock<std::recursive_mutex> lk;
 	explicit DeviceLock(Device *d) : lk(d->mu) {}
-};
-
-// utterance descriptors uploaded per batch call
-struct UttDesc {
-	long long x_off;   // first sample in the packed sample array
-	long long f_off;   // first frame (row) in the packed frame arrays
-	long long y_off;   // first output sample (synthesis)
-	int x_len, f_len, y_len;
-	int f_base;        // absolute frame held in row f_off (synthesis streams; 0 for batch calls): frame k is row f_off + k - f_base
-	unsigned long long rng_pos;  // stream position at which this utterance starts the stage
 };
 
 // host-side RNG jump-ahead (GF(2) linear algebra on the xorshift128 state)

@@ -169,10 +169,6 @@ static int pipeline_ensure_groups(wc_pipeline *p, int ng) {
 		G.d4 = G.ct ? wc_d4c_create(p->fs, p->c_threshold) : nullptr;
 		G.sy = G.d4 ? wc_synthesis_create(p->fs, p->fft_size, p->frame_period) : nullptr;
 		if (!G.sy) return WC_ERR_DEVICE;  // (the failed create has set the error text; wc_pipeline_destroy releases what exists)
-		// the contour these stages see comes out of Harvest: candidates outside [floor, ceil] are struck (reference
-		// src/harvest.cpp:974-979) and the smoothing filter overshoots by a few per cent at most
-		ct_set_f0_bound(G.ct, 1.25 * p->c_ceil);
-		d4c_set_f0_bound(G.d4, 1.25 * p->c_ceil);
 		if (g == 0) { G.main = p->dev->active(); G.aux = p->s1; G.aux_hi = p->s1_hi; }
 		else if (g == 1) { G.main = p->n_split > 1 ? p->hs[1] : p->s2; G.aux = p->s2; }
 		// (groups 2 .. 5 have no streams of their own: HIP multiplexes the streams of one priority onto four hardware queues, and a
@@ -234,10 +230,6 @@ wc_pipeline *wc_pipeline_create(int fs, double frame_period, double harvest_f0_f
 	p->d4 = p->ct ? wc_d4c_create(fs, d4c_threshold) : nullptr;
 	p->sy = p->d4 ? wc_synthesis_create(fs, p->fft_size, frame_period) : nullptr;
 	bool ok = p->sy != nullptr;
-	if (ok) {  // (the contour these stages see comes out of Harvest, see below)
-		ct_set_f0_bound(p->ct, 1.25 * harvest_f0_ceil);
-		d4c_set_f0_bound(p->d4, 1.25 * harvest_f0_ceil);
-	}
 	ok = ok && hipStreamCreateWithFlags(&p->s1, hipStreamNonBlocking) == hipSuccess;
 	ok = ok && hipStreamCreateWithFlags(&p->s2, hipStreamNonBlocking) == hipSuccess;
 	ok = ok && hipEventCreateWithFlags(&p->e0, hipEventDisableTiming) == hipSuccess;
@@ -361,21 +353,18 @@ static int pipeline_run(wc_pipeline *p, int n_utt, const double *d_x, const int 
 	Device *dev = p->dev;
 	hipStream_t s0 = dev->active();
 	std::vector<int> f_len(n_utt), y_len(n_utt);
-	uint64_t lo = ~0ull, hi = 0;
+	DrawRange draws;
 	const int bins = p->fft_size / 2 + 1;
 	for (int u = 0; u < n_utt; ++u) {
 		if (x_length[u] <= 0) return fail(WC_ERR_INVALID, "pipeline: non-positive x_length");
 		f_len[u] = wc_get_samples(p->fs, x_length[u], p->frame_period);
 		y_len[u] = wc_synthesis_out_length(f_len[u], p->frame_period, p->fs);
 		if (f_len[u] < 2) return fail(WC_ERR_INVALID, "pipeline: utterance shorter than two frames");
-		const uint64_t p0 = rng_pos ? rng_pos[u] : 0ull;
-		const uint64_t bound = (uint64_t)(2 * (p->fft_size / 2) + 1 + bins) * (uint64_t)f_len[u] + d4c_draw_bound(p->d4, f_len[u]) +
-							   (uint64_t)y_len[u];
-		lo = p0 < lo ? p0 : lo;
-		hi = p0 + bound > hi ? p0 + bound : hi;
+		// (the three stages draw one behind the other from the utterance's position)
+		draws.add(rng_pos ? rng_pos[u] : 0ull, cheaptrick_draws(p->fft_size, f_len[u]) + d4c_draws(p->fs, f_len[u]) + synthesis_draws(y_len[u]));
 	}
 	int rc;
-	if ((rc = dev->ensure_rng(lo, hi))) return rc;
+	if ((rc = dev->ensure_rng(draws.lo, draws.hi))) return rc;
 	// the start positions are read from a private copy: rng_pos is also the output and a capacity retry re-reads them
 	std::vector<uint64_t> rng_in;
 	if (rng_pos) rng_in.assign(rng_pos, rng_pos + n_utt);
@@ -400,9 +389,8 @@ static int pipeline_run(wc_pipeline *p, int n_utt, const double *d_x, const int 
 			for (int attempt = 0; attempt < 3 && !done; ++attempt) {
 				int rc2;
 				long long total = 0;
-				uint64_t a0 = 0, a1 = 0;
 				if ((rc2 = hv_enqueue(t, s0, nu, gx, x_length + u0, gt, gf, hv_full, nullptr, nullptr))) return rc2;
-				if ((rc2 = ct_prepare(p->ct, s0, nu, x_length + u0, gf, f_len.data() + u0, rng_start ? rng_start + u0 : nullptr, &total, &a0, &a1))) return rc2;
+				if ((rc2 = ct_prepare(p->ct, s0, nu, x_length + u0, gf, f_len.data() + u0, rng_start ? rng_start + u0 : nullptr, &total))) return rc2;
 				if ((rc2 = ct_frames(p->ct, s0, nu, gx, gt, gf, gsp, total, nullptr))) return rc2;
 				if ((rc2 = d4c_enqueue(p->d4, s0, nu, gx, x_length + u0, gt, gf, f_len.data() + u0, p->fft_size, gap, nullptr, ct_end_positions(p->ct)))) return rc2;
 				if ((rc2 = syn_prepare(p->sy, s0, nu, gf, f_len.data() + u0, y_len.data() + u0, gy, nullptr, syn_full))) return rc2;
@@ -599,9 +587,8 @@ static int pipeline_run(wc_pipeline *p, int n_utt, const double *d_x, const int 
 					double *gy = d_y + sl[g].yo;
 					const uint64_t *grp_rng = rng_start ? rng_start + u0 : nullptr;
 					long long total = 0;
-					uint64_t a0 = 0, a1 = 0;
 					if ((rc = hv_enqueue(hvg[g], S, nu, gx, x_length + u0, gt, gf, full[g][0], nullptr, nullptr, 2, nullptr, G.e_mid))) return rc;
-					if ((rc = ct_prepare(G.ct, S, nu, x_length + u0, gf, f_len.data() + u0, grp_rng, &total, &a0, &a1))) return rc;
+					if ((rc = ct_prepare(G.ct, S, nu, x_length + u0, gf, f_len.data() + u0, grp_rng, &total))) return rc;
 					WC_HIP(hipEventRecord(G.e0, S));
 					if ((rc = syn_prepare(G.sy, S, nu, gf, f_len.data() + u0, y_len.data() + u0, gy, nullptr, full[g][1]))) return rc;
 					WC_HIP(hipEventRecord(G.e_ct, S));
@@ -652,8 +639,7 @@ static int pipeline_run(wc_pipeline *p, int n_utt, const double *d_x, const int 
 				double *gy = d_y + sl[g].yo;
 				const uint64_t *grp_rng = rng_start ? rng_start + u0 : nullptr;
 				long long total = 0;
-				uint64_t a0 = 0, a1 = 0;
-				if ((rc = ct_prepare(G.ct, mainS[g], nu, x_length + u0, gf, f_len.data() + u0, grp_rng, &total, &a0, &a1))) return rc;
+				if ((rc = ct_prepare(G.ct, mainS[g], nu, x_length + u0, gf, f_len.data() + u0, grp_rng, &total))) return rc;
 				WC_HIP(hipEventRecord(G.e0, mainS[g]));
 				if (gpu_marks) WC_HIP(hipEventRecord(tm[g][0], mainS[g]));
 				WC_HIP(hipStreamWaitEvent(G_aux, G.e0, 0));
@@ -801,8 +787,7 @@ static int pipeline_run(wc_pipeline *p, int n_utt, const double *d_x, const int 
 			for (int k = 1; k < ns; ++k) WC_HIP(hipStreamWaitEvent(s0, p->he[k], 0));
 		}
 		long long total = 0;
-		uint64_t a0 = 0, a1 = 0;
-		if ((rc = ct_prepare(p->ct, s0, n_utt, x_length, d_f0, f_len.data(), rng_start, &total, &a0, &a1))) return rc;
+		if ((rc = ct_prepare(p->ct, s0, n_utt, x_length, d_f0, f_len.data(), rng_start, &total))) return rc;
 		WC_HIP(hipEventRecord(p->e0, s0));
 		WC_HIP(hipStreamWaitEvent(ns > 1 ? p->hs[1] : p->s1, p->e0, 0));
 		WC_HIP(hipStreamWaitEvent(p->s2, p->e0, 0));

@@ -28,19 +28,15 @@ double *hv_candidate_rows(wc_harvest *h);
 double *hv_score_rows(wc_harvest *h);
 
 int ct_prepare(wc_cheaptrick *c, hipStream_t s, int n_utt, const int *x_length, const double *d_f0, const int *f0_length,
-			   const uint64_t *rng_pos, long long *total_out, uint64_t *min_pos_out, uint64_t *max_end_out);
+			   const uint64_t *rng_pos, long long *total_out);
 int ct_frames(wc_cheaptrick *c, hipStream_t s, int n_utt, const double *d_x, const double *d_tpos, const double *d_f0,
 			  double *d_sp, long long total, hipEvent_t *rows_done);
 const unsigned long long *ct_end_positions(const wc_cheaptrick *c);
-// the caller vouches that no F0 handed to the stage exceeds f0_bound (0: no promise): passes over frames with F0 in the kHz are not launched
-void ct_set_f0_bound(wc_cheaptrick *c, double f0_bound);
-void d4c_set_f0_bound(wc_d4c *d, double f0_bound);
 
 int d4c_enqueue(wc_d4c *d, hipStream_t s, int n_utt, const double *d_x, const int *x_length, const double *d_tpos,
 				const double *d_f0, const int *f0_length, int fft_size, double *d_ap, const uint64_t *rng_pos,
 				const unsigned long long *d_start);
 const unsigned long long *d4c_end_positions(const wc_d4c *d);
-uint64_t d4c_draw_bound(const wc_d4c *d, int f0_length);
 
 int syn_prepare(wc_synthesis *sy, hipStream_t s, int n_utt, const double *d_f0, const int *f0_length, const int *out_length,
 				double *d_out, const uint64_t *rng_pos, bool full);

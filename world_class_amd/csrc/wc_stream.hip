@@ -159,6 +159,29 @@ static int common_parity(std::vector<int> &parity, const std::vector<int> &act, 
 	return parity[act[0]];
 }
 
+// A stage on the frames a push committed, its noise positions carried per stream in `carried`: one batched call on one draw table
+// where the positions of the streams that committed frames allow it (DrawRange::one_table), else one call per such stream.
+// stage(n, a, pos): the stage's device call on the n active streams from the a-th on (their windows and frames lie packed in that order).
+template <class Stage>
+static int stage_on_committed(const std::vector<int> &count, std::vector<uint64_t> &carried, const std::vector<int> &act, Stage stage) {
+	const int na = (int)act.size();
+	std::vector<uint64_t> pos(na);
+	DrawRange starts;
+	for (int a = 0; a < na; ++a) {
+		pos[a] = carried[act[a]];
+		if (count[a] > 0) starts.add_start(pos[a]);
+	}
+	int rc;
+	if (starts.one_table()) {
+		if ((rc = stage(na, 0, pos.data()))) return rc;
+	} else {
+		for (int a = 0; a < na; ++a)
+			if (count[a] > 0 && (rc = stage(1, a, &pos[a]))) return rc;
+	}
+	for (int a = 0; a < na; ++a) carried[act[a]] = pos[a];
+	return WC_OK;
+}
+
 static int stream_widen(wc_stream *s, const void *d_chunk, int chunk_format, const int *n_new);
 
 extern "C" {
@@ -488,51 +511,19 @@ static int stream_push(wc_stream *s, const double *d_chunk, const int *n_new, co
 					   s->win_f0.as<double>(), s->frame_period, d_tpos, s->tpos_rel.as<double>(), d_f0);
 	WC_HIP(hipGetLastError());
 	// ---- CheapTrick on the committed frames, noise positions carried per stream ----
-	std::vector<uint64_t> pos(na);
-	uint64_t lo = ~0ull, hi = 0;
-	for (int a = 0; a < na; ++a) {
-		pos[a] = s->rng_pos[act[a]];
-		if (count[a] > 0) { lo = std::min(lo, pos[a]); hi = std::max(hi, pos[a]); }
-	}
 	const int bins = s->fft_size / 2 + 1;
-	if (hi - lo <= (1ull << 28)) {
-		if ((rc = wc_cheaptrick_compute_device(s->ct, na, s->batch.as<double>(), win_len.data(), s->tpos_rel.as<double>(), d_f0, count.data(),
-											   d_sp, pos.data())))
-			return rc;
-	} else {
-		// streams whose noise positions lie further apart than one draw table covers (one of them was reset hours after the
-		// others started): one call per stream, each with its own stretch of the table
-		for (int a = 0; a < na; ++a) {
-			if (count[a] == 0) continue;
-			if ((rc = wc_cheaptrick_compute_device(s->ct, 1, s->batch.as<double>() + desc[a].batch_off, &win_len[a],
-												   s->tpos_rel.as<double>() + desc[a].out_off, d_f0 + desc[a].out_off, &count[a],
-												   d_sp + desc[a].out_off * bins, &pos[a])))
-				return rc;
-		}
-	}
-	for (int a = 0; a < na; ++a) s->rng_pos[act[a]] = pos[a];
-	if (s->d4c) {
-		// ---- D4C on the same committed frames, window batch and whole-ms relative times, with its own noise positions ----
-		std::vector<uint64_t> pos4(na);
-		uint64_t lo4 = ~0ull, hi4 = 0;
-		for (int a = 0; a < na; ++a) {
-			pos4[a] = s->d4c_pos[act[a]];
-			if (count[a] > 0) { lo4 = std::min(lo4, pos4[a]); hi4 = std::max(hi4, pos4[a]); }
-		}
-		if (hi4 - lo4 <= (1ull << 28)) {
-			if ((rc = wc_d4c_compute_device(s->d4c, na, s->batch.as<double>(), win_len.data(), s->tpos_rel.as<double>(), d_f0, count.data(),
-											s->fft_size, d_ap, pos4.data())))
-				return rc;
-		} else {
-			for (int a = 0; a < na; ++a) {  // positions further apart than one draw table: one call per stream
-				if (count[a] == 0) continue;
-				if ((rc = wc_d4c_compute_device(s->d4c, 1, s->batch.as<double>() + desc[a].batch_off, &win_len[a], s->tpos_rel.as<double>() + desc[a].out_off,
-												d_f0 + desc[a].out_off, &count[a], s->fft_size, d_ap + desc[a].out_off * bins, &pos4[a])))
-					return rc;
-			}
-		}
-		for (int a = 0; a < na; ++a) s->d4c_pos[act[a]] = pos4[a];
-	}
+	const double *batch = s->batch.as<double>(), *tpos_rel = s->tpos_rel.as<double>();
+	if ((rc = stage_on_committed(count, s->rng_pos, act, [&](int n, int a, uint64_t *pos) {
+			const long long xo = desc[a].batch_off, fo = desc[a].out_off;
+			return wc_cheaptrick_compute_device(s->ct, n, batch + xo, &win_len[a], tpos_rel + fo, d_f0 + fo, &count[a], d_sp + fo * bins, pos);
+		})))
+		return rc;
+	// ---- D4C on the same committed frames, window batch and whole-ms relative times, with its own noise positions ----
+	if (s->d4c && (rc = stage_on_committed(count, s->d4c_pos, act, [&](int n, int a, uint64_t *pos) {
+			const long long xo = desc[a].batch_off, fo = desc[a].out_off;
+			return wc_d4c_compute_device(s->d4c, n, batch + xo, &win_len[a], tpos_rel + fo, d_f0 + fo, &count[a], s->fft_size, d_ap + fo * bins, pos);
+		})))
+		return rc;
 	guard.keep = true;
 	return WC_OK;
 }

@@ -979,13 +979,9 @@ int ss_enqueue_responses(wc_synth_stream *s, hipStream_t hs, SsCore &c, double *
 			for (auto &d : ol_expand) { d.dst_off = d.src_off / s->ccap * s->wsz; d.cut = d.lo; }
 		}
 		// the noise draws of stream a's final pulses: [start, start + (E - first_index) + 1)
-		auto draws_end = [&](int a) { return c.start[a] + (uint64_t)(c.E[c.act[a]] - c.first[a]) + 1; };
-		uint64_t lo = ~0ull, hi = 0;
-		for (int a = 0; a < na; ++a) {
-			if (c.n_syn[a] == 0) continue;
-			lo = std::min<uint64_t>(lo, c.start[a]);
-			hi = std::max<uint64_t>(hi, draws_end(a));
-		}
+		auto n_draws = [&](int a) -> uint64_t { return c.n_syn[a] == 0 ? 0 : (uint64_t)(c.E[c.act[a]] - c.first[a]) + 1; };
+		DrawRange draws;
+		for (int a = 0; a < na; ++a) draws.add(c.start[a], n_draws(a));
 		if (atomic) {
 			// expand: carried sums -> work rows (everything "carried", nothing committed)
 			if ((rc = s->aux.reserve(sizeof(OlDesc) * na))) return rc;
@@ -993,19 +989,18 @@ int ss_enqueue_responses(wc_synth_stream *s, hipStream_t hs, SsCore &c, double *
 			overlap(nullptr, carry_old, s->work.as<double>(), s->aux.as<OlDesc>());
 			WC_HIP(hipStreamSynchronize(hs));  // (ol_expand is a host vector)
 		}
-		if (hi - lo <= (1ull << 28)) {
-			if ((rc = s->dev->ensure_rng(lo, hi))) return rc;
+		if (draws.one_table()) {
+			if ((rc = s->dev->ensure_rng(draws.lo, draws.hi))) return rc;
 			sa.rng_table = s->dev->rng_table.as<uint32_t>(); sa.rng_base = s->dev->rng_base;
 			sa.pulse_utt = pu.as<int>();
 			sa.total_pulses = total_p;
 			if (split && (rc = syn_launch_class_lists(sa, s->cls.as<int>(), nullptr, hs))) return rc;
 			if ((rc = syn_launch_responses(N, sa, hs))) return rc;
 		} else {
-			// streams whose noise positions lie further apart than one draw table covers: one launch per stream, each with its own
-			// stretch of the table
+			// one launch per stream, each with its own stretch of the table
 			for (int a = 0; a < na; ++a) {
 				if (c.n_syn[a] == 0) continue;
-				if ((rc = s->dev->ensure_rng(c.start[a], draws_end(a)))) return rc;
+				if ((rc = s->dev->ensure_rng(c.start[a], c.start[a] + n_draws(a)))) return rc;
 				SynArgs one = sa;
 				one.utts = dm.utt + a; one.n_utt = 1; one.pulse_prefix = dm.pairs + 2 * a; one.cap_off = dm.capoff + a; one.first_index = dm.first + a;
 				one.rng_table = s->dev->rng_table.as<uint32_t>(); one.rng_base = s->dev->rng_base;

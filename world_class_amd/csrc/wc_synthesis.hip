@@ -13,6 +13,8 @@
 //                        atomics (reference :118-139)
 // The sum order of the overlap-add (FP64 atomics) differs from the reference's sequential loop;
 // the phase accumulation is exact.
+// The descriptors, the batch layout and the range of noise draws a call asks the table for are the stages' shared ones
+// (wc_stage_plan.hpp), the options are read through wc_options.hpp; the meta block and its upload are this file's own.
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -23,6 +25,7 @@
 #include "wc_frames.hpp"
 #include "wc_wavefft.hpp"
 #include "wc_hostcopy.hpp"
+#include "wc_options.hpp"
 #include "wc_synthesis.hpp"
 #include "wc_stages.hpp"
 
@@ -2074,6 +2077,19 @@ struct wc_synthesis {
 	int n_utt = 0, max_out = 0;
 };
 
+// the development options, read once when the handle is created
+static void syn_read_options(wc_synthesis *s) {
+	s->serial_timebase = opt_is("WC_SYN_TIMEBASE", "serial");
+	s->phase_single = opt_is("WC_SYN_PHASE", "single");
+	s->pulses_by_utterance = opt_is("WC_SYN_PULSES", "utterance");
+	s->wave = !opt_is("WC_SYN_IMPL", "block");
+	s->wave_atomic = opt_is("WC_SYN_OLA", "atomic");
+	s->split = !opt_off("WC_SYN_SPLIT");
+	size_t free_b = 0, total_b = 0;
+	if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) total_b = (size_t)64 << 30;
+	s->rows_budget = opt_set("WC_SYN_ROWS_BUDGET_MB") ? (size_t)opt_int("WC_SYN_ROWS_BUDGET_MB", 0) << 20 : total_b / 8;
+}
+
 // threads of a workgroup-per-pulse block:
 // eight samples per thread up to N = 2048 (at N = 1024 / 512 a 256-thread block idles half / three quarters of its threads in
 // every FFT pass: 3.53 -> 3.35 ms per 64 x 10 s at 16 kHz, 2.08 -> 1.53 ms at 8 kHz); 512 threads per 2048-point pulse measured
@@ -2154,20 +2170,14 @@ __global__ void syn_prefix_kernel(int n_utt, const int *__restrict__ count, cons
 int syn_prepare(wc_synthesis *sy, hipStream_t s, int n_utt, const double *d_f0, const int *f0_length, const int *out_length,
 				double *d_out, const uint64_t *rng_pos, bool full) {
 	Device *dev = sy->dev;
-	std::vector<UttDesc> utts(n_utt);
-	long long fo = 0, yo = 0;
 	int max_out = 0;
 	for (int u = 0; u < n_utt; ++u) {
 		if (f0_length[u] < 2) return fail(WC_ERR_INVALID, "synthesis: f0_length must be at least 2 (reference src/synthesis.cpp:241-242)");
 		if (out_length[u] < 0) return fail(WC_ERR_INVALID, "synthesis: negative out_length");
-		UttDesc &t = utts[u];
-		t.x_off = 0; t.f_off = fo; t.y_off = yo; t.x_len = 0; t.f_len = f0_length[u]; t.y_len = out_length[u]; t.f_base = 0;
-		t.rng_pos = rng_pos ? rng_pos[u] : 0ull;
-		fo += f0_length[u];
-		yo += out_length[u];
 		max_out = std::max(max_out, out_length[u]);
 	}
-	const long long total_out = yo;
+	std::vector<UttDesc> utts(n_utt);
+	const long long total_out = batch_layout(n_utt, nullptr, f0_length, out_length, rng_pos, utts.data()).y;
 	sy->total_out = total_out;
 	sy->n_utt = n_utt;
 	sy->max_out = max_out;
@@ -2400,14 +2410,9 @@ static int syn_run_device(wc_synthesis *sy, int n_utt, const double *d_f0, const
 	Device *dev = sy->dev;
 	hipStream_t s = dev->active();
 	int rc;
-	uint64_t lo = ~0ull, hi = 0;
-	for (int u = 0; u < n_utt; ++u) {
-		uint64_t p0 = rng_pos ? rng_pos[u] : 0ull;
-		lo = p0 < lo ? p0 : lo;
-		uint64_t e = p0 + (uint64_t)(out_length[u] > 0 ? out_length[u] : 0);
-		hi = e > hi ? e : hi;
-	}
-	if ((rc = dev->ensure_rng(lo, hi))) return rc;
+	DrawRange draws;
+	for (int u = 0; u < n_utt; ++u) draws.add(rng_pos ? rng_pos[u] : 0ull, synthesis_draws(out_length[u]));
+	if (!draws.empty() && (rc = dev->ensure_rng(draws.lo, draws.hi))) return rc;
 	// A large batch runs as two halves with a twin handle on a second stream (round 4): the second half's time base -- one
 	// wavefront or workgroup per utterance, ~1 ms of latency whatever the batch -- runs beside the first half's pulses instead of
 	// in front of everything (BASELINE config 4, 128 utterances: 10.4 -> 9.7 ms).  WC_SYN_HALVES=0: one piece.
@@ -2497,24 +2502,7 @@ wc_synthesis *wc_synthesis_create(int fs, int fft_size, double frame_period_ms) 
 	s->fs = fs;
 	s->fft_size = fft_size;
 	s->frame_period = frame_period_ms / 1000.;  // reference :31
-	{
-		const char *tb = getenv("WC_SYN_TIMEBASE");
-		s->serial_timebase = tb && std::string(tb) == "serial";
-		const char *ph = getenv("WC_SYN_PHASE");
-		s->phase_single = ph && std::string(ph) == "single";
-		const char *pu = getenv("WC_SYN_PULSES");
-		s->pulses_by_utterance = pu && std::string(pu) == "utterance";
-		const char *impl = getenv("WC_SYN_IMPL");
-		s->wave = !(impl && std::string(impl) == "block");
-		const char *ola = getenv("WC_SYN_OLA");
-		s->wave_atomic = ola && std::string(ola) == "atomic";
-		const char *sp = getenv("WC_SYN_SPLIT");
-		s->split = !(sp && sp[0] == '0');
-		size_t free_b = 0, total_b = 0;
-		if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) total_b = (size_t)64 << 30;
-		s->rows_budget = total_b / 8;
-		if (const char *mb = getenv("WC_SYN_ROWS_BUDGET_MB")) s->rows_budget = (size_t)atoll(mb) << 20;
-	}
+	syn_read_options(s);
 	s->dev = dev;
 	// getDCRemover, reference :290-303
 	std::vector<double> d(fft_size);
