@@ -246,13 +246,19 @@ def _rng_arg(rng_pos, n):
     return arr, arr
 
 
+from ._binding import _Handle  # noqa: E402  (below what _binding takes from this module: lib, _check, _handle, _ints, DeviceArray)
+
+
 # ---- stage classes ----------------------------------------------------------------------------
-class CheapTrick:
+class CheapTrick(_Handle):
     """reference include/cheaptrick.hpp:14-38 (CheapTrickOption defaults: q1 -0.15, f0_floor 71, fft_size 0=auto)"""
+
+    _lib = staticmethod(lib)
+    _sym = "wc_cheaptrick"
 
     def __init__(self, fs, q1=-0.15, f0_floor=71.0, fft_size=0):
         self.fs = fs
-        self._h = _handle(lib().wc_cheaptrick_create(fs, q1, f0_floor, fft_size))
+        self._create(fs, q1, f0_floor, fft_size)
         self.fft_size = lib().wc_cheaptrick_get_fft_size(self._h)
         self.bins = self.fft_size // 2 + 1
 
@@ -282,14 +288,6 @@ class CheapTrick:
                                                  _ints([len(v) for v in fs_]), tabs, arg))
         return (out, list(arr)) if rng_pos is not None else out
 
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                lib().wc_cheaptrick_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
-
 
 def _check_batch_shapes(who, xs, ts, fs_):
     """the per-utterance lists of a host batch call must agree: the C side strides by the lengths it is given"""
@@ -300,12 +298,14 @@ def _check_batch_shapes(who, xs, ts, fs_):
             raise ValueError(f"{who}: utterance {u}: x, temporal positions and f0 must be vectors, the last two of one length")
 
 
-class D4C:
+class D4C(_Handle):
     """reference include/d4c.hpp:16-36 (D4COption default threshold 0.85)"""
+    _lib = staticmethod(lib)
+    _sym = "wc_d4c"
 
     def __init__(self, fs, threshold=0.85):
         self.fs = fs
-        self._h = _handle(lib().wc_d4c_create(fs, threshold))
+        self._create(fs, threshold)
 
     def compute(self, x, temporal_positions, f0, fft_size, out=None):
         x, t, f = _c(x), _c(temporal_positions), _c(f0)
@@ -331,14 +331,6 @@ class D4C:
         _check(lib().wc_d4c_compute_batch(self._h, len(xs), _ptr_array(xs), _ints([len(v) for v in xs]), _ptr_array(ts), _ptr_array(fs_),
                                           _ints([len(v) for v in fs_]), fft_size, tabs, arg))
         return (out, list(arr)) if rng_pos is not None else out
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                lib().wc_d4c_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
 
 
 from ._synthesis import Synthesis  # noqa: E402,F401

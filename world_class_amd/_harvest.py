@@ -3,19 +3,20 @@ import ctypes as C
 
 import numpy as np
 
-from . import _c, _check, _handle, _ints, _p, _ptr, _ptr_array, get_samples, lib
+from . import _c, _check, _Handle, _ints, _p, _ptr, _ptr_array, get_samples, lib
 
 
-class Harvest:
+class Harvest(_Handle):
     """HarvestOption defaults of reference src/harvest.cpp:52-56: f0_floor 71, f0_ceil 800, frame_period 5,
     target_fs 8000, channels_in_octave 40, use_cos_table False (True: the reference's tabulated refinement window)."""
+    _lib = staticmethod(lib)
+    _sym = "wc_harvest"
 
     def __init__(self, fs, f0_floor=71.0, f0_ceil=800.0, frame_period=5.0, target_fs=8000.0,
                  channels_in_octave=40.0, use_cos_table=False):
         self.fs, self.frame_period = fs, frame_period
         self._last_lengths = []  # sample counts of the most recent call's utterances (debug_tail)
-        self._h = _handle(lib().wc_harvest_create(fs, f0_floor, f0_ceil, frame_period, target_fs,
-                                                  channels_in_octave, int(use_cos_table)))
+        self._create(fs, f0_floor, f0_ceil, frame_period, target_fs, channels_in_octave, int(use_cos_table))
 
     def get_samples(self, x_length):
         return get_samples(self.fs, x_length, self.frame_period)
@@ -92,11 +93,3 @@ class Harvest:
         _check(fn(self._h, cand.ctypes.data, score.ctypes.data, tpos.ctypes.data, f0.ctypes.data))
         at = np.concatenate([[0], np.cumsum(fl)])
         return [(tpos[a:b].copy(), f0[a:b].copy()) for a, b in zip(at[:-1], at[1:])]
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                lib().wc_harvest_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass

@@ -2,15 +2,17 @@
 Synthesis for a packed batch, stages overlapped on HIP streams, noise-stream positions chained on the device."""
 import numpy as np
 
-from . import (DeviceArray, _c, _check, _handle, _ints, _ptr, _rng_arg, get_samples, lib, synthesis_out_length)
+from . import (DeviceArray, _c, _check, _Handle, _ints, _ptr, _rng_arg, get_samples, lib, synthesis_out_length)
 
 
-class Pipeline:
+class Pipeline(_Handle):
+    _lib = staticmethod(lib)
+    _sym = "wc_pipeline"
+
     def __init__(self, fs, frame_period=5.0, harvest_f0_floor=71.0, harvest_f0_ceil=800.0, q1=-0.15,
                  cheaptrick_f0_floor=71.0, fft_size=0, d4c_threshold=0.85):
         self.fs, self.frame_period = fs, frame_period
-        self._h = _handle(lib().wc_pipeline_create(fs, frame_period, harvest_f0_floor, harvest_f0_ceil, q1,
-                                                   cheaptrick_f0_floor, fft_size, d4c_threshold))
+        self._create(fs, frame_period, harvest_f0_floor, harvest_f0_ceil, q1, cheaptrick_f0_floor, fft_size, d4c_threshold)
         self.fft_size = lib().wc_pipeline_get_fft_size(self._h)
         self.bins = self.fft_size // 2 + 1
 
@@ -168,11 +170,3 @@ class Pipeline:
                                                       tabs["csp"], number_of_dimensions, tabs["cap"], tabs["y"], 1 if y_pcm16 else 0, arg))
         res = [{k: outs[k][u] for k in outs} for u in range(n)]
         return (res, list(arr)) if rng_pos is not None else res
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                lib().wc_pipeline_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass

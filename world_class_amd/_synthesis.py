@@ -3,17 +3,19 @@ import ctypes as C
 
 import numpy as np
 
-from . import (_c, _check, _handle, _ints, _opt, _p, _ptr, _ptr_array, _rng_arg, _row_tables, _rows, lib,
+from . import (_c, _check, _Handle, _ints, _opt, _p, _ptr, _ptr_array, _rng_arg, _row_tables, _rows, lib,
                synthesis_out_length)
 
 
-class Synthesis:
+class Synthesis(_Handle):
     """Synthesis(fs, fft_size, frame_period_ms); compute(f0, spectrogram, aperiodicity, out_length)"""
+    _lib = staticmethod(lib)
+    _sym = "wc_synthesis"
 
     def __init__(self, fs, fft_size, frame_period=5.0):
         self.fs, self.fft_size, self.frame_period = fs, fft_size, frame_period
         self.bins = fft_size // 2 + 1
-        self._h = _handle(lib().wc_synthesis_create(fs, fft_size, frame_period))
+        self._create(fs, fft_size, frame_period)
 
     def out_length(self, f0_length):
         return synthesis_out_length(f0_length, self.frame_period, self.fs)  # reference test/test.cpp:362-363
@@ -144,11 +146,3 @@ class Synthesis:
                                                        _ptr_array([a[1] for a in args]), nd, _ptr_array([a[2] for a in args]),
                                                        _ints(out_lengths), _ptr_array(ys), 1 if y_pcm16 else 0, arg))
         return (ys, list(arr)) if rng_pos is not None else ys
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                lib().wc_synthesis_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass

@@ -3,7 +3,8 @@ import ctypes as C
 
 import numpy as np
 
-from . import _check, _opt, _ptr, lib
+from . import _check, _opt, _ptr, _rows
+from ._binding import _binder
 
 _dp = C.POINTER(C.c_double)
 _rows_t = C.POINTER(_dp)
@@ -24,24 +25,7 @@ CODEC_SIGNATURES = {
     "wc_code_features_device": (C.c_int, [C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
-_bound = False
-
-
-def _L():
-    global _bound
-    L = lib()
-    if not _bound:
-        for name, (res, args) in CODEC_SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.restype = res
-            fn.argtypes = args
-        _bound = True
-    return L
-
-
-def _rows(mat):
-    from . import _rows as rows  # (a table of row addresses built by numpy, see world_class_amd/__init__.py)
-    return rows(mat)
+_L = _binder(CODEC_SIGNATURES)
 
 
 def number_of_aperiodicities(fs):

@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import DeviceArray, _check, _ints, _opt  # noqa: F401  (_ints: for raw calls through _L(), as the tests make them)
-from .resample import _binder
+from ._binding import _binder
 
 _ip = C.POINTER(C.c_int)
 _vp = C.c_void_p

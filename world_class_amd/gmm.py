@@ -8,7 +8,7 @@ import numpy as np
 
 from . import DeviceArray, WorldClassError, _check, _handle, _opt, last_error  # noqa: F401
 from .features import FORMATS, _up
-from .resample import _binder
+from ._binding import _binder, _Handle
 
 _vp = C.c_void_p
 _dp = C.POINTER(C.c_double)
@@ -44,9 +44,11 @@ def joint_from_blocks(mux, muy, sxx, syx, syy):
     return mean, cov
 
 
-class Gmm:
+class Gmm(_Handle):
     """A joint-density mixture prepared for conversion: the handle lives on the device current at construction and is read-only, so
     several host threads may convert with it on their own streams."""
+    _lib = staticmethod(_L)
+    _sym = "wc_gmm"
 
     def __init__(self, weight, mean, cov, dx):
         w = np.ascontiguousarray(weight, dtype=np.float64).ravel()
@@ -57,7 +59,7 @@ class Gmm:
         cv = np.ascontiguousarray(cov, dtype=np.float64)
         if cv.size != self.n_mix * D * D:
             raise ValueError("cov holds n_mix * (dx + dy) * (dx + dy) values")
-        self._h = _handle(_L().wc_gmm_create(self.n_mix, self.dx, self.dy, _host(w), _host(m), _host(cv)))
+        self._create(self.n_mix, self.dx, self.dy, _host(w), _host(m), _host(cv))
 
     def convert(self, n_frames, d_rows_in, ld_in, d_mean, d_var, ld_out, col_in=0, col_out=0, d_best=None, d_loglik=None, in_format="f64",
                 out_format="f64"):
@@ -93,14 +95,3 @@ class Gmm:
         B, cvar = np.empty((self.n_mix, self.dy, self.dx)), np.empty((self.n_mix, self.dy))
         _check(_L().wc_gmm_prepared_host(self._h, _host(c), _host(W), _host(B), _host(cvar)))
         return c, W, B, cvar
-
-    def close(self):
-        if getattr(self, "_h", None):
-            _L().wc_gmm_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

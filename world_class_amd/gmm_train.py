@@ -8,7 +8,7 @@ import numpy as np
 
 from . import DeviceArray, WorldClassError, _check, _handle, _opt, last_error  # noqa: F401
 from .features import FORMATS, _up
-from .resample import _binder
+from ._binding import _binder, _Handle
 
 _vp = C.c_void_p
 _dp = C.POINTER(C.c_double)
@@ -56,14 +56,16 @@ def initial_model(rows, n_mix, seed=0):
     return np.full(n_mix, 1.0 / n_mix), rows[picks].copy(), cov
 
 
-class GmmTrainer:
+class GmmTrainer(_Handle):
     """A trainer handle: a model, and the statistics accumulated under it since the last update or reset.  It lives on the device
     current at construction and belongs to one host thread at a time."""
+    _lib = staticmethod(_L)
+    _sym = "wc_gmm_trainer"
 
     def __init__(self, n_mix, dx, dy):
         self.n_mix, self.dx, self.dy = int(n_mix), int(dx), int(dy)
         self.D = self.dx + self.dy
-        self._h = _handle(_L().wc_gmm_trainer_create(self.n_mix, self.dx, self.dy))
+        self._create(self.n_mix, self.dx, self.dy)
 
     def set_model(self, weight, mean, cov):
         """the arrays gmm.Gmm takes: weight [n_mix], mean [n_mix, D], cov [n_mix, D, D] (the lower triangle is read)"""
@@ -143,14 +145,3 @@ class GmmTrainer:
         from .gmm import Gmm
         w, m, cv = self.model()
         return Gmm(w, m, cv, self.dx)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            _L().wc_gmm_trainer_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -8,7 +8,7 @@ import numpy as np
 
 from . import DeviceArray, _check, _ints, _opt  # noqa: F401  (_ints: for raw calls through _L(), as the tests make them)
 from .features import FORMATS, _split, _up, width
-from .resample import _binder
+from ._binding import _binder
 
 _ip = C.POINTER(C.c_int)
 _vp = C.c_void_p

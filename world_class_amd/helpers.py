@@ -4,7 +4,8 @@ import ctypes as C
 
 import numpy as np
 
-from . import _c, lib
+from . import _c
+from ._binding import _binder
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int)
@@ -25,19 +26,7 @@ HELPER_SIGNATURES = {
     "NuttallWindow": (None, [C.c_int, _dp]),
 }
 
-_bound = False
-
-
-def _L():
-    global _bound
-    L = lib()
-    if not _bound:
-        for name, (res, args) in HELPER_SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.restype = res
-            fn.argtypes = args
-        _bound = True
-    return L
+_L = _binder(HELPER_SIGNATURES)
 
 
 def _p(a):

@@ -4,7 +4,8 @@ import ctypes as C
 
 import numpy as np
 
-from . import WorldClassError, _c, _check, _opt, _ptr, lib
+from . import WorldClassError, _c, _check, _opt, _ptr, _rows, lib
+from ._binding import _binder
 
 _dp = C.POINTER(C.c_double)
 _i16p = C.POINTER(C.c_int16)
@@ -39,28 +40,11 @@ IO_SIGNATURES = {
 
 ALIGN_OPEN_BEGIN, ALIGN_OPEN_END = 1, 2  # WC_ALIGN_OPEN_BEGIN, WC_ALIGN_OPEN_END
 
-_bound = False
-
-
-def _io():
-    global _bound
-    L = lib()
-    if not _bound:
-        for name, (res, args) in IO_SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.restype = res
-            fn.argtypes = args
-        _bound = True
-    return L
+_io = _binder(IO_SIGNATURES)
 
 
 def _path(p):
     return str(p).encode()
-
-
-def _rows(mat):
-    from . import _rows as rows  # (a table of row addresses built by numpy, see world_class_amd/__init__.py)
-    return rows(mat)
 
 
 def wavwrite(x, fs, filename, nbit=16):

@@ -5,7 +5,7 @@ import ctypes as C
 
 from . import DeviceArray, _check, _ints, _opt  # noqa: F401  (_ints: for raw calls through _L(), as the tests make them)
 from .features import FORMATS
-from .resample import _binder, _lag_emitted, _LagStream
+from ._binding import _binder, _lag_emitted, _LagStream
 
 _ip = C.POINTER(C.c_int)
 _vp = C.c_void_p

@@ -3,7 +3,9 @@ import ctypes as C
 
 import numpy as np
 
-from . import DeviceArray, _check, _handle, _ints, _opt, _ptr, lib
+from . import DeviceArray, _check, _ints, _opt
+# (the definitions live in _binding; the names stay importable from here, where other modules, tests and tools take them)
+from ._binding import IN_FORMATS, OUT_FORMATS, _binder, _count, _Handle, _lag_emitted, _LagStream, pack_rows, split_rows, uploaded  # noqa: F401
 
 _ip = C.POINTER(C.c_int)
 _vp = C.c_void_p
@@ -28,34 +30,8 @@ RESAMPLE_SIGNATURES = {
 }
 
 WAVE = 64  # outputs of one phase that a wavefront of the phase mapping takes
-IN_FORMATS = {"f64": (0, np.float64), "i16": (1, np.int16), "f32": (2, np.float32)}
-OUT_FORMATS = {"f64": (0, np.float64), "i16": (1, np.int16)}
-
-
-def _binder(signatures):
-    """the library with a module's signatures bound on first use"""
-    done = []
-
-    def get():
-        L = lib()
-        if not done:
-            for name, (res, args) in signatures.items():
-                fn = getattr(L, name)
-                fn.restype = res
-                fn.argtypes = args
-            done.append(True)
-        return L
-
-    return get
-
 
 _L = _binder(RESAMPLE_SIGNATURES)
-
-
-def _count(n):
-    if n < 0:
-        _check(int(n))
-    return int(n)
 
 
 def plan(fs_in, fs_out, zeros=0, rolloff=0.0, beta=0.0):
@@ -101,74 +77,10 @@ def _in_format(arrays):
     return "f64"
 
 
-class _Handle:
-    """a handle of either converter: _lib is its module's binder, _sym the prefix of its symbols, _kind what follows the prefix in
-    the names of its create and destroy"""
-    _lib = staticmethod(_L)
-    _sym = "wc_resample"
-    _kind = None
-    _h = None
-
-    def _fn(self, name):
-        return getattr(self._lib(), self._sym + name)
-
-    def _create(self, *args):
-        self._h = _handle(self._fn(self._kind + "_create")(*args))
-
-    def close(self):
-        if self._h:
-            self._fn(self._kind + "_destroy")(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class _LagStream(_Handle):
-    """what the two lagged row streams share (csrc/wc_lag_stream.hpp): MlpgStream and FeatureStream"""
-    _kind = "_stream"
-    n_streams = 0
-
-    @property
-    def max_frames_per_push(self):
-        return int(self._fn("_stream_max_frames_per_push")(self._h))
-
-    @property
-    def max_frames_per_flush(self):
-        return int(self._fn("_stream_max_frames_per_flush")(self._h))
-
-    def _counts(self, counts):
-        if len(counts) != self.n_streams:
-            raise ValueError("one entry per stream")
-        return _ints(counts), (C.c_int * self.n_streams)()
-
-    def rows_received(self, stream):
-        return int(self._fn("_stream_rows_received")(self._h, int(stream)))
-
-    def frames_emitted(self, stream):
-        return int(self._fn("_stream_frames_emitted")(self._h, int(stream)))
-
-    def get_lag(self, stream):
-        return int(self._fn("_stream_get_lag")(self._h, int(stream)))
-
-
-def _lag_emitted(binder, symbol, doc):
-    """a module's emitted(rows, lag), bound to its library symbol"""
-    def emitted(rows, lag):
-        n = int(getattr(binder(), symbol)(int(rows), int(lag)))
-        if n < 0:
-            raise ValueError("rows and lag must not be negative")
-        return n
-
-    emitted.__doc__ = doc
-    return emitted
-
-
 class _Batch(_Handle):
     """the batch handle of either converter: the packing of host arrays around its run_device"""
+    _lib = staticmethod(_L)
+    _sym = "wc_resample"
     _kind = "r"
 
     def _device(self, d_x, x_lengths, extra, d_y, in_format, out_format):
@@ -187,16 +99,14 @@ class _Batch(_Handle):
     @staticmethod
     def _run(fmt, xs, outs, out_format, run_device):
         """the packed signals up, run_device(d_x, d_y), the outputs of lengths outs down"""
-        d_x = DeviceArray.from_host(np.concatenate(xs), dtype=IN_FORMATS[fmt][1])
         d_y = DeviceArray(sum(outs), dtype=OUT_FORMATS[out_format][1])
         try:
-            run_device(d_x, d_y)
-            y = d_y.to_host()  # (the copy waits for the stream)
+            with uploaded(np.concatenate(xs), dtype=IN_FORMATS[fmt][1]) as (d_x,):
+                run_device(d_x, d_y)
+                y = d_y.to_host()  # (the copy waits for the stream)
         finally:
-            d_x.free()
             d_y.free()
-        cuts = np.cumsum(outs)[:-1]
-        return [part.copy() for part in np.split(y, cuts)]
+        return split_rows(y, outs)
 
 
 class Resampler(_Batch):
@@ -223,6 +133,8 @@ class Resampler(_Batch):
 
 class _Stream(_Handle):
     """the stream handle of either converter: everything but its create and what only one of them has"""
+    _lib = staticmethod(_L)
+    _sym = "wc_resample"
     _kind = "_stream"
 
     def _create(self, n_streams, max_samples, *plan):
@@ -260,20 +172,14 @@ class _Stream(_Handle):
             raise ValueError("one entry per stream")
         fmt = _in_format(chunks)
         idt, odt = IN_FORMATS[fmt][1], OUT_FORMATS[out_format][1]
-        parts = [np.zeros(0, dtype=idt) if c is None else np.ascontiguousarray(c, dtype=idt).ravel() for c in chunks]
-        counts = [len(p) for p in parts]
+        counts, flat = pack_rows([None if c is None else np.ravel(c) for c in chunks], 1, dtype=idt, placeholder=False)  # (nothing pushed: NULL)
         if out_format not in self._out:
             self._out[out_format] = DeviceArray(self.n_streams * self.max_out_per_push, dtype=odt)
         d_y = self._out[out_format]
-        d = DeviceArray.from_host(np.concatenate(parts), dtype=idt) if sum(counts) else None
-        try:
+        with uploaded(flat, dtype=idt) as (d,):
             got = self.push_device(counts, d, flush, d_y, fmt, out_format)
-            y = d_y.to_host()[:sum(got)] if sum(got) else np.zeros(0, dtype=odt)
-        finally:
-            if d is not None:
-                d.free()
-        cuts = np.cumsum(got)[:-1]
-        return [part.copy() for part in np.split(y, cuts)]
+            y = d_y.to_host() if sum(got) else np.zeros(0, dtype=odt)
+        return split_rows(y, got)
 
     def close(self):
         super().close()

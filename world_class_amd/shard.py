@@ -10,6 +10,9 @@ from typing import List, Sequence
 import torch
 import torch.distributed as dist
 
+from . import _check
+from ._binding import _binder
+
 # the C-ABI of include/world_class_shard.h (C / C++ hosts shard and gather through it; this module is the torch.distributed twin)
 SHARD_SIGNATURES = {
     "wc_shard_partition": (C.c_int, [C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_int)]),
@@ -17,18 +20,15 @@ SHARD_SIGNATURES = {
     "wc_gather_to_root_device": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_longlong), C.c_void_p]),
 }
 
+_L = _binder(SHARD_SIGNATURES)
+
 
 def partition_c(lengths: Sequence[int], world: int) -> List[List[int]]:
     """`partition` through the C-ABI (wc_shard_partition): the same deal, for hosts without Python"""
-    from . import _check, lib
-    L = lib()
-    for name, (res, args) in SHARD_SIGNATURES.items():
-        fn = getattr(L, name)
-        fn.restype, fn.argtypes = res, args
     n = len(lengths)
     arr = (C.c_int * max(n, 1))(*[int(v) for v in lengths])
     out = (C.c_int * max(n, 1))()
-    _check(L.wc_shard_partition(arr, n, world, out))
+    _check(_L().wc_shard_partition(arr, n, world, out))
     parts: List[List[int]] = [[] for _ in range(world)]
     for i in range(n):
         parts[out[i]].append(i)

@@ -5,7 +5,8 @@ import ctypes as C
 import numpy as np
 
 from . import _check, _ints  # noqa: F401  (_ints: for raw calls through _L(), as the tests make them)
-from .resample import IN_FORMATS, OUT_FORMATS, WAVE, _Batch, _binder, _count, _Stream  # noqa: F401  (the formats are the rational converter's)
+from ._binding import IN_FORMATS, OUT_FORMATS, _binder, _count  # noqa: F401  (the formats are the rational converter's too)
+from .resample import WAVE, _Batch, _Stream  # noqa: F401
 
 _ip = C.POINTER(C.c_int)
 _vp = C.c_void_p

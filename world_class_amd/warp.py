@@ -6,7 +6,8 @@ import ctypes as C
 import numpy as np
 
 from . import DeviceArray, _check, _ints, _opt  # noqa: F401  (_ints: for raw calls through _L(), as the tests make them)
-from .resample import IN_FORMATS, OUT_FORMATS, _Batch, _binder, _count
+from ._binding import IN_FORMATS, OUT_FORMATS, _binder, _count
+from .resample import _Batch
 from .vresample import _step, _u64
 
 _ip = C.POINTER(C.c_int)

@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import DeviceArray, _check, _ints, _opt  # noqa: F401  (_ints: for raw calls through _L(), as the tests make them)
-from .resample import IN_FORMATS, OUT_FORMATS, _binder, _count, _Handle
+from ._binding import IN_FORMATS, OUT_FORMATS, _binder, _count, _Handle
 from .vresample import _plan, _step
 
 _ip = C.POINTER(C.c_int)
