@@ -24,6 +24,7 @@
 #include "wc_internal.hpp"
 #include "wc_frames.hpp"
 #include "wc_wavefft.hpp"
+#include "wc_minphase.hpp"
 #include "wc_hostcopy.hpp"
 #include "wc_options.hpp"
 #include "wc_synthesis.hpp"
@@ -796,106 +797,6 @@ __global__ void syn_noise_size_kernel(const long long *__restrict__ cap_off, con
 	}
 }
 
-// MinimumPhaseAnalysis::compute (reference src/world_common.cpp:196-233) for the block.
-// ls[BPT]: log spectrum of this thread's bins k = tid + e T (k <= M).  On return A[0..M] holds the
-// minimum-phase spectrum (full complex, M+1 entries).  Ends with a __syncthreads().
-#ifndef WC_SYN_MINPHASE_REAL
-#define WC_SYN_MINPHASE_REAL 1
-#endif
-template <int N, int T>
-__device__ __forceinline__ void minimum_phase_lds(double2 *A, const double (&ls)[(N / 2 + T) / T],
-												  const double2 *__restrict__ tw, int tid) {
-	constexpr int M = N / 2;
-	constexpr int BPT = (M + T) / T;
-	double *Ar = reinterpret_cast<double *>(A);
-	WC_FRESH(tid);
-#pragma unroll
-	for (int e = 0; e < BPT; ++e) {
-		int k = tid + e * T;
-		if (k <= M) {
-			Ar[k] = ls[e];
-			if (k > 0 && k < M) Ar[N - k] = ls[e];  // mirroring (reference :199-200)
-		}
-	}
-	__syncthreads();
-	fft_lds<M, T, +1>(A, tw, tid);
-	r2c_post<M, T>(A, tw, tid);
-	WC_FRESH(tid);
-#if WC_SYN_MINPHASE_REAL
-	// cepstrum folding (reference :207-217): bins 1..M-1 doubled (and conjugated), upper half zeroed.  The cepstrum of a
-	// real even log spectrum is real -- the imaginary parts the reference carries along are its FFT's rounding noise,
-	// 1e-16 of the real parts -- so the second transform is taken as a real one too (an M-point complex FFT and the
-	// unpacking pass instead of an N-point complex FFT; SYN_MINPHASE_REAL=0 keeps the complex transform for comparison).
-	double cr[2 * BPT];  // this thread's real samples n = tid + e T, n < N
-#pragma unroll
-	for (int e = 0; e < 2 * BPT; ++e) {
-		int n = tid + e * T;
-		cr[e] = 0.0;
-		if (n == 0) cr[e] = A[0].x;
-		else if (n == M) cr[e] = A[0].y;
-		else if (n < M) cr[e] = A[n].x * 2.0;
-	}
-	__syncthreads();
-#pragma unroll
-	for (int e = 0; e < 2 * BPT; ++e) {
-		int n = tid + e * T;
-		if (n < N) Ar[n] = cr[e];
-	}
-	__syncthreads();
-	fft_lds<M, T, +1>(A, tw, tid);
-	r2c_post<M, T>(A, tw, tid);
-	WC_FRESH(tid);
-	double2 c[BPT];
-#pragma unroll
-	for (int e = 0; e < BPT; ++e) {
-		int k = tid + e * T;
-		if (k <= M) {
-			double2 m = (k == 0) ? make_double2(A[0].x, 0.0) : (k == M) ? make_double2(A[0].y, 0.0) : A[k];
-			double t = exp(m.x / N), sn, cs;
-			sincos(m.y / N, &sn, &cs);
-			c[e] = make_double2(t * cs, t * sn);
-		}
-	}
-#else
-	// cepstrum folding (reference :207-217): bins 1..M-1 doubled and conjugated, upper half zeroed
-	double2 c[BPT];
-#pragma unroll
-	for (int e = 0; e < BPT; ++e) {
-		int k = tid + e * T;
-		c[e] = make_double2(0.0, 0.0);
-		if (k == 0) c[e] = make_double2(A[0].x, 0.0);
-		else if (k == M) c[e] = make_double2(A[0].y, 0.0);
-		else if (k < M) c[e] = make_double2(A[k].x * 2.0, A[k].y * -2.0);
-	}
-	__syncthreads();
-#pragma unroll
-	for (int e = 0; e < BPT; ++e) {
-		int k = tid + e * T;
-		if (k <= M) A[k] = c[e];
-		if (k >= 1 && k < M) A[M + k] = make_double2(0.0, 0.0);
-	}
-	__syncthreads();
-	fft_lds<N, T, +1>(A, tw, tid);
-	WC_FRESH(tid);
-#pragma unroll
-	for (int e = 0; e < BPT; ++e) {
-		int k = tid + e * T;
-		if (k <= M) {
-			double2 m = A[k];
-			double t = exp(m.x / N), sn, cs;
-			sincos(m.y / N, &sn, &cs);
-			c[e] = make_double2(t * cs, t * sn);
-		}
-	}
-#endif
-	__syncthreads();
-#pragma unroll
-	for (int e = 0; e < BPT; ++e) {
-		int k = tid + e * T;
-		if (k <= M) A[k] = c[e];
-	}
-	__syncthreads();
-}
 
 __device__ __forceinline__ double safe_ap(double v) { return fmax(0.001, fmin(0.999999999999, v)); }
 
@@ -1111,65 +1012,6 @@ __global__ __launch_bounds__(T) void syn_pulse_kernel(SynArgs a) {
 // exchanges each and no workgroup barrier; lean log / exp (wf_log, wf_exp).  Only the first half of the periodic response
 // survives the reference's DC removal (:459-474: the shifted first half is overwritten with -dc * remover), so 16 values per
 // lane are all that is kept of it while the aperiodic response is formed.  LDS: 9.2 KB per pulse.
-//
-// MinimumPhaseAnalysis::compute (reference src/world_common.cpp:196-233): in: the log spectrum ls[4 g + q] of bin
-// j_g + 256 q and lsM of bin 1024 (lane 0); out: the minimum-phase spectrum (mr, mi) in the same layout, (mMr, 0) for bin 1024.
-// (the caller has put the log spectrum into L itself, value by value as it formed them: L[bin], bins 0 .. 1024)
-__device__ __forceinline__ void minimum_phase_wave(double (&mr)[16], double (&mi)[16], double &mMr,
-												   double *L, const double *T, const double2 *__restrict__ tw, int lane) {
-	constexpr int N = 2048, M = 1024;
-	WC_FRESH(lane);
-	int jg[4];
-#pragma unroll
-	for (int g = 0; g < 4; ++g) jg[g] = wf_bin(lane, g, 0);
-	// the mirrored log spectrum (reference :199-200) as the packed input of the first transform
-	wf_fence();
-#pragma unroll
-	for (int q = 0; q < 8; ++q) {
-		const double2 v = *reinterpret_cast<const double2 *>(&L[2 * lane + 128 * q]);
-		mr[q] = v.x;
-		mi[q] = v.y;
-	}
-#pragma unroll
-	for (int q = 8; q < 16; ++q) {
-		mr[q] = L[2048 - 2 * lane - 128 * q];
-		mi[q] = L[2047 - 2 * lane - 128 * q];
-	}
-	wf_fence();
-	wf_fft1024_dit<+1>(mr, mi, L, tw, lane);
-	double nyq;
-	wf_r2c_unpack_re(mr, mi, nyq, tw, lane);  // twice the (real) cepstrum
-	// folding (reference :207-217): bins 1 .. M-1 doubled, 0 and M kept, the upper half zero; the cepstrum of a real even log
-	// spectrum is real, so the second transform is a real one too (see minimum_phase_lds)
-#pragma unroll
-	for (int g = 0; g < 4; ++g)
-#pragma unroll
-		for (int q = 0; q < 4; ++q) L[jg[g] + 256 * q] = (g == 0 && q == 0 && lane == 0) ? 0.5 * mr[0] : mr[4 * g + q];
-	if (lane == 0) L[M] = 0.5 * nyq;
-	wf_fence();
-#pragma unroll
-	for (int q = 0; q < 8; ++q) {
-		const double2 v = *reinterpret_cast<const double2 *>(&L[2 * lane + 128 * q]);
-		mr[q] = v.x;
-		mi[q] = v.y;
-	}
-	mr[8] = lane == 0 ? L[M] : 0.0;
-	mi[8] = 0.0;
-#pragma unroll
-	for (int q = 9; q < 16; ++q) mr[q] = mi[q] = 0.0;
-	wf_fence();
-	wf_fft1024_dit<+1>(mr, mi, L, tw, lane);
-	wf_r2c_unpack(mr, mi, nyq, tw, lane);  // twice the spectrum of the folded cepstrum
-#pragma unroll
-	for (int s = 0; s < 16; ++s) {
-		const double t = wf_exp_l(mr[s] * (0.5 / N), T);
-		double sn, cs;
-		wf_sincos(mi[s] * (0.5 / N), sn, cs);
-		mr[s] = t * cs;
-		mi[s] = t * sn;
-	}
-	mMr = wf_exp_l(nyq * (0.5 / N), T);
-}
 
 #ifndef WC_SYN_WAVE_OCC
 #define WC_SYN_WAVE_OCC 2
@@ -1572,60 +1414,6 @@ void syn_pulse_wave_kernel(SynArgs a) {
 // wavefronts per SIMD.  A workgroup is FOUR such wavefronts, each on a pulse of its own with its own exchange buffer and parking
 // array; all they share is the table of the lean log / exp (2.5 KB a wavefront would otherwise copy for itself: with it the
 // sixteen wavefronts of a CU would not fit its LDS), loaded in front of the only barrier of the kernel.
-__device__ __forceinline__ void minimum_phase_wave8(double (&mr)[8], double (&mi)[8], double &mMr,
-													double *L, const double *T, const double2 *__restrict__ tw, int lane) {
-	constexpr int N = 1024, M = 512;
-	WC_FRESH(lane);
-	int jg[2];
-#pragma unroll
-	for (int g = 0; g < 2; ++g) jg[g] = wf8_bin(lane, g, 0);
-	// the mirrored log spectrum (reference :199-200) as the packed input of the first transform
-	wf_fence();
-#pragma unroll
-	for (int q = 0; q < 4; ++q) {
-		const double2 v = *reinterpret_cast<const double2 *>(&L[2 * lane + 128 * q]);
-		mr[q] = v.x;
-		mi[q] = v.y;
-	}
-#pragma unroll
-	for (int q = 4; q < 8; ++q) {
-		mr[q] = L[1024 - 2 * lane - 128 * q];
-		mi[q] = L[1023 - 2 * lane - 128 * q];
-	}
-	wf_fence();
-	wf8_fft512_dit<+1>(mr, mi, L, tw, lane);
-	double nyq;
-	wf8_r2c_unpack_re(mr, mi, nyq, tw, lane);  // twice the (real) cepstrum
-	// folding (reference :207-217): bins 1 .. M-1 doubled, 0 and M kept, the upper half zero (see minimum_phase_wave)
-#pragma unroll
-	for (int g = 0; g < 2; ++g)
-#pragma unroll
-		for (int q = 0; q < 4; ++q) L[jg[g] + 128 * q] = (g == 0 && q == 0 && lane == 0) ? 0.5 * mr[0] : mr[4 * g + q];
-	if (lane == 0) L[M] = 0.5 * nyq;
-	wf_fence();
-#pragma unroll
-	for (int q = 0; q < 4; ++q) {
-		const double2 v = *reinterpret_cast<const double2 *>(&L[2 * lane + 128 * q]);
-		mr[q] = v.x;
-		mi[q] = v.y;
-	}
-	mr[4] = lane == 0 ? L[M] : 0.0;
-	mi[4] = 0.0;
-#pragma unroll
-	for (int q = 5; q < 8; ++q) mr[q] = mi[q] = 0.0;
-	wf_fence();
-	wf8_fft512_dit<+1>(mr, mi, L, tw, lane);
-	wf8_r2c_unpack(mr, mi, nyq, tw, lane);  // twice the spectrum of the folded cepstrum
-#pragma unroll
-	for (int s = 0; s < 8; ++s) {
-		const double t = wf_exp_l(mr[s] * (0.5 / N), T);
-		double sn, cs;
-		wf_sincos(mi[s] * (0.5 / N), sn, cs);
-		mr[s] = t * cs;
-		mi[s] = t * sn;
-	}
-	mMr = wf_exp_l(nyq * (0.5 / N), T);
-}
 
 #ifndef WC_SYN_WAVE8_OCC
 #define WC_SYN_WAVE8_OCC 4
@@ -2693,7 +2481,8 @@ int wc_synthesis_compute(wc_synthesis *s, const double *f0, int f0_length, const
 
 }  // extern "C"
 
-// Development hook (undeclared, like the wc_debug_* of wc_testhooks.hip; it lives here because the analyses are defined here):
+// Development hook (undeclared, like the wc_debug_* of wc_testhooks.hip; it lives here, next to the pulse kernels whose block sizes it takes; the analyses
+// themselves are wc_minphase.hpp's):
 // `batch` log spectra of n / 2 + 1 doubles each in `ls`, their minimum-phase spectra, n / 2 + 1 complex values each, in `out`;
 // host pointers.  form 0: minimum_phase_lds<n, T> with the pulse kernel's block size, n = 512, 1024, 2048, 4096; form 1: the
 // one-wavefront forms, minimum_phase_wave8 for n = 1024 and minimum_phase_wave for n = 2048.
