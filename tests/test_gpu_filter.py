@@ -15,8 +15,9 @@ import filter_rule as fr
 
 pytestmark = pytest.mark.gpu
 
-# (fs, fft_size, frame_period_ms): 512 at 8 kHz; 1024 at 16 kHz / 5 ms and 24 kHz / 1 ms (43 rows over a sample); 2048 at 44.1 kHz / 5 ms
-# (a fractional hop) and 48 kHz; 4096 at 96 kHz
+# (fs, fft_size, frame_period_ms): 512 at 8 kHz; 1024 at 16 kHz / 5 ms and 24 kHz / 1 ms (hop 24: 43 rows would lie over a sample, but
+# batch() gives it 111 samples, six segments; tests/test_gpu_filter_long.py runs that depth and hop 1); 2048 at 44.1 kHz / 5 ms (a
+# fractional hop) and 48 kHz; 4096 at 96 kHz
 SETTINGS = [(8000, 512, 5.0), (16000, 1024, 5.0), (24000, 1024, 1.0), (44100, 2048, 5.0), (48000, 2048, 5.0), (96000, 4096, 5.0)]
 # the largest hop each size accepts and one step beyond it
 EDGES = [(8000, 512, 16.0, 16.125), (16000, 1024, 16.0, 16.0625), (48000, 2048, 512 / 48.0, 513 / 48.0), (96000, 4096, 1024 / 96.0, 1025 / 96.0)]
