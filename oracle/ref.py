@@ -253,13 +253,32 @@ def taps_available():
     return os.path.exists(os.path.join(_HERE, "_ref", "libworld_ref_taps.so"))
 
 
+_TAP_NAMES = ("y", "raw", "cand_refined", "score_refined", "cand", "score", "f0_base", "f0_fixed", "f0_1ms")
+
+
+def _taps_lib():
+    lib = C.CDLL(os.path.join(_HERE, "_ref", "libworld_ref_taps.so"))
+    lib.ref_harvest_taps.restype = C.c_int
+    lib.ref_harvest_taps.argtypes = [_dp, C.c_int, C.c_int, C.c_double, C.c_double, _ip] + [_dp] * len(_TAP_NAMES)
+    return lib
+
+
+def harvest_taps_into(x, fs, f0_floor, f0_ceil, **bufs):
+    """The same call writing into the caller's own float64 buffers, named as harvest_taps' keys (a tap that is not named is
+    not written): for a caller whose buffers outlive the call, such as shared memory read by a parent when the reference's
+    tail does not return.  Returns the frame count."""
+    assert set(bufs) <= set(_TAP_NAMES)
+    x = _c(x)
+    dims = np.zeros(4, dtype=np.int32)
+    return _taps_lib().ref_harvest_taps(_p(x), len(x), fs, f0_floor, f0_ceil, dims.ctypes.data_as(_ip),
+                                        *[_p(bufs[k]) if k in bufs else None for k in _TAP_NAMES])
+
+
 def harvest_taps(x, fs, f0_floor=71.0, f0_ceil=800.0):
     """Intermediates of the real reference's Harvest (oracle/ref_harvest_taps.cpp): y, raw [band][frame], candidates and
     scores after refinement and after removeUnreliableCandidates [frame][max_candidates], base / fixed / smoothed 1 ms
     contours.  Harvest draws no random numbers, so no fresh process is needed."""
-    lib = C.CDLL(os.path.join(_HERE, "_ref", "libworld_ref_taps.so"))
-    lib.ref_harvest_taps.restype = C.c_int
-    lib.ref_harvest_taps.argtypes = [_dp, C.c_int, C.c_int, C.c_double, C.c_double, _ip] + [_dp] * 9
+    lib = _taps_lib()
     x = _c(x)
     dims = np.zeros(4, dtype=np.int32)
     nul = [None] * 9
