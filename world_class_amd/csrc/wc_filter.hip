@@ -18,7 +18,10 @@
 //                    from 0.0 and writes every sample of y.  No atomics.
 //   filter_difference_kernel       the coded call's d = to - from (d[0] = 0.0 with skip_energy), in front of the codec's decoder.
 // Every load and store is bounded by the utterance's own n, f_length and S; the centres c_t are computed by one expression on the
-// host and on the device (the build contracts no product into an fma).
+// host and on the device (ff_centre in wc_filter_stream_plan.hpp; the build contracts no product into an fma).
+// The segment kernels and the difference kernel also serve the filter streams (wc_filter_stream.hip), through filter_segments_launch
+// and filter_difference_launch (wc_internal.hpp): a record's t0 is the number of its first segment, 0 for the batch, and its offsets
+// count from the sample a_t0 and the row t0.
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
@@ -28,6 +31,7 @@
 #include "../../include/world_class_filter.h"
 #include "wc_device.hpp"
 #include "wc_features_rows.hpp"
+#include "wc_filter_stream_plan.hpp"  // ff_centre, ff_segments
 #include "wc_internal.hpp"
 #include "wc_minphase.hpp"
 #include "wc_options.hpp"
@@ -36,27 +40,7 @@
 
 namespace wc {
 
-// c_t of THE rule
-__host__ __device__ __forceinline__ long long ff_centre(long long t, double fp_ms, int fs) {
-	return (long long)floor(((double)t * fp_ms) * (double)fs / 1000.0 + 0.5);
-}
-
-struct FfUtt {  // one per utterance, and one more behind the last whose seg_off is the batch's segment count
-	long long x_off, row_off, seg_off;
-	int n, f_len, S, pad;
-};
-
-struct FfArgs {
-	const double *x, *gain;
-	double *rows, *y;
-	const FfUtt *utts;
-	const double2 *tw;
-	long long total_seg;
-	double fp_ms;
-	int n_utt, fs, kind;
-};
-
-// where a segment stands: its utterance, its centres and its span
+// where a segment stands: its utterance, its number within the record, its centres and its span, counted from the record's a_t0
 struct FfPlace {
 	int u, t, Lt;
 	long long cm, c0, cp, a;
@@ -70,10 +54,13 @@ __device__ __forceinline__ FfPlace ff_place(const FfArgs &a, long long seg) {
 	FfPlace p;
 	p.u = lo;
 	p.t = (int)(seg - a.utts[lo].seg_off);
-	p.cm = p.t ? ff_centre(p.t - 1, a.fp_ms, a.fs) : 0;
-	p.c0 = ff_centre(p.t, a.fp_ms, a.fs);
-	p.cp = ff_centre(p.t + 1, a.fp_ms, a.fs);
-	p.a = p.t ? p.cm + 1 : 0;
+	const int t0 = a.utts[lo].t0;
+	const long long ta = (long long)t0 + p.t;  // the segment's number in the signal
+	const long long base = t0 ? ff_centre((long long)t0 - 1, a.fp_ms, a.fs) + 1 : 0;
+	p.cm = ta ? ff_centre(ta - 1, a.fp_ms, a.fs) - base : 0;
+	p.c0 = ff_centre(ta, a.fp_ms, a.fs) - base;
+	p.cp = ff_centre(ta + 1, a.fp_ms, a.fs) - base;
+	p.a = ta ? p.cm + 1 : 0;
 	const long long b = min((long long)a.utts[lo].n - 1, p.cp - 1);
 	p.Lt = (int)(b - p.a + 1);
 	return p;
@@ -360,14 +347,7 @@ namespace {
 
 int refuse(const char *why) { return fail(WC_ERR_INVALID, std::string("frame filter: ") + why); }
 
-int segments_of(const wc_frame_filter *f, int n) {
-	if (n <= 0) return 0;
-	const double h = f->fp_ms * (double)f->fs / 1000.0;
-	long long t = (long long)ceil((double)(n - 1) / h);
-	while (ff_centre(t, f->fp_ms, f->fs) < n - 1) ++t;
-	while (t > 0 && ff_centre(t - 1, f->fp_ms, f->fs) >= n - 1) --t;
-	return (int)(t + 1);
-}
+int segments_of(const wc_frame_filter *f, int n) { return (int)ff_segments(n, f->fp_ms, f->fs); }
 
 struct Totals {
 	long long x = 0, frames = 0, seg = 0;
@@ -402,6 +382,38 @@ void launch_ola(const FfArgs &a, int u0, unsigned tiles, unsigned nu, hipStream_
 	hipLaunchKernelGGL(filter_overlap_add_kernel<N>, dim3(tiles, nu), dim3(FO_T), 0, s, a, u0);
 }
 
+}  // namespace
+
+namespace wc {
+int filter_segments_launch(Device *dev, hipStream_t s, int fft_size, bool block, const FfArgs &a) {
+	const int N = fft_size;
+	int rc;
+	const bool wave = !block && (N == 1024 || N == 2048);
+	const char *name = wave ? "filter_segment_wave_kernel" : "filter_segment_kernel";
+	if ((rc = dev->time_begin(name, s))) return rc;
+	constexpr long long kGrid = 1ll << 30;
+	for (long long seg0 = 0; seg0 < a.total_seg; seg0 += kGrid) {
+		const unsigned n = (unsigned)(a.total_seg - seg0 < kGrid ? a.total_seg - seg0 : kGrid);
+		if (wave && N == 2048) hipLaunchKernelGGL(filter_segment_wave_kernel<2048>, dim3(n), dim3(64), 0, s, a, seg0);
+		else if (wave) hipLaunchKernelGGL(filter_segment_wave_kernel<1024>, dim3(n), dim3(64), 0, s, a, seg0);
+		else if (N == 512) launch_block<512>(a, seg0, n, s);
+		else if (N == 1024) launch_block<1024>(a, seg0, n, s);
+		else if (N == 2048) launch_block<2048>(a, seg0, n, s);
+		else launch_block<4096>(a, seg0, n, s);
+		WC_HIP(hipGetLastError());
+	}
+	return dev->time_end(name, s);
+}
+int filter_difference_launch(hipStream_t s, const double *d_to, const double *d_from, double *d_diff, long long total, int nd, int skip_energy) {
+	if (total <= 0) return WC_OK;
+	hipLaunchKernelGGL(filter_difference_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, d_to, d_from, d_diff, total, nd, skip_energy);
+	WC_HIP(hipGetLastError());
+	return WC_OK;
+}
+}  // namespace wc
+
+namespace {
+
 // the POWER / LOG call behind its checks
 int enqueue(wc_frame_filter *f, hipStream_t s, int n_utt, const double *d_x, const int *x_length, int kind, const double *d_rows,
 			const int *f_length, double *d_y, const Totals &tot) {
@@ -427,21 +439,7 @@ int enqueue(wc_frame_filter *f, hipStream_t s, int n_utt, const double *d_x, con
 	FfArgs a;
 	a.x = d_x; a.gain = d_rows; a.rows = f->rows.as<double>(); a.y = d_y; a.utts = d_utts; a.tw = dev->twiddle;
 	a.total_seg = tot.seg; a.fp_ms = f->fp_ms; a.n_utt = n_utt; a.fs = f->fs; a.kind = kind;
-	const bool wave = !f->block && (N == 1024 || N == 2048);
-	const char *name = wave ? "filter_segment_wave_kernel" : "filter_segment_kernel";
-	if ((rc = dev->time_begin(name, s))) return rc;
-	constexpr long long kGrid = 1ll << 30;
-	for (long long seg0 = 0; seg0 < tot.seg; seg0 += kGrid) {
-		const unsigned n = (unsigned)(tot.seg - seg0 < kGrid ? tot.seg - seg0 : kGrid);
-		if (wave && N == 2048) hipLaunchKernelGGL(filter_segment_wave_kernel<2048>, dim3(n), dim3(64), 0, s, a, seg0);
-		else if (wave) hipLaunchKernelGGL(filter_segment_wave_kernel<1024>, dim3(n), dim3(64), 0, s, a, seg0);
-		else if (N == 512) launch_block<512>(a, seg0, n, s);
-		else if (N == 1024) launch_block<1024>(a, seg0, n, s);
-		else if (N == 2048) launch_block<2048>(a, seg0, n, s);
-		else launch_block<4096>(a, seg0, n, s);
-		WC_HIP(hipGetLastError());
-	}
-	if ((rc = dev->time_end(name, s))) return rc;
+	if ((rc = filter_segments_launch(dev, s, N, f->block, a))) return rc;
 	if ((rc = dev->time_begin("filter_overlap_add_kernel", s))) return rc;
 	const unsigned tiles = (unsigned)((max_n + FO_TILE - 1) / FO_TILE);
 	for (int u0 = 0; u0 < n_utt; u0 += 65535) {
@@ -544,9 +542,7 @@ int wc_frame_filter_run_coded_device(wc_frame_filter *f, int n_utt, const double
 	if ((rc = f->dec.reserve(sizeof(double) * (size_t)tot.frames * (N / 2 + 1)))) return rc;
 	if ((rc = take(f, s))) return rc;
 	const long long total = tot.frames * nd;
-	hipLaunchKernelGGL(filter_difference_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, d_coded_to, d_coded_from,
-					   f->diff.as<double>(), total, nd, skip_energy);
-	WC_HIP(hipGetLastError());
+	if ((rc = filter_difference_launch(s, d_coded_to, d_coded_from, f->diff.as<double>(), total, nd, skip_energy))) return rc;
 	if ((rc = codec_decode_sp_launch(dev, s, N, tot.frames, nd, f->diff.as<double>(), f->dec.as<double>(), *pl))) return rc;
 	if ((rc = enqueue(f, s, n_utt, d_x, x_length, WC_FILTER_POWER, f->dec.as<double>(), f_length, d_y, tot))) return rc;
 	return hand(f, s);

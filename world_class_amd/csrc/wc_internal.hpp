@@ -142,4 +142,28 @@ void rng_state_at(uint64_t position, uint32_t state[4]);
 // device entry points implemented in the .hip files
 int launch_rng_fill(Device *dev, uint32_t *table, uint64_t first, uint64_t count);
 
+// Frame filtering's segments (wc_filter.hip), which the batch and the filter streams (wc_filter_stream.hip) place by the same record.
+// One per utterance -- for a stream: per stream that a push touches -- and one more behind the last whose seg_off is the call's segment
+// count.  t0 is the number of the record's first segment (the batch: 0).  x_off and row_off lead to the sample a_t0 and to row t0: n
+// and f_len count from there, and so do the segment's own offsets.  A segment past f_len reads row f_len - 1, the held one; with
+// f_len == 0 that is the row in front of row_off.
+struct FfUtt {
+	long long x_off, row_off, seg_off;
+	int n, f_len, S, t0;
+};
+struct FfArgs {
+	const double *x, *gain;
+	double *rows, *y;
+	const FfUtt *utts;
+	const double2 *tw;
+	long long total_seg;
+	double fp_ms;
+	int n_utt, fs, kind;
+};
+// the response rows of a.total_seg segments into a.rows, enqueued on s: the one-wavefront kernel at fft_size 1024 / 2048 unless block
+// is set, the workgroup-per-segment kernel otherwise (arguments already checked)
+int filter_segments_launch(Device *dev, hipStream_t s, int fft_size, bool block, const FfArgs &a);
+// the coded call's d = to - from over total values in rows of nd (from == nullptr: d = to; skip_energy: d[0] of a row is 0.0)
+int filter_difference_launch(hipStream_t s, const double *d_to, const double *d_from, double *d_diff, long long total, int nd, int skip_energy);
+
 }  // namespace wc
