@@ -36,7 +36,7 @@ def sources():
 def headers():
     inc = os.path.join(os.path.dirname(HERE), "include")
     hs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp"))
-    hs += [os.path.join(inc, f) for f in ("world_class_c.h", "world_class_io.h", "world_class_codec.h", "world_class_stream.h", "world_class_align_stream.h", "world_class_align_window.h", "world_class_align_lag.h", "world_class_track_morph.h", "world_class_track_morph_coded.h", "world_class_shard.h", "world_class_resample.h", "world_class_vresample.h", "world_class_warp.h", "world_class_warp_stream.h", "world_class_features.h", "world_class_mlpg_stream.h", "world_class_feature_stream.h", "world_class_gv.h", "world_class_gmm.h", "world_class_gmm_train.h", "world_class_filter.h", "world_class_filter_stream.h",
+    hs += [os.path.join(inc, f) for f in ("world_class_c.h", "world_class_io.h", "world_class_codec.h", "world_class_stream.h", "world_class_align_stream.h", "world_class_align_window.h", "world_class_align_lag.h", "world_class_track_morph.h", "world_class_track_morph_coded.h", "world_class_shard.h", "world_class_resample.h", "world_class_vresample.h", "world_class_warp.h", "world_class_warp_stream.h", "world_class_features.h", "world_class_mlpg_stream.h", "world_class_feature_stream.h", "world_class_gv.h", "world_class_gmm.h", "world_class_gmm_train.h", "world_class_parallel.h", "world_class_filter.h", "world_class_filter_stream.h",
                                           "world_matlabfunctions.hpp", "world_fft.hpp") if os.path.exists(os.path.join(inc, f))]
     return hs
 
